@@ -20,8 +20,12 @@ are all-gathered and re-split evenly (unordered pairs kept on one rank) for veri
 and each rank receives the SuperPoint features of exactly the keyframes its pairs touch
 (all_to_all); the counts are all-reduced.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--verify all|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--verify all|none] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full then runs the
+sub-benches on the same process and adds their objects to the line: configs[4] LoFTR,
+configs[0], keyframe ingestion, the stress size (--stress-keyframes), the CPU baseline.
 """
 import argparse
 import json
@@ -432,6 +436,47 @@ def stress_bench(n, k, dev):
     return out
 
 
+DUMP_KEYFRAMES = {"local_features": 4, "superpoint_keypoints": 256, "superpoint_descriptors": 8}
+
+
+def dump_outputs(path, gate, counts, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy --
+    the step's counts (float64, in sorted key order: accepted, features_exchanged_bytes if
+    sharded, gate_rejected_cross_floor, matches, ...), and the arrays the step left in the
+    gate: the [N, 768] GeM descriptors, the ordered pair list it verified, every local
+    keyframe's SuperPoint keypoint count and, for fixed seeded samples of DUMP_KEYFRAMES
+    local keyframes, the CricaVPR local features and the SuperPoint keypoints / descriptors
+    (rows past a keyframe's count zeroed: the extractor leaves them unwritten).  float32
+    as computed, 44 MB at the default size."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+
+    def sample(name):
+        rows = np.sort(rng.choice(gate.n_local, min(DUMP_KEYFRAMES[name], gate.n_local), replace=False))
+        return rows, torch.from_numpy(rows).to(gate.dev)
+    out = {"counts": np.array([counts[k_] for k_ in sorted(counts)], np.float64),
+           "descriptors": gate.gather.out.float().cpu().numpy()}
+    if gate.local_feats is not None:
+        rows, sel = sample("local_features")
+        out["local_features_keyframes"] = rows.astype(np.float64)
+        out["local_features"] = gate.local_feats.index_select(0, sel).cpu().numpy()
+    if gate.verify and gate.matcher == "lightglue":
+        cnt = gate.cnt_loc.view(-1).cpu().numpy()
+        out["superpoint_counts"] = cnt.astype(np.float64)
+        out["verified_pairs"] = np.stack(gate.last_pairs, 1).astype(np.float64)
+        for name, table, width in (("superpoint_keypoints", gate.kp_loc, 2), ("superpoint_descriptors", gate.ds_loc, 256)):
+            rows, sel = sample(name)
+            a = table.index_select(0, sel).view(len(rows), gate.kp, width).cpu().numpy()
+            a[np.arange(gate.kp)[None, :] >= cnt[rows][:, None]] = 0.0
+            out[name + "_keyframes"] = rows.astype(np.float64)
+            out[name] = a
+    size = sum(a.nbytes for a in out.values())
+    if size > 64e6:
+        raise ValueError(f"--dump-outputs: {size / 1e6:.0f} MB at {gate.N} keyframes, over the 64 MB it may write")
+    for name, a in out.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,12 +499,19 @@ def main():
     ap.add_argument("--k", type=int, default=20)  # configs[2]: top-20 candidates per query
     ap.add_argument("--places", type=int, default=600)
     ap.add_argument("--verify", choices=["all", "none"], default="all")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the f2 ingestion sub-object")
-    ap.add_argument("--loftr-pairs", type=int, default=1024, help="configs[4] LoFTR sub-object: gate pairs (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sub-benches and add their objects to the line: "
+                         "configs[4] LoFTR, configs[0], f2 ingestion, --stress-keyframes, the CPU baseline "
+                         "(without it: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ingest", action="store_true", help="with --full: skip the f2 ingestion sub-object")
+    ap.add_argument("--loftr-pairs", type=int, default=1024,
+                    help="with --full: configs[4] LoFTR sub-object: gate pairs (0: skip)")
     ap.add_argument("--stress-keyframes", type=int, default=0,
-                    help="also gate an N-keyframe sequence once warm (SURVEY §8d: 19163, the ORB-SLAM3 pose count) "
-                         "on one GPU and report it as the 'stress' sub-object (0: skip; one rank only)")
+                    help="with --full: also gate an N-keyframe sequence once warm (SURVEY §8d: 19163, the ORB-SLAM3 "
+                         "pose count) on one GPU and report it as the 'stress' sub-object (0: skip; one rank only)")
     ap.add_argument("--vit", choices=["split", "bf16"], default="split",
                     help="split: split-bf16 ViT (MLG_VIT_SPLIT, fp32-faithful descriptors); bf16: plain bf16 operands")
     args = ap.parse_args()
@@ -506,9 +558,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    counts = {}
+    counts, last = {}, {}
     for _ in range(args.steps):
-        for key, v in gate.step().items():
+        last = gate.step()
+        for key, v in last.items():
             counts[key] = counts.get(key, 0) + v
     torch.cuda.synchronize()
     if world > 1:
@@ -538,15 +591,18 @@ def main():
     steps = max(args.steps, 1)
     counts = {k_: int(v) // steps for k_, v in zip(keys, cv.cpu().tolist())}  # per step, all ranks
     N = args.keyframes
-    torch.cuda.empty_cache()  # the main gate's LightGlue workspace
-    lft = loftr_bench(frames, seq, labels, lo, dev, world, rank, args.loftr_pairs) if args.loftr_pairs > 0 else None
-    c0 = configs0_bench(frames, seq, labels, lo, dev) if rank == 0 else None
-    ing = ingest_bench(dev) if rank == 0 and not args.no_ingest else None
-    stress = None
-    if args.stress_keyframes > 0 and world == 1:
-        del gate, frames
-        torch.cuda.empty_cache()
-        stress = stress_bench(args.stress_keyframes, args.k, dev)
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, gate, last, f"_rank{rank}" if world > 1 else "")
+    lft = c0 = ing = stress = None
+    if args.full:
+        torch.cuda.empty_cache()  # the main gate's LightGlue workspace
+        lft = loftr_bench(frames, seq, labels, lo, dev, world, rank, args.loftr_pairs) if args.loftr_pairs > 0 else None
+        c0 = configs0_bench(frames, seq, labels, lo, dev) if rank == 0 else None
+        ing = ingest_bench(dev) if rank == 0 and not args.no_ingest else None
+        if args.stress_keyframes > 0 and world == 1:
+            del gate, frames
+            torch.cuda.empty_cache()
+            stress = stress_bench(args.stress_keyframes, args.k, dev)
 
     if rank == 0:
         avg_s = ms / 1e3 / max(cnt, 1)
@@ -610,7 +666,7 @@ def main():
             line["ingest"] = ing
         if stress:
             line["stress"] = stress
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the timed region (at world > 1 the other ranks wait at the
             # final barrier, so their processes leave the host cores to it)
             line["cpu_baseline"] = cpu_baseline(pairs_per_kf=(counts["pairs_verified"] / N) if args.verify == "all" else 0.0)

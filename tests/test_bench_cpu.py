@@ -6,6 +6,7 @@ import socket
 import sys
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -51,6 +52,48 @@ def test_all_reduce_helper_under_gloo(tmp_path):
     out = str(tmp_path / "r.npy")
     mp.spawn(_reduce_worker, args=(3, _free_port(), out), nprocs=3, join=True)
     assert np.load(out).tolist() == [3.5, 20.0, 9.0, 3.0]
+
+
+def test_dump_outputs_writes_the_steps_arrays(tmp_path):
+    """--dump-outputs on a stand-in gate with host tensors: one float .npy per name, the
+    same seeded keyframe samples on every call, SuperPoint rows past a keyframe's count
+    zeroed, the counts in sorted key order; over 64 MB it refuses."""
+    from types import SimpleNamespace
+    n, kp = 300, 8
+    g = torch.Generator().manual_seed(1)
+    cnt = torch.randint(0, kp + 1, (n, 1), generator=g, dtype=torch.int32)
+    gate = SimpleNamespace(
+        n_local=n, N=n, dev=torch.device("cpu"), kp=kp, verify=True, matcher="lightglue",
+        gather=SimpleNamespace(out=torch.randn(n, 768, generator=g)), local_feats=torch.randn(n, 5, 768, generator=g),
+        cnt_loc=cnt, kp_loc=torch.randn(n, kp * 2, generator=g) + 9.0, ds_loc=torch.randn(n, kp * 256, generator=g) + 9.0,
+        last_pairs=(np.arange(7, dtype=np.int32), np.arange(7, dtype=np.int32)[::-1].copy()))
+    counts = {"matches": 11, "accepted": 2, "pairs_verified": 7}
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(a, gate, counts)
+    bench.dump_outputs(b, gate, counts)
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) and "descriptors.npy" in names
+    out = {f[:-4]: np.load(os.path.join(a, f)) for f in names}
+    for f in names:
+        assert out[f[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(out[f[:-4]], np.load(os.path.join(b, f)))
+    assert out["counts"].tolist() == [2.0, 11.0, 7.0]
+    assert np.array_equal(out["descriptors"], gate.gather.out.numpy())
+    assert out["verified_pairs"].tolist() == [[i, 6 - i] for i in range(7)]
+    assert np.array_equal(out["superpoint_counts"], cnt.view(-1).numpy())
+    rows = out["local_features_keyframes"].astype(int)
+    assert len(rows) == bench.DUMP_KEYFRAMES["local_features"]
+    assert np.array_equal(out["local_features"], gate.local_feats.numpy()[rows])
+    for name, table, width in (("superpoint_keypoints", gate.kp_loc, 2), ("superpoint_descriptors", gate.ds_loc, 256)):
+        rows = out[name + "_keyframes"].astype(int)
+        assert len(rows) == min(bench.DUMP_KEYFRAMES[name], n) and len(set(rows)) == len(rows)
+        want = table.numpy()[rows].reshape(len(rows), kp, width).copy()
+        for i, r in enumerate(rows):
+            want[i, int(cnt[r]):] = 0.0
+        assert np.array_equal(out[name], want)
+    gate.gather.out = torch.zeros(21000, 768)
+    with pytest.raises(ValueError, match="64 MB"):
+        bench.dump_outputs(a, gate, counts)
 
 
 def test_same_model_compares_bits():

@@ -7,7 +7,7 @@ OUT="$REPO/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- \
-    python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_stdout.log" 2>&1
+    python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_stdout.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"; tail -2 "$OUT/bench_stdout.log"
 find "$OUT" -name "*stats*" | head
 exit $rc
