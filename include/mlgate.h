@@ -624,6 +624,54 @@ int mlg_png_decode_bgr(const uint8_t* const* data, const size_t* lens, int n, ui
                        int threads, int32_t* status);
 int mlg_png_load_bgr(const char* const* paths, int n, uint8_t* out, int H, int W, int threads, int32_t* status);
 
+/* JPEG keyframes (the sorted(*.jpg) half of process_image_sequence,
+ * place_recognition.py:960-973) in two halves.  The host half parses the markers and
+ * Huffman-decodes a batch on `threads` host threads into quantised DCT coefficients;
+ * the device half (mlg_jpeg_pixels) dequantises, runs libjpeg's jpeg_idct_islow, the
+ * fancy chroma upsampling and the YCbCr -> BGR conversion, so its pixels are
+ * cv2.imread's (libjpeg-turbo defaults) bit for bit.
+ *
+ * Accepted: baseline / extended sequential Huffman (SOF0, SOF1), 8 bit, one interleaved
+ * scan, gray or YCbCr (JFIF, or Adobe APP14 transform 1) with luma sampling 1x1, 2x1 or
+ * 2x2 over 1x1 chroma; DRI / RSTn, 8- and 16-bit DQT.  status[i]: 0; MLG_EUNSUP for a
+ * valid stream outside that set (progressive, arithmetic, lossless, 12 bit, CMYK / RGB,
+ * other samplings, several scans, an Exif orientation other than 1); MLG_EINVAL for an
+ * unreadable or corrupt one; MLG_ESIZE for a supported stream that is not H x W.
+ *
+ * Per image i (HOST pointers, pinned in practice):
+ *   coefs + i * mlg_jpeg_coef_bytes(H, W) / 2: int16, de-zigzagged (natural order), not
+ *     dequantised, zero-filled, component-major [block_rows_c][block_cols_c][64]; the
+ *     block counts are whole MCUs x the sampling factors;
+ *   qtabs + i * 3 * 64: uint16 [3][64], natural order, the table of each component;
+ *   params + i * MLG_JPEG_PARAMS: int32 record
+ *     [0] components (1 or 3)  [1] luma h  [2] luma v  [3] 0
+ *     [4 + 4c] block_cols_c  [5 + 4c] block_rows_c  [6 + 4c] offset of component c in
+ *     int16 elements from the image's base  [7 + 4c] 0.
+ *     An image whose status is not 0 gets an all-zero record: mlg_jpeg_pixels leaves its
+ *     frame untouched.
+ * DC prediction and coefficient values wrap to int16 as libjpeg's JCOEF does. */
+#define MLG_EUNSUP (-5)
+#define MLG_JPEG_PARAMS 16
+/* info[8]: width, height, components, luma h, luma v, supported (0 / 1), 0, 0.  Reads no
+ * further than SOS; MLG_EINVAL if the bytes are not a JPEG header. */
+int mlg_jpeg_info(const uint8_t* data, size_t len, int32_t* info);
+/* Worst-case coefficient bytes of one H x W image over the accepted samplings (a
+ * multiple of 128), so a batch has fixed strides whatever each file's subsampling. */
+size_t mlg_jpeg_coef_bytes(int H, int W);
+int mlg_jpeg_coefs_decode(const uint8_t* const* data, const size_t* lens, int n, int16_t* coefs, uint16_t* qtabs,
+                          int32_t* params, int H, int W, int threads, int32_t* status);
+int mlg_jpeg_coefs_load(const char* const* paths, int n, int16_t* coefs, uint16_t* qtabs, int32_t* params, int H,
+                        int W, int threads, int32_t* status);
+/* HOST: 0 if the n records are exactly what an H x W image of their component count and
+ * sampling has (block counts) and every component lies inside coef_bytes; else
+ * MLG_EINVAL.  mlg_jpeg_pixels indexes memory through the records only, so callers run
+ * this before a launch (the torch op does). */
+int mlg_jpeg_params_check(const int32_t* params, int n, int H, int W, size_t coef_bytes);
+/* DEVICE pointers: coefficients (image stride mlg_jpeg_coef_bytes(H, W)), tables and
+ * validated records of n images -> out_bgr uint8 [n, H, W, 3].  One kernel; no workspace. */
+int mlg_jpeg_pixels(const int16_t* coefs, const uint16_t* qtabs, const int32_t* params, int n, int H, int W,
+                    uint8_t* out_bgr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

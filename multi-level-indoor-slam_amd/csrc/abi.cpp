@@ -126,6 +126,7 @@ const char* mlg_strerror(int status) {
         case MLG_EHIP: return "HIP launch error";
         case MLG_ENOMEM: return "workspace too small";
         case MLG_ESIZE: return "image size differs from the batch size";
+        case MLG_EUNSUP: return "valid stream outside the supported subset";
         default: return "unknown mlgate status";
     }
 }

@@ -814,6 +814,88 @@ std::tuple<Tensor, Tensor> png_decode(std::vector<Tensor> blobs, int64_t H, int6
     return {out, status};
 }
 
+// JPEG: the host half fills three caller-owned host tensors (views of one pinned staging
+// buffer in mlgate.ingest); image i lies at coefs + i * mlg_jpeg_coef_bytes(H, W).
+size_t jpeg_check_host(int64_t n, const Tensor& coefs, const Tensor& qtabs, const Tensor& params, int64_t H,
+                       int64_t W, bool device) {
+    TORCH_CHECK(H > 0 && W > 0 && H <= 65535 && W <= 65535 && n <= 65535, "jpeg: bad batch ", n, " x ", H, " x ", W);
+    const size_t per = mlg_jpeg_coef_bytes((int)H, (int)W);
+    want(coefs, at::kShort, "coefs", device);
+    want(qtabs, at::kUInt16, "qtabs", device);
+    TORCH_CHECK((size_t)coefs.numel() * 2 >= (size_t)n * per, "coefs: needs ", (size_t)n * per, " bytes, has ",
+                coefs.numel() * 2);
+    TORCH_CHECK(qtabs.numel() >= n * 192, "qtabs: needs ", n * 192, " elements, has ", qtabs.numel());
+    TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() >= n * MLG_JPEG_PARAMS,
+                "params: expected contiguous int32 with ", n * MLG_JPEG_PARAMS, " elements");
+    return per;
+}
+
+Tensor jpeg_coefs_load_into(std::vector<std::string> paths, Tensor coefs, Tensor qtabs, Tensor params, int64_t H,
+                            int64_t W, int64_t threads) {
+    const int64_t n = (int64_t)paths.size();
+    jpeg_check_host(n, coefs, qtabs, params, H, W, false);
+    TORCH_CHECK(params.device().is_cpu(), "params must be a host tensor");
+    std::vector<const char*> cps(paths.size());
+    for (size_t i = 0; i < paths.size(); ++i) cps[i] = paths[i].c_str();
+    Tensor status = at::zeros({n}, at::TensorOptions().dtype(at::kInt));
+    check_rc(mlg_jpeg_coefs_load(cps.data(), (int)n, mp<int16_t>(coefs), mp<uint16_t>(qtabs), mp<int32_t>(params),
+                                 (int)H, (int)W, (int)threads, mp<int32_t>(status)), "mlg_jpeg_coefs_load");
+    return status;
+}
+
+Tensor jpeg_coefs_decode(std::vector<Tensor> blobs, Tensor coefs, Tensor qtabs, Tensor params, int64_t H, int64_t W,
+                         int64_t threads) {
+    const int64_t n = (int64_t)blobs.size();
+    jpeg_check_host(n, coefs, qtabs, params, H, W, false);
+    TORCH_CHECK(params.device().is_cpu(), "params must be a host tensor");
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<size_t> lens(n);
+    for (int64_t i = 0; i < n; ++i) {
+        want(blobs[i], at::kByte, "blob", false);
+        ptrs[i] = cp<uint8_t>(blobs[i]);
+        lens[i] = (size_t)blobs[i].numel();
+    }
+    Tensor status = at::zeros({n}, at::TensorOptions().dtype(at::kInt));
+    check_rc(mlg_jpeg_coefs_decode(ptrs.data(), lens.data(), (int)n, mp<int16_t>(coefs), mp<uint16_t>(qtabs),
+                                   mp<int32_t>(params), (int)H, (int)W, (int)threads, mp<int32_t>(status)),
+             "mlg_jpeg_coefs_decode");
+    return status;
+}
+
+// [status, width, height, components, luma h, luma v, supported, 0, 0] of one blob's header
+Tensor jpeg_info(const Tensor& blob) {
+    want(blob, at::kByte, "blob", false);
+    Tensor out = at::zeros({9}, at::TensorOptions().dtype(at::kInt));
+    int32_t* o = mp<int32_t>(out);
+    o[0] = blob.numel() ? mlg_jpeg_info(cp<uint8_t>(blob), (size_t)blob.numel(), o + 1) : MLG_EINVAL;
+    return out;
+}
+
+int64_t jpeg_coef_bytes(int64_t H, int64_t W) {
+    return H > 0 && W > 0 && H <= 65535 && W <= 65535 ? (int64_t)mlg_jpeg_coef_bytes((int)H, (int)W) : 0;
+}
+
+// Device half.  The kernel indexes the coefficient buffer through `params` alone, so every
+// record is checked on the host against the tensors' sizes before the launch.  `params` is
+// normally the host tensor the decoder filled (checked, then uploaded); a device tensor is
+// read back first (one synchronising copy of 64 B per image).
+Tensor jpeg_pixels(const Tensor& coefs, const Tensor& qtabs, const Tensor& params, int64_t H, int64_t W) {
+    TORCH_CHECK(params.dim() >= 1 && params.numel() % MLG_JPEG_PARAMS == 0, "params: expected [n, ", MLG_JPEG_PARAMS,
+                "] int32");
+    const int64_t n = params.numel() / MLG_JPEG_PARAMS;
+    const size_t per = jpeg_check_host(n, coefs, qtabs, params, H, W, true);
+    const c10::DeviceGuard guard(coefs.device());
+    TORCH_CHECK(qtabs.device() == coefs.device(), "qtabs and coefs must be on one device");
+    const Tensor host = params.device().is_cpu() ? params : params.cpu();
+    check_rc(mlg_jpeg_params_check(cp<int32_t>(host), (int)n, (int)H, (int)W, per), "jpeg_pixels: parameter records");
+    const Tensor dev = params.is_cuda() ? params : params.to(coefs.device());
+    TORCH_CHECK(dev.device() == coefs.device(), "params and coefs must be on one device");
+    Tensor out = at::empty({n, H, W, 3}, coefs.options().dtype(at::kByte));
+    check_rc(mlg_jpeg_pixels(cp<int16_t>(coefs), cp<uint16_t>(qtabs), cp<int32_t>(dev), (int)n, (int)H, (int)W,
+                             mp<uint8_t>(out), stream_of(coefs)), "mlg_jpeg_pixels");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mlgate, m) {
@@ -855,6 +937,13 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("orb_match(Tensor desc, Tensor counts, Tensor pair_a, Tensor pair_b) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("png_load_into(str[] paths, Tensor(a!) out, int H, int W, int threads) -> Tensor");
     m.def("png_decode(Tensor[] blobs, int H, int W, int threads) -> (Tensor, Tensor)");
+    m.def("jpeg_coefs_load_into(str[] paths, Tensor(a!) coefs, Tensor(b!) qtabs, Tensor(c!) params, int H, int W, "
+          "int threads) -> Tensor");
+    m.def("jpeg_coefs_decode(Tensor[] blobs, Tensor(a!) coefs, Tensor(b!) qtabs, Tensor(c!) params, int H, int W, "
+          "int threads) -> Tensor");
+    m.def("jpeg_info(Tensor blob) -> Tensor");
+    m.def("jpeg_coef_bytes(int H, int W) -> int");
+    m.def("jpeg_pixels(Tensor coefs, Tensor qtabs, Tensor params, int H, int W) -> Tensor");
     m.def("prof_enable(int mask) -> int");
     m.def("prof_reset() -> int");
     m.def("prof_read(int slot) -> (float, int, float)");
@@ -880,6 +969,7 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("superglue", &superglue);
     m.impl("loftr_match", &loftr_match);
     m.impl("pillow_resize_224", &pillow_resize_224);
+    m.impl("jpeg_pixels", &jpeg_pixels);
     m.impl("plane_ransac", &plane_ransac);
     m.impl("proximity", &proximity);
     m.impl("lg_orient", &lg_orient);
@@ -890,10 +980,14 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
 TORCH_LIBRARY_IMPL(mlgate, CPU, m) {
     m.impl("png_load_into", &png_load_into);
     m.impl("png_decode", &png_decode);
+    m.impl("jpeg_coefs_load_into", &jpeg_coefs_load_into);
+    m.impl("jpeg_coefs_decode", &jpeg_coefs_decode);
+    m.impl("jpeg_info", &jpeg_info);
 }
 
 TORCH_LIBRARY_IMPL(mlgate, CompositeExplicitAutograd, m) {
     m.impl("prof_enable", &prof_enable);
+    m.impl("jpeg_coef_bytes", &jpeg_coef_bytes);
     m.impl("prof_reset", &prof_reset);
     m.impl("prof_read", &prof_read);
 }

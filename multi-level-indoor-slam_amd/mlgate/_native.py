@@ -19,6 +19,7 @@ TORCH_LIB_PATH = os.path.join(_HERE, "libmlgate_torch.so")
 OPS = ("vit_forward_into", "salad_forward", "knn_gate", "knn_query", "row_normalize", "similarity", "xcorr_score", "xcorr_batch",
        "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
+       "jpeg_pixels",
        "prof_enable", "prof_reset", "prof_read")
 
 
@@ -109,6 +110,13 @@ EXPORTS = {
     "mlg_png_info": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mlg_png_decode_bgr": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mlg_png_load_bgr": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mlg_jpeg_info": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "mlg_jpeg_coef_bytes": (c_size_t, [c_int, c_int]),
+    "mlg_jpeg_coefs_decode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p]),
+    "mlg_jpeg_coefs_load": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mlg_jpeg_params_check": (c_int, [c_void_p, c_int, c_int, c_int, c_size_t]),
+    "mlg_jpeg_pixels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

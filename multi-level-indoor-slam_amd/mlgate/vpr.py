@@ -502,11 +502,13 @@ def process_image_sequence(image_dir: Union[str, Path], timestamps: np.ndarray, 
     """Sorted *.png then *.jpg of a directory -> database -> floor-gated loop closures
     (place_recognition.py:936-991).
 
-    PNG keyframes (what bag_utils.extract_images writes) are decoded by the native
-    loader (mlgate.ingest: host thread pool -> pinned buffer -> HBM on a side stream)
-    and added in device batches; the database, warnings and matches are those of the
-    reference's one-image-at-a-time loop.  *.jpg files go through cv2.imread when OpenCV is
-    installed, else through Pillow's libjpeg(-turbo) decode (mlgate.ingest.jpeg_reader)."""
+    Both kinds go through one mlgate.ingest.KeyframeStream and are added in device
+    batches: PNG keyframes (what bag_utils.extract_images writes) are decoded on a host
+    thread pool; *.jpg files are Huffman-decoded there and finished on the GPU (IDCT,
+    upsampling, colour: libjpeg-turbo's integers, so cv2.imread's pixels).  A JPEG the
+    native path declines is read by mlgate.ingest.jpeg_reader() (cv2.imread when OpenCV is
+    installed, else Pillow's libjpeg decode; its ImportError is raised only then).  The
+    database, warnings and matches are those of the reference's one-image-at-a-time loop."""
     from . import ingest
     image_dir = Path(image_dir)
     spr = SemanticPlaceRecognition(vpr_method=vpr_method, device=device)
@@ -515,25 +517,12 @@ def process_image_sequence(image_dir: Union[str, Path], timestamps: np.ndarray, 
         warnings.warn(f"Number of images ({len(files)}) != timestamps ({len(timestamps)}). Using minimum of both.")
     n = min(len(files), len(timestamps), len(floor_labels))
     files = files[:n]
-    jpeg_read = None
-    if any(f.suffix == '.jpg' for f in files):
-        jpeg_read = ingest.jpeg_reader()  # cv2.imread, else Pillow's libjpeg decode; ImportError if neither
     print(f"Processing {n} images with {vpr_method}...")
-    pngs = [i for i, f in enumerate(files) if f.suffix == '.png']
-    for idx, frames in ingest.KeyframeStream([files[i] for i in pngs], device=device):
-        rows = [pngs[j] for j in idx]
+    for rows, frames in ingest.KeyframeStream(files, device=device):
         spr.add_images(frames, [timestamps[i] for i in rows], [int(floor_labels[i]) for i in rows],
                        [str(files[i]) for i in rows])
         for i in rows:
             if (i + 1) % 100 == 0:
                 print(f"  Processed {i + 1}/{n} images")
-    for i in range(len(pngs), n):  # *.jpg files sort after every *.png file
-        img = jpeg_read(files[i])
-        if img is None:
-            warnings.warn(f"Failed to load image: {files[i]}")
-            continue
-        spr.add_image(image=img, timestamp=timestamps[i], floor_label=int(floor_labels[i]), image_path=str(files[i]))
-        if (i + 1) % 100 == 0:
-            print(f"  Processed {i + 1}/{n} images")
     print("Finding loop closure candidates...")
     return spr, spr.find_loop_closures(enable_floor_gating=True)
