@@ -100,7 +100,6 @@ struct EpiSimLoFTR {
     __device__ void apply(int m, int n, const f32x4& v, const Col&, const Row&, const Pre&) const {
         store(m, n, sc(v[0]), sc(v[1]), sc(v[2]), sc(v[3]));
     }
-    __device__ void operator()(int m, int n, const f32x4& v) const { apply(m, n, v, Col{}, Row{}, Pre{}); }
 };
 
 struct EpiBiasBF16 {  // y = acc + b  -> bf16
@@ -133,17 +132,9 @@ struct EpiBiasGeluBF16 {
 // y = gelu(acc + b) as the split pair: hi = bf16(y) at column n, lo = bf16(y - hi) at
 // column n + lo_col of the same row (the [hi | lo] A rows of the split fc2 GEMM).  GELU as
 // common.h gelu_poly2 (|error| <= 1e-6, below the pair's 2^-17 relative representation
-// error for |y| > 0.13; erff here made fc1 epilogue-bound: MLG_SPLIT_GELU_ERF=1 keeps it
-// for A/B)
-#ifndef MLG_SPLIT_GELU_ERF
-#define MLG_SPLIT_GELU_ERF 0
-#endif
-#ifndef MLG_EPI_PROBE
-#define MLG_EPI_PROBE 0  // timing-probe builds only (results wrong): 4 no fc1 stores, 8 no GELU
-#endif
+// error for |y| > 0.13; erff here made fc1 epilogue-bound)
 struct EpiBiasGeluSplit {
     bf16_t* C; int ldc; int lo_col; const float* bias;
-    __device__ static float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f)); }
     // batched form (epi_tile): column data, row data, per-fragment prefetch, apply
     struct Col { float4 b; };
     struct Row { size_t key = 0; };  // (staged form: unused)
@@ -157,13 +148,9 @@ struct EpiBiasGeluSplit {
     __device__ bool staged_wave(int) const { return true; }
     __device__ void stage2(const f32x4& v, const Col& c, uint2& h, uint2& l) const {
         const float4 b = c.b;
-#if MLG_SPLIT_GELU_ERF
-        split_bf16x4(gelu(v[0] + b.x), gelu(v[1] + b.y), gelu(v[2] + b.z), gelu(v[3] + b.w), h, l);
-#else
         const f32x2 g01 = gelu_poly2(f32x2{v[0] + b.x, v[1] + b.y});
         const f32x2 g23 = gelu_poly2(f32x2{v[2] + b.z, v[3] + b.w});
         split_bf16x4(g01.x, g01.y, g23.x, g23.y, h, l);
-#endif
     }
     __device__ void put(int m, int n, int plane, size_t, const uint4& d) const {
         *reinterpret_cast<uint4*>(C + (size_t)m * ldc + (plane ? lo_col : 0) + n) = d;
@@ -171,22 +158,12 @@ struct EpiBiasGeluSplit {
     __device__ void apply(int m, int n, const f32x4& v, const Col& c, const Row&, const Pre&) const {
         const float4 b = c.b;
         uint2 h, l;
-#if MLG_SPLIT_GELU_ERF
-        split_bf16x4(gelu(v[0] + b.x), gelu(v[1] + b.y), gelu(v[2] + b.z), gelu(v[3] + b.w), h, l);
-#elif MLG_EPI_PROBE & 8  // timing probe only: no GELU
-        split_bf16x4(v[0] + b.x, v[1] + b.y, v[2] + b.z, v[3] + b.w, h, l);
-#else
         const f32x2 g01 = gelu_poly2(f32x2{v[0] + b.x, v[1] + b.y});
         const f32x2 g23 = gelu_poly2(f32x2{v[2] + b.z, v[3] + b.w});
         split_bf16x4(g01.x, g01.y, g23.x, g23.y, h, l);
-#endif
-#if MLG_EPI_PROBE & 4  // timing probe only: stores kept alive by an impossible test
-        if (h.x != 0x7f817f81u) return;
-#endif
         *reinterpret_cast<uint2*>(C + (size_t)m * ldc + n) = h;
         *reinterpret_cast<uint2*>(C + (size_t)m * ldc + lo_col + n) = l;
     }
-    __device__ void operator()(int m, int n, const f32x4& v) const { apply(m, n, v, col(n), Row{}, Pre{}); }
 };
 
 struct EpiResidual {  // X += gamma * (acc + b)   (attn.proj / mlp.fc2 + LayerScale + residual)
@@ -266,7 +243,6 @@ struct EpiQKVSplit {
         return {(size_t)bi * Tpad + t};
     }
     __device__ Pre pre(int, int, const Col&, const Row&) const { return {}; }
-    __device__ void operator()(int m, int n, const f32x4& v) const { apply(m, n, v, col(n), row(m), Pre{}); }
     // staged form (k_gemm256s) for the Q / K waves (a wave's 64 columns are one head of one
     // of q, k, v): whole 128-B token rows of the head-major planes; V^T keeps apply
     static constexpr int STAGED = 1;
@@ -335,13 +311,10 @@ struct EpiBiasAddRelu {
 // Generic conv / linear epilogue (LoFTR, loftr.hip): y = acc (+ bias) (+ R[m, n]), then
 // act 1 = ReLU, 2 = LeakyReLU(0.01), 3 = elu + 1 on columns < act_cols; stored as f32
 // (X, ldx) and / or bf16 (C, ldc), either may be null.
-#ifndef MLG_GEMM_ROW_STAGED
-#define MLG_GEMM_ROW_STAGED 1  // 0: EpiConv fragment-at-a-time in k_gemm256 (A/B arm)
-#endif
 struct EpiConv {
     // row-major outputs / residual: k_gemm256 runs it from an LDS row image (whole-row
     // accesses) -- see row_staged below
-    static constexpr bool ROW_STAGED = MLG_GEMM_ROW_STAGED;
+    static constexpr bool ROW_STAGED = true;
     const float* bias; const float* R; int ldr; float* X; int ldx; bf16_t* C; int ldc; int act; int act_cols;
     float vdiv = 0.f;  // != 0: columns >= act_cols divided by it (LoFTR's values / v_length)
     __device__ void operator()(int m, int n, const f32x4& v) const {
@@ -864,16 +837,8 @@ struct staged_of { static constexpr int value = 0; };
 template <class E>
 struct staged_of<E, std::void_t<decltype(E::STAGED)>> { static constexpr int value = E::STAGED; };
 
-// MLG_S256_PRIO: s_setprio(1) / (0) around each MFMA cluster of k_gemm256s (the guide's
-// T5: hipcc then keeps the cluster between its barriers)
-#ifndef MLG_S256_PRIO
-#define MLG_S256_PRIO 1
-#endif
-#if MLG_S256_PRIO
-#define S256_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define S256_PRIO(p) ((void)0)
-#endif
+// s_setprio(1) / (0) around each MFMA cluster of k_gemm256s: hipcc then keeps the cluster
+// between its barriers (about -1 % on qkv / proj / fc2, profiles/r04aq_ab_split_gemm_setprio.txt)
 template <class Epi>
 __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                     int M, int N, int K0, int lda, int ldw, Epi epi, int nb,
@@ -945,20 +910,20 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
             const int row = wm * 128 + j * 16 + (lane & 15);                                               \
             af[j] = *reinterpret_cast<const bf16x8*>((ST) + soff<32>(row, ch));                            \
         }                                                                                                  \
-        S256_PRIO(1);                                                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                     \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i) {      \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], af[j], acc[i][j], 0, 0, 0);         \
         }                                                                                                  \
-        S256_PRIO(0);                                                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                     \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                    \
             const int row = wm * 128 + j * 16 + (lane & 15);                                               \
             af[j] = *reinterpret_cast<const bf16x8*>((ST) + PLANE + soff<32>(row, ch));                    \
         }                                                                                                  \
-        S256_PRIO(1);                                                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                     \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i)        \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
-        S256_PRIO(0);                                                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                     \
     }
 
     S256_DMA(st0, oa, sa, sb, 0);
@@ -1131,127 +1096,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
 #undef S256_DMA
 }
 
-// Split-bf16 GEMM, 192 x 192 form (MLG_SPLIT_TILE=192): the same three products per
-// K-step of 32 as k_gemm256s on a 192 x 192 tile, whose four operand planes (48 KiB) fit a
-// THREE-stage LDS-DMA ring (144 KiB): each K-step's planes are fetched two compute steps
-// ahead instead of one.  The ring runs on across the workgroup's output tiles (flat step
-// index over its tiles; steps past the last re-fetch the last one into a slot already
-// consumed).  Same per-output MFMA order as k_gemm256s, so the same bits.
-template <class Epi>
-__global__ __launch_bounds__(512, 1) void k_gemm192s(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
-                                                    int M, int N, int K0, int lda, int ldw, Epi epi) {
-    constexpr int BK = 32, TM = 192, TN = 192;
-    constexpr int PLANE = TM * BK * 2;  // 12 KiB
-    constexpr int STAGE = 4 * PLANE;    // A_hi, A_lo, W_hi, W_lo
-    constexpr int PIECES = 6;           // 1 KiB DMA wave-instructions per wave and stage (48 / 8 waves)
-    __shared__ __attribute__((aligned(16))) char ring[3 * STAGE];
-    // wave index through readfirstlane: the DMA bases derived from it stay in SGPRs
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nN = N / TN, nM = (M + TM - 1) / TM, ntiles = nN * nM;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int tx = (ntiles + 7) >> 3;
-    const int tile_end = min((xcd + 1) * tx, ntiles);
-    const int tile0 = xcd * tx + (blockIdx.x >> 3);
-    if (tile0 >= tile_end) return;
-    const int ntl = (tile_end - tile0 + per_xcd - 1) / per_xcd;
-    const int nk = K0 / BK;
-    const int S = ntl * nk;
-
-    const int lr = lane >> 2, lp = lane & 3;
-    const int wm = wave & 1, wn = wave >> 1;
-    // piece i of this wave: plane pl = p / 12 (0 A_hi, 1 A_lo, 2 W_hi, 3 W_lo), rows 16 (p % 12) ..
-    int prow[PIECES], pplane[PIECES];
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-        const int p = wave * PIECES + i;
-        pplane[i] = p / 12;
-        prow[i] = (p % 12) * 16 + lr;
-    }
-    auto issue = [&](int st, int slot) {  // DMA of flat step st into ring slot `slot`
-        const int q = st / nk, k = st - q * nk;
-        const int tile = tile0 + q * per_xcd;
-        const int m0 = (tile / nN) * TM, n0 = (tile - (tile / nN) * nN) * TN;
-        const unsigned b = lds_addr(ring + slot * STAGE);
-#pragma unroll
-        for (int i = 0; i < PIECES; ++i) {
-            const int row = prow[i], pl = pplane[i];
-            const int sw = (lp ^ ((row >> 1) & 3)) * 8;
-            const unsigned dst = b + pl * PLANE + (row - lr) * 64;
-            if (pl < 2) {
-                const unsigned off = (unsigned)((min(m0 + row, M - 1) - m0) * lda + sw) * 2u;
-                dma16s(off, A + (size_t)m0 * lda + k * BK + (pl ? K0 : 0), dst);
-            } else {
-                const unsigned off = (unsigned)(row * ldw + sw) * 2u;
-                dma16s(off, W + (size_t)n0 * ldw + k * BK + (pl == 3 ? K0 : 0), dst);
-            }
-        }
-    };
-    f32x4 acc[3][6];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    issue(0, 0);
-    issue(min(1, S - 1), 1);
-    __builtin_amdgcn_s_waitcnt(0xF70 | PIECES);  // vmcnt(6): step 0 has landed
-    __builtin_amdgcn_s_barrier();
-    const int ch = lane >> 4;
-    for (int st = 0; st < S; ++st) {
-        issue(min(st + 2, S - 1), (st + 2) % 3);  // into the slot step st - 1 used (all waves are past it)
-        const char* P = ring + (st % 3) * STAGE;
-        {
-            bf16x8 af[6], wh[3], wl[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int row = wn * 48 + i * 16 + (lane & 15);
-                wh[i] = *reinterpret_cast<const bf16x8*>(P + 2 * PLANE + soff<32>(row, ch));
-                wl[i] = *reinterpret_cast<const bf16x8*>(P + 3 * PLANE + soff<32>(row, ch));
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int row = wm * 96 + j * 16 + (lane & 15);
-                af[j] = *reinterpret_cast<const bf16x8*>(P + soff<32>(row, ch));
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], af[j], acc[i][j], 0, 0, 0);
-                }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int row = wm * 96 + j * 16 + (lane & 15);
-                af[j] = *reinterpret_cast<const bf16x8*>(P + PLANE + soff<32>(row, ch));
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);
-        }
-        const int q = st / nk;
-        if (st - q * nk == nk - 1) {  // the tile's last K-step: epilogue
-            const int tile = tile0 + q * per_xcd;
-            const int mt = tile / nN, m0 = mt * TM, n0 = (tile - mt * nN) * TN;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    const int n = n0 + wn * 48 + i * 16 + (lane >> 4) * 4;
-                    const int m = m0 + wm * 96 + j * 16 + (lane & 15);
-                    if (m < M) epi(m, n, acc[i][j]);
-                    acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            __builtin_amdgcn_s_waitcnt(0xF70);  // vmcnt(0): stores counted there too
-        } else {
-            __builtin_amdgcn_s_waitcnt(0xF70 | PIECES);  // vmcnt(6): step st + 1 has landed
-        }
-        __builtin_amdgcn_s_barrier();
-    }
-    __builtin_amdgcn_s_waitcnt(0xF70);
-}
-
 // Variant 5: the 256 x 256 persistent tile of k_gemm256 with K-tiles of 32 in a 4-deep
 // LDS ring (4 x 32 KiB): the DMA of K-tile t + 3 is issued when t is computed, so three
 // compute steps (not one) hide each tile's fetch; the ring runs on across output tiles
@@ -1381,9 +1225,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm256q(const bf16_t* __restrict__ 
 // the zero padding read a 16-B zero line (`zero`).  TN = 256: 8 waves 2 (M) x 4 (N) of
 // 128 x 64; TN = 128: 4 (M) x 2 (N) of 64 x 64.  Same MFMA k order as the explicit
 // im2col GEMM, so the same bits.
-#ifndef MLG_CONV_STAGED
-#define MLG_CONV_STAGED 1
-#endif
 struct ConvGeom {
     const bf16_t* in; const bf16_t* zero; int H, W, C, kw, s, pad, Ho, Wo;
 };
@@ -1494,23 +1335,11 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
             __builtin_amdgcn_s_barrier();
         }
         const int mt = tile / nN, m0 = mt * TM, n0 = (tile - mt * nN) * TN;
-        if constexpr (MLG_CONV_STAGED) {
-            // row-staged (gemm256_rows_epilogue; timing probe with the epilogue skipped: the
-            // LoFTR backbone 29 % faster, the staged form -3 %, profiles/
-            // r06r_ab_conv_staged_epilogue.txt)
-            gemm256_rows_epilogue<RM, STAGE / 8>(epi, acc, st1 + wave * (STAGE / 8), m0 + wm * RM, n0 + wn * 64, M,
-                                                 lane);
-            __syncthreads();  // every wave's image read: the next tile DMAs into st1
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < JM; ++j) {
-                    const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-                    const int m = m0 + wm * RM + j * 16 + (lane & 15);
-                    if (m < M) epi(m, n, acc[i][j]);
-                }
-        }
+        // row-staged (gemm256_rows_epilogue; timing probe with the epilogue skipped: the
+        // LoFTR backbone 29 % faster; the staged form -3 % against fragment-at-a-time epi()
+        // calls, bit-identical, profiles/r06r_ab_conv_staged_epilogue.txt)
+        gemm256_rows_epilogue<RM, STAGE / 8>(epi, acc, st1 + wave * (STAGE / 8), m0 + wm * RM, n0 + wn * 64, M, lane);
+        __syncthreads();  // every wave's image read: the next tile DMAs into st1
         sb = nsb;
     }
     __builtin_amdgcn_s_waitcnt(0xF70);
@@ -1573,11 +1402,9 @@ int launch(const bf16_t* A, const bf16_t* W, int M, int N, int K, int lda, int l
 }
 
 // Split-bf16 GEMM (MLG_VIT_SPLIT): A rows [A_hi | A_lo] of K0 each (lda >= 2 K0), W rows
-// [W_hi | W_lo] (ldw >= 2 K0); dma::k_gemm256s
+// [W_hi | W_lo] (ldw >= 2 K0); dma::k_gemm256s.  (A 192 x 192 tile on a three-stage LDS-DMA
+// ring was bit-identical and 12-25 % slower, profiles/r04n_split_gemm_ab.txt.)
 template <class Epi>
-#ifndef MLG_SPLIT_TILE
-#define MLG_SPLIT_TILE 256
-#endif
 int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda, int ldw, Epi epi, hipStream_t s,
                  int nb = 1, long sA = 0, long sW = 0) {
     g_num_cus = num_cus();
@@ -1586,13 +1413,6 @@ int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda
     // batched products: staged-f32 epilogues only (their row index is the only per-problem
     // output coordinate), 16-B aligned problem bases
     if (nb < 1 || (nb > 1 && (dma::staged_of<Epi>::value != 2 || ((sA | sW) & 7)))) return MLG_EINVAL;
-    if (MLG_SPLIT_TILE == 192 && N % 192 == 0 && nb == 1) {
-        const long nt = (long)(N / 192) * ((M + 191) / 192);
-        const long g = std::min<long>(g_num_cus, (nt + 7) / 8 * 8);
-        hipLaunchKernelGGL(dma::k_gemm192s<Epi>, dim3((unsigned)g), dim3(512), 0, s, A, W, M, N, K0, lda, ldw, epi);
-        MLG_LAUNCH_CHECK();
-        return MLG_OK;
-    }
     if (N % 256) return MLG_EINVAL;
     const long ntiles = (long)nb * (N / 256) * ((M + 255) / 256);
     if (ntiles > INT32_MAX) return MLG_EINVAL;

@@ -66,15 +66,12 @@ __global__ __launch_bounds__(256) void k_lg_kpnorm(const Seg* __restrict__ segs,
     }
 }
 
-#ifndef MLG_LG_INIT_FUSED
-#define MLG_LG_INIT_FUSED 1  // 0: the separate k_lg_gather_rows pass (A/B only)
-#endif
-
 // 64 rows of one segment per workgroup: Fourier positional encoding (cos / sin of
 // Wr . k', 32 frequencies), x = desc, cat[:, :256] = bf16(desc), ind = source index;
 // rows past len zeroed.  With mv (layer 0's self block already run per frame): the live
 // rows' x and bf16 copy come from that block's output instead, mv[seg] = (pair offset,
-// live rows, frame offset, -) -- k_lg_gather_rows folded into this pass.
+// live rows, frame offset, -) -- no separate row-gather pass (+0.3 %, same counts,
+// profiles/r04x_ab_lg_init_fused.txt).
 __global__ __launch_bounds__(256) void k_lg_init(const Seg* __restrict__ segs, const float4* __restrict__ norm,
                                                  const float* __restrict__ kpts, const float* __restrict__ desc,
                                                  int kmax, const float* __restrict__ Wr, float* __restrict__ x,
@@ -270,10 +267,9 @@ constexpr int SBM = 128;               // k_asg_sim tile (rows = columns)
 constexpr int TSS = SBM + 4;           // its LDS row stride: the 16 lanes of a b128 group (16 rows)
                                        // and the 64 lanes of a b32 column read hit distinct banks
 constexpr int ARM = 64, ARN = 128;     // k_asg_arg tile
-#ifndef MLG_ASG_FULL
-#define MLG_ASG_FULL 1  // k_asg_arg: straight-line scans for full tiles (0: the general loops only, A/B)
-#endif
 constexpr int TSA = ARN + 8;           // its LDS row stride: b128 groups of 8 rows x 2 halves
+// Both kernels scan full tiles straight-line and leave the edge tiles to the general loops:
+// k_asg_arg -19 %, k_asg_sim -1.5 %, digest identical (profiles/r05ah_ab_assignment_full_tiles.txt).
 
 // per-tile partials: part[((slot * 2 + dir) * tiles + t) * kmax + i]; dir 0 = rows
 // (t = 128-column tile), dir 1 = columns (t = row tile: 128 rows in k_asg_sim's
@@ -394,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void k_asg_sim(const Asg* __restrict__ tab,
     const int q = tid & (SBM - 1);
     if (q >= (colw ? nc : mr)) return;
     float mx = -INFINITY, sm = 0.f;
-    if (MLG_ASG_FULL && (colw ? mr : nc) == SBM) {
+    if ((colw ? mr : nc) == SBM) {
         // full-length line: straight-line scans, no per-element bounds test (same order)
         if (colw) {
 #pragma unroll 8
@@ -518,7 +514,7 @@ __global__ __launch_bounds__(256, 4) void k_asg_arg(const Asg* __restrict__ tab,
     int bi = 0x7fffffff;
     if (tid < ARN) {
         const int r = tid >> 1, h = tid & 1;
-        if (r < mr && MLG_ASG_FULL && nc == ARN) {
+        if (r < mr && nc == ARN) {
             // full-width tile: straight-line scan, no per-element bounds test (same scores,
             // same order, same strict > -- the general loop below, branch-free)
             const float4 me = sr[r];
@@ -568,7 +564,7 @@ __global__ __launch_bounds__(256, 4) void k_asg_arg(const Asg* __restrict__ tab,
         const int j = tid - ARN;
         if (j >= nc) return;
         const float4 me = sc[j];
-        if (MLG_ASG_FULL && mr == ARM) {
+        if (mr == ARM) {
 #pragma unroll 8
             for (int e = 0; e < ARM; ++e) {
                 const float4 ot = sr[e];
@@ -726,31 +722,6 @@ __global__ __launch_bounds__(256) void k_lg_orient(const int32_t* __restrict__ m
     if (tid == 0) n_out[p] = n;
 }
 
-
-#if !MLG_LG_INIT_FUSED
-// Layer 0's self block on the frame layout -> the pair layout: pair segment k copies the
-// rows of its frame's segment (x f32 and the bf16 x copy in CAT's first 256 columns).
-// mv[k] = (pair offset, live rows, frame offset, -).
-__global__ __launch_bounds__(256) void k_lg_gather_rows(const int4* __restrict__ mv, const float* __restrict__ xf,
-                                                        const bf16_t* __restrict__ catf, float* __restrict__ x,
-                                                        bf16_t* __restrict__ cat) {
-    const int4 m = mv[blockIdx.y];
-    const int r0 = blockIdx.x * 16;
-    if (r0 >= m.y) return;
-    for (int e = threadIdx.x; e < 16 * 64; e += 256) {  // 16 rows x 64 float4 of x
-        const int i = r0 + e / 64, c = e % 64;
-        if (i >= m.y) continue;
-        reinterpret_cast<float4*>(x + (size_t)(m.x + i) * LG_D)[c] =
-            reinterpret_cast<const float4*>(xf + (size_t)(m.z + i) * LG_D)[c];
-    }
-    for (int e = threadIdx.x; e < 16 * 32; e += 256) {  // 16 rows x 32 x 16 B of the bf16 copy
-        const int i = r0 + e / 32, c = e % 32;
-        if (i >= m.y) continue;
-        reinterpret_cast<uint4*>(cat + (size_t)(m.x + i) * 512)[c] =
-            reinterpret_cast<const uint4*>(catf + (size_t)(m.z + i) * 512)[c];
-    }
-}
-#endif
 
 size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1073,22 +1044,10 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     }
     LG_TRY(upload_layout());
     hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)segs.size()), dim3(256), 0, s, SEGS, kpts, kmax, (float4*)(base + L.norm));
-#if MLG_LG_INIT_FUSED
     hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)segs.size()), dim3(256), 0, s, SEGS,
                        (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X, CAT, EF, IND,
                        self0_done ? (const int4*)MOVES : nullptr, X2, CAT2);
     MLG_LAUNCH_CHECK();
-#else
-    hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)segs.size()), dim3(256), 0, s, SEGS,
-                       (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X, CAT, EF, IND,
-                       nullptr, nullptr, nullptr);
-    MLG_LAUNCH_CHECK();
-    if (self0_done) {
-        hipLaunchKernelGGL(k_lg_gather_rows, dim3((unsigned)((kmax + 15) / 16), (unsigned)segs.size()), dim3(256), 0, s,
-                           MOVES, X2, CAT2, X, CAT);
-        MLG_LAUNCH_CHECK();
-    }
-#endif
     tr_rows(1, X, LG_D * 4, Npad);
     tr_rows(2, CAT, 512, Npad, 1024);
 

@@ -200,7 +200,7 @@ __global__ void k_lf_tokens(const float* __restrict__ coarse, const int32_t* __r
 // Layer 0 of the coarse transformer is a self layer: its output rows depend on the frame
 // alone.  k_lf_stash copies the distinct frames' rows (f32 x and its bf16 copy, the first
 // half of cat) aside; k_lf_gather_rows lays them out per pair side (segment g <- frame row
-// block umap[g]) for layers 1.. (MLG_LF_SELF0_DEDUP).
+// block umap[g]) for layers 1..
 __global__ void k_lf_stash(const float* __restrict__ x, const bf16_t* __restrict__ cat, long rows,
                            float* __restrict__ tx, bf16_t* __restrict__ tc) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;  // (row, 16 B of x) then (row, 16 B of cat)
@@ -293,14 +293,11 @@ __global__ __launch_bounds__(256) void k_lf_kv(const float* __restrict__ k, cons
 // bytes); ksum by the lanes with bv == 0.  Partial sums [seg, head, chunk][DH * DH + DH]
 // (tokens in order inside a chunk); k_lf_kv_combine adds the chunks in chunk order.
 constexpr int LF_KV_CHUNK = 256;
-// MLG_LF_KV_STAGE: the 8 tokens' k / v head slices of a step come in as whole 1-KiB wave
+// The 8 tokens' k / v head slices of a step come in as whole 1-KiB wave
 // loads (lane = 16 B of the 8 x DH k | v block) through a per-wave LDS image, instead of
 // one 16-B load per lane per token and operand (8 lanes sharing each address, 128 B per
 // wave-instruction); the next step's loads are in flight while this step's FMAs run.
-// Same per-lane FMA order, so the same sums.
-#ifndef MLG_LF_KV_STAGE
-#define MLG_LF_KV_STAGE 1
-#endif
+// Same per-lane FMA order, so the same sums (-3 % matching, profiles/r05n_ab_loftr_kv_stage.txt).
 template <int DH>
 __global__ __launch_bounds__(256) void k_lf_kv_part(const float* __restrict__ k, const float* __restrict__ v, int ldk,
                                                     int ldv, int L, int heads, int nseg, int nch,
@@ -316,66 +313,40 @@ __global__ __launch_bounds__(256) void k_lf_kv_part(const float* __restrict__ k,
     float acc[B][B] = {};
     float ks[B] = {};
     int s = s0;
-    if (MLG_LF_KV_STAGE) {
-        float* st = stage[threadIdx.x >> 6];
-        // lane's float4 i of a step: flat f = 4 (lane + 64 i) of [k | v][8 tokens][DH]
-        auto fetch = [&](int s_, float4 (&r)[NI]) {
+    float* st = stage[threadIdx.x >> 6];
+    // lane's float4 i of a step: flat f = 4 (lane + 64 i) of [k | v][8 tokens][DH]
+    auto fetch = [&](int s_, float4 (&r)[NI]) {
 #pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int f = 4 * (lane + 64 * i), kv = f / (8 * DH), u = (f % (8 * DH)) / DH, d = f % DH;
-                const size_t row = (size_t)g * L + s_ + u;
-                r[i] = *reinterpret_cast<const float4*>((kv ? v + row * ldv : k + row * ldk) + h * DH + d);
-            }
-        };
-        float4 nxt[NI];
-        if (s + 8 <= s1) fetch(s, nxt);
-        for (; s + 8 <= s1; s += 8) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) *reinterpret_cast<float4*>(st + 4 * (lane + 64 * i)) = nxt[i];
-            __builtin_amdgcn_wave_barrier();
-            if (s + 16 <= s1) fetch(s + 8, nxt);
-            float a[8][B], b[8][B];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    a[u][i] = st[u * DH + bk * B + i];
-                    b[u][i] = st[8 * DH + u * DH + bv * B + i];
-                }
-            __builtin_amdgcn_wave_barrier();  // reads issued before the next step's writes
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    ks[i] += a[u][i];
-#pragma unroll
-                    for (int j = 0; j < B; ++j) acc[i][j] = fmaf(a[u][i], b[u][j], acc[i][j]);
-                }
+        for (int i = 0; i < NI; ++i) {
+            const int f = 4 * (lane + 64 * i), kv = f / (8 * DH), u = (f % (8 * DH)) / DH, d = f % DH;
+            const size_t row = (size_t)g * L + s_ + u;
+            r[i] = *reinterpret_cast<const float4*>((kv ? v + row * ldv : k + row * ldk) + h * DH + d);
         }
-    } else {
-        // 8 tokens' k / v loads in flight before their FMAs (tokens still summed in order)
-        for (; s + 8 <= s1; s += 8) {
-            float a[8][B], b[8][B];
+    };
+    float4 nxt[NI];
+    if (s + 8 <= s1) fetch(s, nxt);
+    for (; s + 8 <= s1; s += 8) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const size_t row = (size_t)g * L + s + u;
-                const float* kr = k + row * ldk + h * DH + bk * B;
-                const float* vr = v + row * ldv + h * DH + bv * B;
+        for (int i = 0; i < NI; ++i) *reinterpret_cast<float4*>(st + 4 * (lane + 64 * i)) = nxt[i];
+        __builtin_amdgcn_wave_barrier();
+        if (s + 16 <= s1) fetch(s + 8, nxt);
+        float a[8][B], b[8][B];
 #pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    a[u][i] = kr[i];
-                    b[u][i] = vr[i];
-                }
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                a[u][i] = st[u * DH + bk * B + i];
+                b[u][i] = st[8 * DH + u * DH + bv * B + i];
             }
+        __builtin_amdgcn_wave_barrier();  // reads issued before the next step's writes
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < 8; ++u)
 #pragma unroll
-                for (int i = 0; i < B; ++i) {
-                    ks[i] += a[u][i];
+            for (int i = 0; i < B; ++i) {
+                ks[i] += a[u][i];
 #pragma unroll
-                    for (int j = 0; j < B; ++j) acc[i][j] = fmaf(a[u][i], b[u][j], acc[i][j]);
-                }
-        }
+                for (int j = 0; j < B; ++j) acc[i][j] = fmaf(a[u][i], b[u][j], acc[i][j]);
+            }
     }
     for (; s < s1; ++s) {
         const size_t row = (size_t)g * L + s;
@@ -508,7 +479,7 @@ __global__ __launch_bounds__(256) void k_lf_ln(const float* __restrict__ in, con
 }
 
 // f32 [rows][256] -> bf16 [rows][512] = [hi | lo] (x = hi + lo to 2^-17; the LoFTR
-// coarse similarity's split operands, MLG_LF_SIM_SPLIT)
+// coarse similarity's split operands)
 __global__ __launch_bounds__(256) void k_lf_split_rows(const float* __restrict__ x, long rows,
                                                        bf16_t* __restrict__ out) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one float4 per thread
@@ -541,9 +512,7 @@ constexpr int LF_RCH = 64;           // rows per column chunk
 // takes the group in blockIdx.z (pair z: S + z L^2, per-row / per-column arrays + z L, chunk
 // partials + z nch L), so the small per-pair kernels fill the chip and the launch
 // boundaries amortise over the group; per-pair arithmetic unchanged (same bits).
-#ifndef MLG_LF_PGRP
-#define MLG_LF_PGRP 8
-#endif
+constexpr int MLG_LF_PGRP = 8;
 #define LF_Z ((size_t)blockIdx.z)
 
 __device__ __forceinline__ float lf_band(float k) { return LF_KEY_BAND + 1e-5f * fabsf(k); }
@@ -551,88 +520,26 @@ __device__ __forceinline__ float lf_band(float k) { return LF_KEY_BAND + 1e-5f *
 // The softmax SUMS' exponentials (row / column sum of exp(x - max), the chunk merge): the
 // hardware exp2 of x log2 e (__expf: v_mul + v_exp_f32, relative error ~|x| 2^-24 per term)
 // instead of the libm-accurate expf (~10 VALU), as these sums made the statistics passes
-// VALU-bound; the exact conf of a candidate keeps expf.  0 builds the expf sums (A/B arm).
-#ifndef MLG_LF_FAST_EXP
-#define MLG_LF_FAST_EXP 1
-#endif
-__device__ __forceinline__ float lf_sexp(float x) { return MLG_LF_FAST_EXP ? __expf(x) : expf(x); }
+// VALU-bound (k_lf_rowbest -10 %, matches identical, profiles/r06n_ab_loftr_fast_sum_exp.txt);
+// the exact conf of a candidate keeps expf.
+__device__ __forceinline__ float lf_sexp(float x) { return __expf(x); }
 
 // conf as the reference computes it: softmax(sim, 1) * softmax(sim, 2)
 __device__ __forceinline__ float lf_conf(float x, float rm, float rz, float cm, float cz) {
     return (expf(x - cm) / cz) * (expf(x - rm) / rz);
 }
 
-// one wave per row; the row lives in v[] (lane l: float4 l + 64 k); rows longer than
-// 256 LF_ROWREG cells take the two-pass loop over memory
-__global__ __launch_bounds__(256) void k_lf_rowstats(const float* __restrict__ S, int L, int lds,
-                                                     float* __restrict__ rmax, float* __restrict__ rsum,
-                                                     float* __restrict__ rkey) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= L) return;
-    S += LF_Z * L * lds;
-    rmax += LF_Z * L;
-    rsum += LF_Z * L;
-    rkey += LF_Z * L;
-    const float* s = S + (size_t)row * lds;
-    float m = -INFINITY, z = 0.f;
-    if ((lds & 3) == 0 && lds <= 256 * LF_ROWREG) {  // columns [L, lds) hold -inf (EpiSimLoFTR)
-        const float4* s4 = reinterpret_cast<const float4*>(s);
-        float4 v[LF_ROWREG];
-#pragma unroll
-        for (int k = 0; k < LF_ROWREG; ++k) {
-            const int j = lane + 64 * k;
-            v[k] = j < lds / 4 ? s4[j] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            m = fmaxf(m, fmaxf(fmaxf(v[k].x, v[k].y), fmaxf(v[k].z, v[k].w)));
-        }
-        m = wave_max(m);
-#pragma unroll
-        for (int k = 0; k < LF_ROWREG; ++k)
-            if (lane + 64 * k < lds / 4)
-                z += lf_sexp(v[k].x - m) + lf_sexp(v[k].y - m) + lf_sexp(v[k].z - m) + lf_sexp(v[k].w - m);
-    } else {
-        for (int j = lane; j < L; j += 64) m = fmaxf(m, s[j]);
-        m = wave_max(m);
-        for (int j = lane; j < L; j += 64) z += lf_sexp(s[j] - m);
-    }
-    z = wave_sum(z);
-    if (lane == 0) {
-        rmax[row] = m;
-        rsum[row] = z;
-        rkey[row] = m + logf(z);
-    }
-}
-
 // Column statistics in two steps so that the whole chip reads S: grid (column blocks of
 // 256, row chunks of LF_RCH); thread = column, coalesced 1 KiB row reads, the chunk's 64
 // values in registers.  Chunk c's (max, sum exp(x - max)) -> pm / pz [c][L]; k_lf_colfin
 // merges the chunks (max, then sum_c pz_c exp(pm_c - max)).
-__global__ __launch_bounds__(256) void k_lf_colpart(const float* __restrict__ S, int L, int lds,
-                                                    float* __restrict__ pm, float* __restrict__ pz) {
-    const int col = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-    if (col >= L) return;
-    S += LF_Z * L * lds;
-    pm += LF_Z * gridDim.y * L;
-    pz += LF_Z * gridDim.y * L;
-    const int r0 = c * LF_RCH, n = min(L - r0, LF_RCH);
-    float v[LF_RCH], m = -INFINITY, z = 0.f;
-#pragma unroll
-    for (int i = 0; i < LF_RCH; ++i) {
-        v[i] = i < n ? S[(size_t)(r0 + i) * lds + col] : -INFINITY;
-        m = fmaxf(m, v[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < LF_RCH; ++i)
-        if (i < n) z += lf_sexp(v[i] - m);
-    pm[(size_t)c * L + col] = m;
-    pz[(size_t)c * L + col] = z;
-}
-
-// k_lf_colpart plus the row maxima of the same tile, so that one read of S yields both
-// (MLG_LF_STATS1): after the column statistics the 64 x 64 (row x lane) values of a wave
+// The row maxima come from the same tile, so that one read of S yields both (the dual
+// softmax in three reads of S instead of four: -1.2 %, digest identical, profiles/
+// r05g_ab_loftr_dual_softmax_3read.txt): after the column statistics the 64 x 64 (row x lane) values of a wave
 // fold in six butterfly steps -- step b exchanges half of the rows with lane ^ b and keeps
 // the max -- until lane l holds row l's max over the wave's 64 columns; the four waves
 // meet in LDS and prm[column block][row] gets the block's max.  Max is exact in any order,
-// so rmax = max over blocks equals k_lf_rowstats' bit for bit.
+// so rmax = max over blocks equals a whole-row pass's bit for bit.
 __global__ __launch_bounds__(256) void k_lf_stats(const float* __restrict__ S, int L, int lds, float* __restrict__ pm,
                                                   float* __restrict__ pz, float* __restrict__ prm) {
     __shared__ float red[4][LF_RCH];
@@ -708,11 +615,10 @@ __global__ __launch_bounds__(256) void k_lf_colfin(const float* __restrict__ pm,
     }
 }
 
-// SELF (MLG_LF_STATS1): the row max comes from k_lf_stats' block maxima prm[ncb][L] and
-// the row sum is formed here from the registers that hold the row anyway (the same
-// per-lane order and wave sum as k_lf_rowstats, so the same bits); rmax / rsum / rkey are
-// written for k_lf_colmaxpart.  Otherwise they are read (k_lf_rowstats ran before).
-template <bool SELF>
+// One wave per row; the row lives in v[] (lane l: float4 l + 64 k); rows longer than 256
+// LF_ROWREG cells take the loops over memory.  The row max comes from k_lf_stats' block
+// maxima prm[ncb][L] and the row sum is formed here from the registers that hold the row
+// anyway; rmax / rsum / rkey are written for k_lf_colmaxpart.
 __global__ __launch_bounds__(256) void k_lf_rowbest(const float* __restrict__ S, int L, int lds, float* __restrict__ rmax,
                                                     float* __restrict__ rsum, float* __restrict__ rkey,
                                                     const float* __restrict__ prm, int ncb,
@@ -725,7 +631,7 @@ __global__ __launch_bounds__(256) void k_lf_rowbest(const float* __restrict__ S,
     rmax += LF_Z * L;
     rsum += LF_Z * L;
     rkey += LF_Z * L;
-    if (SELF) prm += LF_Z * ncb * L;
+    prm += LF_Z * ncb * L;
     cmax += LF_Z * L;
     csum += LF_Z * L;
     ckey += LF_Z * lds;
@@ -743,7 +649,7 @@ __global__ __launch_bounds__(256) void k_lf_rowbest(const float* __restrict__ S,
         for (int k = 0; k < LF_ROWREG; ++k)
             if (lane + 64 * k < lds / 4) v[k] = s4[lane + 64 * k];
     }
-    if constexpr (SELF) {
+    {
         float m = -INFINITY;
         for (int b = lane; b < ncb; b += 64) m = fmaxf(m, prm[(size_t)b * L + row]);
         m = wave_max(m);
@@ -764,9 +670,6 @@ __global__ __launch_bounds__(256) void k_lf_rowbest(const float* __restrict__ S,
             rsum[row] = z;
             rkey[row] = m + logf(z);
         }
-    } else {
-        rm = rmax[row];
-        rz = rsum[row];
     }
     float bv = -1.f;
     int bi = 0x7fffffff;
@@ -1186,34 +1089,17 @@ namespace {
 // Coarse layers' block tail (merge, norm1, MLP, norm2, residual) as ONE fused kernel per
 // 64-token tile (lg_ffn.hip, LoFTR form): the merge output, the MLP hidden and the
 // pre-norm2 message never leave LDS (per token 3.5 KB of HBM instead of ~11 KB through
-// five launches).  0 builds the unfused GEMM + LayerNorm sequence (A/B arm).
-#ifndef MLG_LF_FUSED_TAIL
-#define MLG_LF_FUSED_TAIL 1
-#endif
+// five launches).  The unfused GEMM + LayerNorm sequence stays reachable at run time
+// (mlg_op_loftr_coarse_layer, fused = 0).
 // Coarse similarity f0 . f1^T from split-bf16 operands (hi * hi + hi * lo + lo * hi, f32
-// accumulation: products to ~2^-17 of f32) instead of the exact-f32 MFMA; 0 builds the
-// exact-f32 form (A/B arm)
-#ifndef MLG_LF_SIM_SPLIT
-#define MLG_LF_SIM_SPLIT 1
-#endif
-int g_lf_sim_split = MLG_LF_SIM_SPLIT;  // mlg_set_loftr_similarity
-// Dual softmax in three reads of S: k_lf_stats (column statistics + row block maxima) and
-// a self-normalising k_lf_rowbest replace k_lf_rowstats + k_lf_colpart; 0 builds the
-// four-read sequence (A/B arm).  Both give the same bits.
-#ifndef MLG_LF_STATS1
-#define MLG_LF_STATS1 1
-#endif
-// The split similarity of a dual-softmax group in ONE persistent GEMM launch (round 6): per
-// pair, 576 tiles (720 x 536) or 361 (640 x 480) over 256 workgroups left a 2-3-tile tail;
-// 0 builds one launch per pair (A/B arm).  Same tiles, same per-tile arithmetic: same bits.
-#ifndef MLG_LF_SIM_BATCH
-#define MLG_LF_SIM_BATCH 1
-#endif
-// Layer 0 (self) once per distinct frame of the call, its rows gathered per pair side
-// (round 6); 0 runs it on every pair side (A/B arm).  Row-independent kernels: same bits.
-#ifndef MLG_LF_SELF0_DEDUP
-#define MLG_LF_SELF0_DEDUP 1
-#endif
+// accumulation: products to ~2^-17 of f32) instead of the exact-f32 MFMA
+int g_lf_sim_split = 1;  // mlg_set_loftr_similarity
+// The split similarity of a dual-softmax group is ONE persistent GEMM launch (round 6): per
+// pair, 576 tiles (720 x 536) or 361 (640 x 480) over 256 workgroups left a 2-3-tile tail
+// (-3.5 % matching, bit-identical, profiles/r06o_ab_loftr_sim_batched.txt).
+// Layer 0 (self) runs once per distinct frame of the call, its rows gathered per pair side
+// (round 6: -4 % matching per pair, profiles/r06x_ab_loftr_self0_dedup.txt).  Row-independent
+// kernels: same bits (tests/test_loftr_gpu.py pins the equality).
 
 // nn.Linear weight [N][K] bf16 -> k-step-major [K / 16][N][16] (lg_ffn.hip's layout)
 __global__ void k_lf_pack_kstep(const bf16_t* __restrict__ w, int N, int K, bf16_t* __restrict__ out) {
@@ -1522,13 +1408,11 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         return MLG_EHIP;
     const long crows = (long)2 * P * L;
     TailW tails[8];
-    if (MLG_LF_FUSED_TAIL) {
-        if (w.coarse_tails)
-            tails_at((char*)w.coarse_tails, tails);  // packed once (mlg_loftr_pack_tails)
-        else
-            LF_TRY(pack_tails(w, (char*)at(ML.tails), tails, s));
-    }
-    const TailW* tw = MLG_LF_FUSED_TAIL ? tails : nullptr;
+    if (w.coarse_tails)
+        tails_at((char*)w.coarse_tails, tails);  // packed once (mlg_loftr_pack_tails)
+    else
+        LF_TRY(pack_tails(w, (char*)at(ML.tails), tails, s));
+    const TailW* tw = tails;
     // the distinct frames of the call (first-appearance order) and each pair side's index
     std::vector<int32_t> h_ufr, h_umap(2 * P);
     {
@@ -1543,7 +1427,7 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         }
     }
     const int NU = (int)h_ufr.size();
-    if (MLG_LF_SELF0_DEDUP && NU < 2 * P) {
+    if (NU < 2 * P) {
         int32_t* ufr = (int32_t*)at(ML.ufr);
         int32_t* umap = (int32_t*)at(ML.umap);
         if (hipMemcpyAsync(ufr, h_ufr.data(), (size_t)NU * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -1590,35 +1474,22 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     const int G = std::min(P, MLG_LF_PGRP);
     for (int p0 = 0; p0 < P; p0 += G) {
         const unsigned g = (unsigned)std::min(G, P - p0);
-        if (split && MLG_LF_SIM_BATCH) {  // the group's g similarities as one tile queue
+        if (split) {  // the group's g similarities as one tile queue
             LF_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p0 * L * 512, CS + ((size_t)P + p0) * L * 512, L, Lpad, 256, S,
                                             lds, L, s, (int)g, (long)L * 512));
         } else {
             for (int q = 0; q < (int)g; ++q) {
                 const int p = p0 + q;
-                float* Sq = S + (size_t)q * L * lds;
-                if (split)
-                    LF_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p * L * 512, CS + ((size_t)P + p) * L * 512, L, Lpad,
-                                                    256, Sq, lds, L, s));
-                else
-                    LF_TRY(mlg_similarity_f32_loftr(bc.x + (size_t)p * L * 256, L, bc.x + ((size_t)P + p) * L * 256, L,
-                                                    256, Sq, L, s));
+                LF_TRY(mlg_similarity_f32_loftr(bc.x + (size_t)p * L * 256, L, bc.x + ((size_t)P + p) * L * 256, L, 256,
+                                                S + (size_t)q * L * lds, L, s));
             }
         }
-        if (MLG_LF_STATS1) {  // three reads of S: stats, rowbest, colmaxpart
-            hipLaunchKernelGGL(k_lf_stats, dim3(ncb, nrch, g), dim3(256), 0, s, S, L, lds, pm, pz, prm);
-            hipLaunchKernelGGL(k_lf_colfin, dim3((L + 63) / 64, 1, g), dim3(256), 0, s, pm, pz, L, lds, nrch, cmax,
-                               csum, ckey);
-            hipLaunchKernelGGL(k_lf_rowbest<true>, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, S, L, lds, rmax, rsum,
-                               rkey, prm, ncb, cmax, csum, ckey, bval, bidx);
-        } else {
-            hipLaunchKernelGGL(k_lf_rowstats, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, S, L, lds, rmax, rsum, rkey);
-            hipLaunchKernelGGL(k_lf_colpart, dim3(ncb, nrch, g), dim3(256), 0, s, S, L, lds, pm, pz);
-            hipLaunchKernelGGL(k_lf_colfin, dim3((L + 63) / 64, 1, g), dim3(256), 0, s, pm, pz, L, lds, nrch, cmax,
-                               csum, ckey);
-            hipLaunchKernelGGL(k_lf_rowbest<false>, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, S, L, lds, rmax, rsum,
-                               rkey, nullptr, 0, cmax, csum, ckey, bval, bidx);
-        }
+        // three reads of S: stats, rowbest, colmaxpart
+        hipLaunchKernelGGL(k_lf_stats, dim3(ncb, nrch, g), dim3(256), 0, s, S, L, lds, pm, pz, prm);
+        hipLaunchKernelGGL(k_lf_colfin, dim3((L + 63) / 64, 1, g), dim3(256), 0, s, pm, pz, L, lds, nrch, cmax, csum,
+                           ckey);
+        hipLaunchKernelGGL(k_lf_rowbest, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, S, L, lds, rmax, rsum, rkey, prm,
+                           ncb, cmax, csum, ckey, bval, bidx);
         hipLaunchKernelGGL(k_lf_colmaxpart, dim3((L + 255) / 256, nrch, g), dim3(256), 0, s, S, L, lds, rmax, rsum,
                            rkey, cmax, csum, pm);
         hipLaunchKernelGGL(k_lf_colmaxfin, dim3((L + 255) / 256, 1, g), dim3(256), 0, s, pm, L, nrch, cbest);

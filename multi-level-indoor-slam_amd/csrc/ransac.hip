@@ -562,12 +562,10 @@ __device__ __forceinline__ bool null_space5_reg(const double (&A)[5][9], double 
 // solvePoly is the related Durand-Kerner iteration); estimates with a negligible
 // imaginary part are the real roots, polished by two real Newton steps and
 // gathered in lane order, so every lane of the group holds the same list.
-// MLG_RS_ROOTS_LDS: each iteration gathers the group's estimates through LDS (one
-// ds_write_b128 of (re, im) per lane, ten broadcast ds_read_b128) instead of twenty
-// 64-bit shuffles (forty ds_bpermute); the same values, so the same roots.
-#ifndef MLG_RS_ROOTS_LDS
-#define MLG_RS_ROOTS_LDS 1
-#endif
+// Each iteration gathers the group's estimates through LDS (one ds_write_b128 of (re, im)
+// per lane, ten broadcast ds_read_b128) instead of twenty 64-bit shuffles (forty
+// ds_bpermute); the same values, so the same roots (-7 %, identical,
+// profiles/r05k_ab_ransac_roots_lds.txt).
 __device__ int real_roots10(double (&c)[11], double (&roots)[10], int r, int gl, double2* __restrict__ zs) {
     double mx = 0.0;
 #pragma unroll
@@ -592,23 +590,15 @@ __device__ int real_roots10(double (&c)[11], double (&roots)[10], int r, int gl,
     for (int it = 0; it < 60; ++it) {
         // every lane of the group takes part in the gathers (converged ones included)
         double xr_[10], xi_[10];
-        if (MLG_RS_ROOTS_LDS) {
-            zs[r] = make_double2(zr, zi);
-            __builtin_amdgcn_wave_barrier();
+        zs[r] = make_double2(zr, zi);
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const double2 z = zs[j];
-                xr_[j] = z.x;
-                xi_[j] = z.y;
-            }
-            __builtin_amdgcn_wave_barrier();  // reads done before the next iteration's write
-        } else {
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                xr_[j] = __shfl(zr, gl + j, 64);
-                xi_[j] = __shfl(zi, gl + j, 64);
-            }
+        for (int j = 0; j < 10; ++j) {
+            const double2 z = zs[j];
+            xr_[j] = z.x;
+            xi_[j] = z.y;
         }
+        __builtin_amdgcn_wave_barrier();  // reads done before the next iteration's write
         if (!done) {
             // p(z), p'(z) by Horner (complex), the complex products as explicit fma chains
             // (the C twin spells the same ones: this file builds without contraction)
@@ -690,12 +680,9 @@ __device__ int real_roots10(double (&c)[11], double (&roots)[10], int r, int gl,
 }
 
 // The 5-point sample's null space (Householder QR) one hypothesis per lane, ahead of
-// k_ransac_hyp5 (MLG_RS_NULL_SPLIT): inside hyp5's 16-lane groups all 16 lanes ran the
-// same QR, 4 hypotheses per wave.  The basis (36 doubles) and the rank flag (slot 36)
-// go to the hypothesis' own model slot, which hyp5 reads before it writes the models.
-#ifndef MLG_RS_NULL_SPLIT
-#define MLG_RS_NULL_SPLIT 1
-#endif
+// k_ransac_hyp5: inside hyp5's lane groups every lane ran the same QR (profiles/
+// r05h_ransac_ablation.txt).  The basis (36 doubles) and the rank flag (slot 36) go to
+// the hypothesis' own model slot, which hyp5 reads before it writes the models.
 __device__ __forceinline__ bool hyp5_active(const PairInfo& pi, int h, int H, const int32_t* __restrict__ nsub, int p) {
     return h < H && (pi.mode == 5 ? h == 0 : h < nsub[p]);
 }
@@ -738,24 +725,17 @@ __global__ __launch_bounds__(64) void k_ransac_null5(const PairInfo* __restrict_
     o[36] = ok ? 1.0 : 0.0;
 }
 
-// GS lanes per hypothesis group: 16 (4 groups per wave) or 10 (MLG_RS_G10: 6 groups, lanes
-// 60..63 idle) -- the solver's ten constraint rows and ten root estimates each fill one
-// lane, so 10-lane groups put 6 hypotheses on a wave instead of 4.  Same arithmetic per
-// lane; the pivot search (max |a|, ties to the lowest lane) scans the group's lanes in
-// order instead of an xor tree -- the same pivot for every non-NaN column.
-#ifndef MLG_RS_G10
-#define MLG_RS_G10 1
-#endif
-constexpr int HYP5_GS = MLG_RS_G10 ? 10 : 16, HYP5_GPB = 4 * (64 / HYP5_GS);  // lanes per group, groups per block
-// MLG_RS_ROOTS_SPLIT: k_ransac_hyp5 stops at the degree-10 polynomial and leaves it, with
-// the 3 x 3 polynomial matrix, in the hypothesis' model slot; k_ransac_roots5 then finds
-// the roots and writes the models with a third of the solver's registers, so more waves
-// hide the f64 latency of the root iteration.  Needs MLG_RS_NULL_SPLIT (the slot then
-// holds: [0, 36) null space, [36] stage flag, [37, 48) polynomial, [48, 87) matrix).
-#ifndef MLG_RS_ROOTS_SPLIT
-#define MLG_RS_ROOTS_SPLIT 1
-#endif
-constexpr bool HYP5_ROOTS_SPLIT = MLG_RS_ROOTS_SPLIT && MLG_RS_NULL_SPLIT;
+// 10 lanes per hypothesis group (6 groups per wave, lanes 60..63 idle) -- the solver's ten
+// constraint rows and ten root estimates each fill one lane, so 10-lane groups put 6
+// hypotheses on a wave where 16-lane groups put 4 (-22 %, identical, profiles/
+// r05l_ab_ransac_10lane_groups.txt).  The pivot search (max |a|, ties to the lowest lane)
+// scans the group's lanes in order.
+constexpr int HYP5_GS = 10, HYP5_GPW = 64 / HYP5_GS, HYP5_GPB = 4 * HYP5_GPW;  // lanes per group, groups per wave / block
+// k_ransac_hyp5 stops at the degree-10 polynomial and leaves it, with the 3 x 3 polynomial
+// matrix, in the hypothesis' model slot; k_ransac_roots5 then finds the roots and writes
+// the models with a third of the solver's registers, so more waves hide the f64 latency of
+// the root iteration (-8 %, identical, profiles/r05m_ab_ransac_roots_kernel.txt).  The slot
+// holds: [0, 36) null space, [36] stage flag, [37, 48) polynomial, [48, 87) matrix.
 constexpr int SLOT_FLAG = 36, SLOT_POLY = 37, SLOT_MAT = 48;
 constexpr double FLAG_POLY = 2.0;  // the slot's polynomial and matrix are written
 
@@ -809,18 +789,17 @@ __device__ __forceinline__ int hyp5_models(const double (&zr)[10], int nz, BX bx
     return ns;
 }
 
-template <int GS, bool SPLIT>
+// (ptsn / subsets: the sample is read by k_ransac_null5 now; the argument list is kept)
 __global__ __launch_bounds__(256) void k_ransac_hyp5(const PairInfo* __restrict__ info,
                                                      const double4* __restrict__ ptsn, int H,
                                                      const int32_t* __restrict__ subsets,
                                                      const int32_t* __restrict__ nsub, double* __restrict__ models,
                                                      int8_t* __restrict__ nsol, int h0,
                                                      const uint8_t* __restrict__ done) {
-    constexpr int GPW = 64 / GS, GPB = 4 * GPW;
+    constexpr int GS = HYP5_GS, GPW = HYP5_GPW, GPB = HYP5_GPB;
     __shared__ double snb[GPB][4][9];
-    __shared__ double2 szs[GPB][17];  // root estimates per group (17: groups on distinct banks)
     const int lane = threadIdx.x & 63, gw = lane / GS;
-    const bool valid = gw < GPW;  // GS = 10: lanes 60..63 belong to no group
+    const bool valid = gw < GPW;  // lanes 60..63 belong to no group
     const int g = (threadIdx.x >> 6) * GPW + (valid ? gw : 0), r = lane - gw * GS, gl = gw * GS;  // group, lane in group, base
     const int p = blockIdx.y;
     const int h = h0 + blockIdx.x * GPB + g;
@@ -831,20 +810,10 @@ __global__ __launch_bounds__(256) void k_ransac_hyp5(const PairInfo* __restrict_
     const bool act = valid && ess && hyp5_active(pi, h, H, nsub, p);
     if (!ess) return;  // uniform per block (one pair per blockIdx.y)
     bool ok = act;
-    if (act) {
-        if (MLG_RS_NULL_SPLIT) {  // k_ransac_null5 left the basis in this hypothesis' model slot
-            const double* nb = models + ((size_t)p * H + h) * MAXSOL * 9;
-            for (int i = r; i < 36; i += GS) snb[g][i / 9][i % 9] = nb[i];
-            ok = nb[36] != 0.0;
-        } else {
-            double Nb[4][9];
-            ok = hyp5_null(pi, ptsn, subsets, p, H, h, Nb);
-            if (r == 0)
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) snb[g][a][k] = Nb[a][k];
-        }
+    if (act) {  // k_ransac_null5 left the basis in this hypothesis' model slot
+        const double* nb = models + ((size_t)p * H + h) * MAXSOL * 9;
+        for (int i = r; i < 36; i += GS) snb[g][i / 9][i % 9] = nb[i];
+        ok = nb[36] != 0.0;
     }
     __syncthreads();
     if (!valid) return;  // after the barrier: no group reads these lanes
@@ -913,22 +882,13 @@ __global__ __launch_bounds__(256) void k_ransac_hyp5(const PairInfo* __restrict_
     for (int c = 0; c < 10; ++c) {
         double best = used ? -1.0 : fabs(row[c]);
         int bl = r;
-        if constexpr (GS == 16) {
+        const double mine = best;
+        best = -2.0;
+        bl = GS;
 #pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, 64);
-                const int ol = __shfl_xor(bl, o, 64);
-                if (ob > best || (ob == best && ol < bl)) { best = ob; bl = ol; }
-            }
-        } else {
-            const double mine = best;
-            best = -2.0;
-            bl = GS;
-#pragma unroll
-            for (int jl = 0; jl < GS; ++jl) {
-                const double ob = __shfl(mine, gl + jl, 64);
-                if (ob > best) { best = ob; bl = jl; }
-            }
+        for (int jl = 0; jl < GS; ++jl) {
+            const double ob = __shfl(mine, gl + jl, 64);
+            if (ob > best) { best = ob; bl = jl; }
         }
         if (!(best > 1e-300)) ok = false;  // singular (uniform in the group)
         piv[c] = bl;
@@ -996,48 +956,36 @@ __global__ __launch_bounds__(256) void k_ransac_hyp5(const PairInfo* __restrict_
         pmul_acc<4, 4>(u, by[1], bx[2], -1.0);
         pmul_acc<5, 7>(poly, b1[0], u, 1.0);
     }
-    double zr[10];
 #if defined(RS_ABLATE) && RS_ABLATE == 1
     if (r == 0) nsol[(size_t)p * H + h] = (int8_t)(poly[3] > 1e300);
     return;
 #endif
-    if constexpr (SPLIT) {  // k_ransac_roots5 continues from the slot
-        if (r == 0) {
-            double* o = models + ((size_t)p * H + h) * MAXSOL * 9;
+    if (r == 0) {  // k_ransac_roots5 continues from the slot
+        double* o = models + ((size_t)p * H + h) * MAXSOL * 9;
 #pragma unroll
-            for (int i = 0; i < 11; ++i) o[SLOT_POLY + i] = poly[i];
+        for (int i = 0; i < 11; ++i) o[SLOT_POLY + i] = poly[i];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
+        for (int i = 0; i < 3; ++i) {
 #pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    o[SLOT_MAT + 13 * i + d] = bx[i][d];
-                    o[SLOT_MAT + 13 * i + 4 + d] = by[i][d];
-                }
-#pragma unroll
-                for (int d = 0; d < 5; ++d) o[SLOT_MAT + 13 * i + 8 + d] = b1[i][d];
+            for (int d = 0; d < 4; ++d) {
+                o[SLOT_MAT + 13 * i + d] = bx[i][d];
+                o[SLOT_MAT + 13 * i + 4 + d] = by[i][d];
             }
-            o[SLOT_FLAG] = FLAG_POLY;
+#pragma unroll
+            for (int d = 0; d < 5; ++d) o[SLOT_MAT + 13 * i + 8 + d] = b1[i][d];
         }
-        return;
-    } else {
-        const int nz = real_roots10(poly, zr, r, gl, szs[g]);
-        if (r != 0) return;
-        nsol[(size_t)p * H + h] = (int8_t)hyp5_models(
-            zr, nz, [&](int i, int d) { return bx[i][d]; }, [&](int i, int d) { return by[i][d]; },
-            [&](int i, int d) { return b1[i][d]; }, [&](int a, int k) { return snb[g][a][k]; },
-            models + ((size_t)p * H + h) * MAXSOL * 9);
+        o[SLOT_FLAG] = FLAG_POLY;
     }
 }
 
-// The roots and models of the hypotheses k_ransac_hyp5<.., true> left at the polynomial
-// stage (same group layout; every other slot is left as it is).
-template <int GS>
+// The roots and models of the hypotheses k_ransac_hyp5 left at the polynomial stage (same
+// group layout; every other slot is left as it is).
 __global__ __launch_bounds__(256) void k_ransac_roots5(const PairInfo* __restrict__ info, int H,
                                                        const int32_t* __restrict__ nsub, double* __restrict__ models,
                                                        int8_t* __restrict__ nsol, int h0,
                                                        const uint8_t* __restrict__ done) {
-    constexpr int GPW = 64 / GS, GPB = 4 * GPW;
-    __shared__ double2 szs[GPB][17];
+    constexpr int GS = HYP5_GS, GPW = HYP5_GPW, GPB = HYP5_GPB;
+    __shared__ double2 szs[GPB][17];  // root estimates per group (17: groups on distinct banks)
     __shared__ double scoef[GPB][39 + 36];  // the slot's matrix and null space, read before models overwrite it
     const int lane = threadIdx.x & 63, gw = lane / GS;
     const bool valid = gw < GPW;
@@ -1659,18 +1607,14 @@ int mlg_ransac_run(const float* kp1, const float* kp2, const int32_t* offs, int 
         hipLaunchKernelGGL(k_ransac_hyp, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, ptsn, H, seed, subsets, nsub,
                            models, nsol, h0, skip);
         MLG_LAUNCH_CHECK();
-        if (MLG_RS_NULL_SPLIT) {
-            hipLaunchKernelGGL(k_ransac_null5, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, ptsn, H, subsets, nsub,
-                               models, h0, hn, skip);
-            MLG_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL((k_ransac_hyp5<HYP5_GS, HYP5_ROOTS_SPLIT>), dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P),
-                           dim3(256), 0, s, info, ptsn, H, subsets, nsub, models, nsol, h0, skip);
-        if (HYP5_ROOTS_SPLIT) {
-            MLG_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_ransac_roots5<HYP5_GS>, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, info,
-                               H, nsub, models, nsol, h0, skip);
-        }
+        hipLaunchKernelGGL(k_ransac_null5, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, ptsn, H, subsets, nsub, models,
+                           h0, hn, skip);
+        MLG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_ransac_hyp5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, info, ptsn, H,
+                           subsets, nsub, models, nsol, h0, skip);
+        MLG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_ransac_roots5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, info, H, nsub,
+                           models, nsol, h0, skip);
         MLG_LAUNCH_CHECK();
         if (g_poison_nsol) {
             hipLaunchKernelGGL(k_ransac_poison_nsol, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, H, nsub, nsol, h0,

@@ -261,3 +261,29 @@ def test_split_similarity_against_exact_arm(dev, setup, hw):
         assert abs(int(n0[p]) - int(n1[p])) <= max(2, 0.01 * n1[p]), (p, n0[p], n1[p])
     print(f"{hw}: {shared} of {tot} coarse matches shared, {close} within conf 1e-3 / 0.05 px")
     assert tot > 18 * 50 and shared >= 0.99 * tot and close >= 0.99 * shared, (tot, shared, close)
+
+
+def test_layer0_dedup_equals_plain_path(dev, setup):
+    """coarse layer 0 (self) runs once per distinct frame of a call and its rows
+    are gathered per pair side whenever a frame repeats; with all-distinct frames every pair
+    side runs it itself.  Both must give the same bits.  Three frames of one place plus a
+    copy of frame 0 as index 3: pairs (0, 1), (0, 2) repeat frame 0 and take the dedup path,
+    pairs (0, 1), (3, 2) name four distinct rows and take the plain one.  At 480 x 640
+    (L = 4800, the fixture's same-place pair and one more revisit, 283 and 279 matches): cropped to 136 x 208
+    (L = 442) the seeded synthetic weights give no coarse match at all (measured: 0 and 0),
+    and an all-empty comparison would show nothing."""
+    sd, lf, orc, frames, pairs, _ = setup
+    po = synthetic.make_sequence(40, 8, 1).place_of
+    trio = [i for i in range(40) if po[i] == po[pairs[0][0]]][:3]
+    assert len(trio) == 3
+    assert tuple(trio[:2]) == tuple(pairs[0])
+    H, W = 480, 640
+    coarse, fine = lf.features(torch.from_numpy(frames[trio]).to(dev))
+    coarse = torch.cat([coarse, coarse[:1]]).contiguous()
+    fine = torch.cat([fine, fine[:1]]).contiguous()
+    dedup = [x.cpu() for x in lf.match_device(coarse, fine, H, W, [0, 0], [1, 2])]
+    plain = [x.cpu() for x in lf.match_device(coarse, fine, H, W, [0, 3], [1, 2])]
+    print("matches per pair:", dedup[0].tolist(), plain[0].tolist())
+    assert int(dedup[0].sum()) > 0, "no coarse match: the comparison would be vacuous"
+    for name, a, b in zip(("n", "k0", "k1", "conf"), dedup, plain):
+        assert torch.equal(a, b), name

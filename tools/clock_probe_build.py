@@ -4,7 +4,7 @@
 
 Copies csrc/ to a scratch directory and stamps thread 0 of every workgroup of the
 LightGlue attention tile (k_attention_varlen), the fused FFN (k_lg_ffn) and the
-projections (k_lg_proj_res) with s_memtime / s_memrealtime around its work; exports
+projections (k_lg_proj_pipe) with s_memtime / s_memrealtime around its work; exports
 mlg_probe_clock() (attention), mlg_probe_clock_ffn() and mlg_probe_clock_proj() (median
 over the last 16,384 workgroups of d(memtime) / d(memrealtime) x 100 MHz, in GHz) and
 links OUT_DIR/libmlgate.so (+ a copy of the tree's libmlgate_torch.so) for
@@ -66,10 +66,11 @@ KERNELS = {
     "lg_ffn.hip": ("_ffn", "mlg_probe_clock_ffn",
                    "    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;\n"
                    "    for (int i = tid; i < 512; i += NTH) {",
-                   "        __syncthreads();  // the next tile overwrites the LDS image\n    }\n}\n"),
+                   "        o[11] = (unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11));  // XCC_ID\n"
+                   "    }\n#endif\n}\n"),
     "lg_proj.hip": ("_proj", "mlg_probe_clock_proj",
                     "    constexpr int N = SELF ? 768 : 512, NPART = SELF ? 3 : 2, R = 64;",
-                    "        if (tn >= ntiles) break;\n        t = tn;\n    }\n}\n"),
+                    "                                ntiles);\n}\n"),
 }
 
 

@@ -2,7 +2,7 @@
 
     python tools/ffn_interference.py [--rows 65536] [--repeats 6]
 
-For each victim kernel (fused block tail k_lg_ffn, projection k_lg_proj_res, ragged
+For each victim kernel (fused block tail k_lg_ffn, projection k_lg_proj_pipe, ragged
 attention k_attention_varlen) on fixed seeded inputs through the op-level C ABI:
 
   alone      the same launch repeated on one stream;

@@ -81,7 +81,7 @@ __device__ __forceinline__ int p_proj_copyout(const Lane& l, int it) {  // copy_
     const int L = (it & 3) * 512 + l.tid, h = L / 512, row = (L >> 3) & 63, c = L & 7;
     return stage_off(h, row, 8 * c);
 }
-// lg_proj.hip paired staging (MLG_PROJ_SWAP, round 5): b128 writes of whole chunks, b128 copy-out
+// lg_proj.hip paired staging (stage_pair, round 5): b128 writes of whole chunks, b128 copy-out
 // (pattern 29-31: the (r >> 1) & 7 swizzle first tried, 2-way on the writes; 36-38: r & 7, the product)
 __device__ __forceinline__ int pair_off(int h, int row, int c) { return (h * 64 + row) * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
 __device__ __forceinline__ int pair_off7(int h, int row, int c) { return (h * 64 + row) * 128 + ((c ^ (row & 7)) << 4); }
