@@ -19,6 +19,20 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
         if (e_ != hipSuccess) return MLG_EHIP;                 \
     } while (0)
 
+// async upload of a host table (a pageable vector: pair_plan.h states its lifetime rule)
+template <class V>
+inline bool mlg_upload(void* dst, const V& v, hipStream_t s) {
+    return hipMemcpyAsync(dst, v.data(), v.size() * sizeof(typename V::value_type), hipMemcpyHostToDevice, s) ==
+           hipSuccess;
+}
+
+// propagate a callee's error code
+#define MLG_TRY(x)                     \
+    do {                               \
+        int rc_ = (x);                 \
+        if (rc_ != MLG_OK) return rc_; \
+    } while (0)
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
     return __uint_as_float(((uint32_t)v) << 16);
 }

@@ -13,21 +13,24 @@
 // (one small D2H copy per layer), stops pairs whose confident ratio exceeds
 // depth_confidence (their assignment runs at that layer), prunes segments above the
 // pruning threshold, and compacts the layout with one gather.
-#include <unordered_map>
+// The host side of that -- segment layout, attention task tables, layer 0's frame layout,
+// the per-layer stop / prune / compaction decision -- is pair_plan.h; this file validates,
+// carves the workspace, uploads the plan's tables and launches.
 #include <vector>
 
 #include "common.h"
 #include "kernels.h"
+#include "pair_plan.h"
 #include "../../include/mlgate.h"
 
 namespace {
 
+using pair_plan::a256;
+using pair_plan::Seg;
+static_assert(sizeof(pair_plan::Task) == sizeof(int4) && sizeof(pair_plan::Move) == sizeof(int4),
+              "the host tables are uploaded by bytes into the kernels' int4 tables");
+
 constexpr int LG_D = 256, LG_H = 4, LG_L = 9;
-
-
-struct Seg {
-    int off, len, frame, pad;  // flat row offset, live tokens, source frame, unused
-};
 
 // ------------------------------------------------------------------ init
 // normalize_keypoints without image_size: size = 1 + max - min per image,
@@ -218,27 +221,6 @@ __global__ __launch_bounds__(256) void k_lg_compact(const int4* __restrict__ mov
         efac2[lg_fac4((size_t)(mv.z + i), p)] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int i = newlen + tid; i < padded; i += 256) ind2[mv.z + i] = -1;
-}
-
-__global__ void k_lg_live(const Seg* __restrict__ segs, int nseg, uint8_t* __restrict__ live,
-                          int* __restrict__ rowseg, int Npad) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= Npad) return;
-    // segments are in increasing offset order: binary search for the last one starting
-    // at or before r (a linear scan over every segment per row was quadratic)
-    int lo = 0, hi = nseg - 1, sgi = -1;
-    while (lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        if (segs[mid].off <= r) {
-            sgi = mid;
-            lo = mid + 1;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    if (sgi >= 0 && r >= segs[sgi].off + segs[sgi].len) sgi = -1;
-    live[r] = sgi >= 0;
-    rowseg[r] = sgi;
 }
 
 // ------------------------------------------------------------------ assignment
@@ -722,9 +704,6 @@ __global__ __launch_bounds__(256) void k_lg_orient(const int32_t* __restrict__ m
     if (tid == 0) n_out[p] = n;
 }
 
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------ debug trace
 // mlg_dbg_lg_trace_begin / _end (include/mlgate.h): the calling thread's mlg_lightglue
 // calls append, after every stage, one 64-bit hash per 64-row tile of the buffer the
@@ -836,12 +815,6 @@ LgLayout lg_layout(int P, int kmax) {
     return L;
 }
 
-#define LG_TRY(x)                      \
-    do {                               \
-        int rc_ = (x);                 \
-        if (rc_ != MLG_OK) return rc_; \
-    } while (0)
-
 float conf_threshold(int i) {
     const double t = 0.8 + 0.1 * exp(-4.0 * i / LG_L);
     return (float)std::min(1.0, std::max(0.0, t));
@@ -908,141 +881,92 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     };
     int tl = 0;  // layer of the next table upload (trace tags)
 
-    // Host tables below are uploaded with hipMemcpyAsync on `s` and only rewritten after
-    // the stream has been synchronised (the per-layer statistics read-back, and one final
-    // synchronisation before returning), so the pageable sources outlive every copy that
-    // reads them.
-    std::vector<Seg> segs;
-    std::vector<int> pair_of;  // pair index per active segment pair
-    std::vector<int> orig_total(P);
-    std::vector<int4> h_tasks;
-    std::vector<int> h_out;
-    std::vector<int4> h_moves;
+    // The plan objects own the host tables (pair_plan.h): they are uploaded with
+    // hipMemcpyAsync on `s` and rebuilt only after the stream has been synchronised (the
+    // per-layer statistics read-back, and one final synchronisation before returning), so
+    // the pageable sources outlive every copy that reads them.  h_asg follows the same rule.
+    pair_plan::Segments lay;  // the current layout
+    pair_plan::AttnTables att;
+    pair_plan::FramePlan fp;
+    pair_plan::LayerDecision dec;
     std::vector<Asg> h_asg;
-    int off = 0;
     if (hipMemsetAsync(nmatch, 0, sizeof(int32_t) * P, s) != hipSuccess) return MLG_EHIP;
-    for (int p = 0; p < P; ++p) {
-        const int la = counts[pa[p]], lb = counts[pb[p]];
-        if (la < 0 || la > kmax || lb < 0 || lb > kmax) return MLG_EINVAL;
-        orig_total[p] = la + lb;
-        if (stop_layer) stop_layer[p] = 0;
-        if (la == 0 || lb == 0) continue;  // empty side: no matches (reference early exit)
-        segs.push_back(Seg{off, la, pa[p], 0});
-        off += (la + 63) & ~63;
-        segs.push_back(Seg{off, lb, pb[p], 0});
-        off += (lb + 63) & ~63;
-        pair_of.push_back(p);
-    }
-    if (segs.empty()) return MLG_OK;
-    int Npad = off;
-    int maxq = 0;
+    if (stop_layer) std::fill(stop_layer, stop_layer + P, 0);
+    if (!lay.build(counts, pa, pb, P, kmax)) return MLG_EINVAL;
+    if (lay.segs.empty()) return MLG_OK;
+    std::vector<Seg>& segs = lay.segs;
+    std::vector<int>& pair_of = lay.pair_of;  // pair index per active segment pair
+    int& Npad = lay.Npad;
     auto upload_layout = [&]() -> int {
         // segments, live-row mask / row -> segment map, self and cross attention tasks
-        h_tasks.clear();
-        h_out.clear();
-        maxq = 0;
-        for (size_t k = 0; k < segs.size(); k += 2) {
-            const Seg a = segs[k], b = segs[k + 1];
-            h_tasks.push_back(make_int4(a.off, a.len, a.off, a.len));
-            h_tasks.push_back(make_int4(b.off, b.len, b.off, b.len));
-            maxq = std::max(maxq, std::max(a.len, b.len));
-        }
-        for (size_t k = 0; k < segs.size(); k += 2) {
-            const Seg a = segs[k], b = segs[k + 1];
-            h_tasks.push_back(make_int4(a.off, a.len, b.off, b.len));
-            h_tasks.push_back(make_int4(b.off, b.len, a.off, a.len));
-        }
-        for (int rep = 0; rep < 2; ++rep)
-            for (size_t k = 0; k < segs.size(); ++k) h_out.push_back(segs[k].off);
-        if (hipMemcpyAsync(SEGS, segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(TASKS, h_tasks.data(), h_tasks.size() * sizeof(int4), hipMemcpyHostToDevice, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(OUTOFF, h_out.data(), h_out.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)
+        att.build(segs);
+        if (!mlg_upload(SEGS, segs, s) || !mlg_upload(TASKS, att.tasks, s) || !mlg_upload(OUTOFF, att.out_off, s))
             return MLG_EHIP;
-        hipLaunchKernelGGL(k_lg_live, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, (int)segs.size(), LIVE, ROWSEG,
-                           Npad);
+        hipLaunchKernelGGL(k_pair_live<int*>, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, (int)segs.size(), LIVE,
+                           ROWSEG, Npad);
         MLG_LAUNCH_CHECK();
         tr_tab(tl * 100 + 3, SEGS, segs.size() * sizeof(Seg));
-        tr_tab(tl * 100 + 4, TASKS, h_tasks.size() * sizeof(int4));
-        tr_tab(tl * 100 + 5, OUTOFF, h_out.size() * sizeof(int));
+        tr_tab(tl * 100 + 4, TASKS, att.tasks.size() * sizeof(int4));
+        tr_tab(tl * 100 + 5, OUTOFF, att.out_off.size() * sizeof(int));
         tr_rows(tl * 100 + 6, LIVE, 1, Npad);
+        return MLG_OK;
+    };
+    // One self block on the uploaded layout's first `nt` (self) tasks: q / k / v projection
+    // with rotary + head split fused in the GEMM epilogue, ragged attention, then out_proj +
+    // FFN + residual fused (lg_ffn.hip).  x / cat / ef: the primary buffers, or the secondary
+    // ones holding layer 0's frame layout; np rows; trace tags tag + 10 .. 15.
+    auto self_block = [&](const mlg_lg_block_i& bw, float* x, bf16_t* cat, const float4* ef, const int4* tasks,
+                          const int* outoff, int nt, int np, int mq, double tok, double work, int tag) -> int {
+        {
+            MlgProfScope prof(6, s, 2.0 * tok * 768 * 256);
+            MLG_TRY(mlg_lg_proj(true, cat, 512, bw.Wqkv, bw.bqkv, (const float*)ef, LIVE, Q, K, VT, np, s));
+        }
+        tr_heads(tag + 10, Q, np);
+        tr_heads(tag + 11, K, np);
+        tr_heads(tag + 12, VT, np);
+        {
+            MlgProfScope prof(5, s, work);
+            MLG_TRY(mlg_attention_varlen(Q, K, VT, CTX, LG_D, np, LG_H, tasks, outoff, nt, mq, s));
+        }
+        tr_rows(tag + 13, CTX, 512, np);
+        {
+            // algorithmic FLOPs per live token: 2 (256 x 256 + 512 x 512 + 256 x 512) = 917,504.
+            // Its HBM bytes per token (ctx + bf16 x in 512 + 512, f32 x read + written 1024 +
+            // 1024, bf16 x copy 512 = 3,584) give 256 FLOP/B, near the ridge (2.5 PF / 8 TB/s =
+            // 312): the three GEMM phases, not HBM, bound it, so the slot is
+            // priced against the MFMA peak
+            MlgProfScope prof(8, s, 917504.0 * tok);
+            MLG_TRY(mlg_lg_ffn(CTX, x, cat, 512, np, bw, s, nullptr));
+        }
+        tr_rows(tag + 14, x, LG_D * 4, np);
+        tr_rows(tag + 15, cat, 512, np, 1024);
         return MLG_OK;
     };
     // Layer 0's self block reads one image only (its tokens, its positional encoding), so
     // it runs once per distinct frame of the call -- a frame layout in the secondary
     // buffers -- and its output rows are copied into every pair segment of that frame:
     // the same kernels on the same rows, so the same bits as running it per pair.
-    std::vector<Seg> fsegs;
-    std::vector<int4> f_tasks, f_moves;
-    std::vector<int> f_out;
-    bool self0_done = false;
-    {
-        std::unordered_map<int, int> fidx;
-        std::vector<int> fmap(segs.size());
-        int foff = 0;
-        for (size_t k = 0; k < segs.size(); ++k) {
-            auto it = fidx.find(segs[k].frame);
-            if (it == fidx.end()) {
-                it = fidx.emplace(segs[k].frame, (int)fsegs.size()).first;
-                fsegs.push_back(Seg{foff, segs[k].len, segs[k].frame, 0});
-                foff += (segs[k].len + 63) & ~63;
-            }
-            fmap[k] = it->second;
-        }
-        if (fsegs.size() < segs.size()) {
-            const int NpadF = std::max(foff, 64);
-            int maxqf = 0;
-            double tok = 0, work = 0;
-            for (const Seg& f : fsegs) {
-                f_tasks.push_back(make_int4(f.off, f.len, f.off, f.len));
-                f_out.push_back(f.off);
-                maxqf = std::max(maxqf, f.len);
-                tok += f.len;
-                work += 4.0 * LG_H * 64 * (double)f.len * f.len;
-            }
-            for (size_t k = 0; k < segs.size(); ++k)
-                f_moves.push_back(make_int4(segs[k].off, segs[k].len, fsegs[fmap[k]].off, 0));
-            const int nf = (int)fsegs.size();
-            if (hipMemcpyAsync(SEGS, fsegs.data(), fsegs.size() * sizeof(Seg), hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(TASKS, f_tasks.data(), f_tasks.size() * sizeof(int4), hipMemcpyHostToDevice, s) !=
-                    hipSuccess ||
-                hipMemcpyAsync(OUTOFF, f_out.data(), f_out.size() * sizeof(int), hipMemcpyHostToDevice, s) !=
-                    hipSuccess ||
-                hipMemcpyAsync(MOVES, f_moves.data(), f_moves.size() * sizeof(int4), hipMemcpyHostToDevice, s) !=
-                    hipSuccess)
-                return MLG_EHIP;
-            hipLaunchKernelGGL(k_lg_live, dim3((NpadF + 255) / 256), dim3(256), 0, s, SEGS, nf, LIVE, ROWSEG, NpadF);
-            hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)nf), dim3(256), 0, s, SEGS, kpts, kmax,
-                               (float4*)(base + L.norm));
-            hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)nf), dim3(256), 0, s, SEGS,
-                               (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X2, CAT2, EF2, IND2);
-            MLG_LAUNCH_CHECK();
-            tr_tab(9903, SEGS, fsegs.size() * sizeof(Seg));
-            tr_tab(9904, TASKS, f_tasks.size() * sizeof(int4));
-            tr_rows(9901, X2, LG_D * 4, NpadF);
-            tr_rows(9902, CAT2, 512, NpadF, 1024);
-            {
-                MlgProfScope prof(6, s, 2.0 * tok * 768 * 256);
-                LG_TRY(mlg_lg_proj(true, CAT2, 512, w.self[0].Wqkv, w.self[0].bqkv, (const float*)EF2, LIVE, Q, K, VT, NpadF, s));
-            }
-            tr_heads(9910, Q, NpadF);
-            tr_heads(9911, K, NpadF);
-            tr_heads(9912, VT, NpadF);
-            {
-                MlgProfScope prof(5, s, work);
-                LG_TRY(mlg_attention_varlen(Q, K, VT, CTX, LG_D, NpadF, LG_H, TASKS, OUTOFF, nf, maxqf, s));
-            }
-            tr_rows(9913, CTX, 512, NpadF);
-            {
-                MlgProfScope prof(8, s, 917504.0 * tok);
-                LG_TRY(mlg_lg_ffn(CTX, X2, CAT2, 512, NpadF, w.self[0], s, nullptr));
-            }
-            tr_rows(9914, X2, LG_D * 4, NpadF);
-            tr_rows(9915, CAT2, 512, NpadF, 1024);
-            self0_done = true;
-        }
+    fp.build(segs, LG_H);
+    const bool self0_done = fp.repeats;
+    if (fp.repeats) {
+        const int nf = (int)fp.fsegs.size(), NpadF = fp.NpadF;
+        if (!mlg_upload(SEGS, fp.fsegs, s) || !mlg_upload(TASKS, fp.tasks, s) || !mlg_upload(OUTOFF, fp.out_off, s) ||
+            !mlg_upload(MOVES, fp.moves, s))
+            return MLG_EHIP;
+        hipLaunchKernelGGL(k_pair_live<int*>, dim3((NpadF + 255) / 256), dim3(256), 0, s, SEGS, nf, LIVE, ROWSEG,
+                           NpadF);
+        hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)nf), dim3(256), 0, s, SEGS, kpts, kmax,
+                           (float4*)(base + L.norm));
+        hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)nf), dim3(256), 0, s, SEGS,
+                           (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X2, CAT2, EF2, IND2);
+        MLG_LAUNCH_CHECK();
+        tr_tab(9903, SEGS, fp.fsegs.size() * sizeof(Seg));
+        tr_tab(9904, TASKS, fp.tasks.size() * sizeof(int4));
+        tr_rows(9901, X2, LG_D * 4, NpadF);
+        tr_rows(9902, CAT2, 512, NpadF, 1024);
+        MLG_TRY(self_block(w.self[0], X2, CAT2, EF2, TASKS, OUTOFF, nf, NpadF, fp.maxqf, fp.tok, fp.work, 9900));
     }
-    LG_TRY(upload_layout());
+    MLG_TRY(upload_layout());
     hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)segs.size()), dim3(256), 0, s, SEGS, kpts, kmax, (float4*)(base + L.norm));
     hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)segs.size()), dim3(256), 0, s, SEGS,
                        (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X, CAT, EF, IND,
@@ -1056,32 +980,18 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         for (const Seg& sg : segs) t += sg.len;
         return t;
     };
-    auto attention = [&](bool cross) -> int {
-        const int nt = (int)segs.size();
-        const int o = cross ? nt : 0;
-        double work = 0;  // 4 * heads * q * kv * 64 per task (QK^T and PV)
+    auto attn_work = [&](bool cross) {  // 4 * heads * q * kv * 64 per task (QK^T and PV)
+        double work = 0;
         for (size_t k = 0; k < segs.size(); k += 2) {
             const double a = segs[k].len, b = segs[k + 1].len;
             work += 4.0 * LG_H * 64 * (cross ? 2 * a * b : a * a + b * b);
         }
-        MlgProfScope prof(5, s, work);
-        return mlg_attention_varlen(Q, cross ? Q : K, VT, CTX, LG_D, Npad, LG_H, TASKS + o, OUTOFF + o, nt, maxq, s);
-    };
-    // out_proj / to_out + FFN + residual, fused (lg_ffn.hip)
-    // (conf: the layer's token-confidence / matchability heads, fused into the tail)
-    auto ffn = [&](const mlg_lg_block_i& bw, const mlg_lg_conf_i* conf) -> int {
-        // algorithmic FLOPs per live token: 2 (256 x 256 + 512 x 512 + 256 x 512) = 917,504.
-        // Its HBM bytes per token (ctx + bf16 x in 512 + 512, f32 x read + written 1024 +
-        // 1024, bf16 x copy 512 = 3,584) give 256 FLOP/B, near the ridge (2.5 PF / 8 TB/s =
-        // 312): the three GEMM phases, not HBM, bound it, so the slot is
-        // priced against the MFMA peak
-        MlgProfScope prof(8, s, 917504.0 * live_tokens());
-        return mlg_lg_ffn(CTX, X, CAT, 512, Npad, bw, s, conf);
+        return work;
     };
     // assignment + filter of the listed segment pairs (k = index of image a's segment)
     auto assign = [&](int i, const std::vector<size_t>& ks) -> int {
         // mdesc = final_proj(x) for every token, as bf16 hi + lo; the 1/4 per side folds into S / 16
-        LG_TRY(mlg_gemm_bias_split_bf16(CAT, 512, w.Wfinal[i], w.bfinal[i], MDH, MDH + (size_t)Npad * LG_D, Npad, LG_D,
+        MLG_TRY(mlg_gemm_bias_split_bf16(CAT, 512, w.Wfinal[i], w.bfinal[i], MDH, MDH + (size_t)Npad * LG_D, Npad, LG_D,
                                          LG_D, s));
         if (t_trace) trace(i * 100 + 40, MDH, 64, 32, 32, 32, (size_t)Npad * 32, Npad / 64, s);
         // one table upload for all chunks (the per-layer statistics read-back orders its
@@ -1102,8 +1012,7 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             h_asg.push_back(a);
             if (stop_layer) stop_layer[a.pair] = i + 1;
         }
-        if (hipMemcpyAsync(ASG, h_asg.data(), h_asg.size() * sizeof(Asg), hipMemcpyHostToDevice, s) != hipSuccess)
-            return MLG_EHIP;
+        if (!mlg_upload(ASG, h_asg, s)) return MLG_EHIP;
         tr_tab(i * 100 + 41, ASG, h_asg.size() * sizeof(Asg));
         for (size_t c0 = 0; c0 < ks.size(); c0 += L.asg_cap) {
             const size_t c1 = std::min(ks.size(), c0 + L.asg_cap);
@@ -1131,31 +1040,23 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
 
     std::vector<int> stats(segs.size() * 2);
     for (int i = 0; i < LG_L && !segs.empty(); ++i) {
-        // self block: projection + rotary + head split fused in the GEMM epilogue (layer 0's
-        // already ran per frame above when frames repeat)
-        if (!(i == 0 && self0_done)) {
-            {
-                MlgProfScope prof(6, s, 2.0 * live_tokens() * 768 * 256);
-                LG_TRY(mlg_lg_proj(true, CAT, 512, w.self[i].Wqkv, w.self[i].bqkv, (const float*)EF, LIVE, Q, K, VT, Npad, s));
-            }
-            tr_heads(i * 100 + 10, Q, Npad);
-            tr_heads(i * 100 + 11, K, Npad);
-            tr_heads(i * 100 + 12, VT, Npad);
-            LG_TRY(attention(false));
-            tr_rows(i * 100 + 13, CTX, 512, Npad);
-            LG_TRY(ffn(w.self[i], nullptr));
-            tr_rows(i * 100 + 14, X, LG_D * 4, Npad);
-            tr_rows(i * 100 + 15, CAT, 512, Npad, 1024);
-        }
+        const int nt = (int)segs.size();
+        // self block (layer 0's already ran per frame above when frames repeat)
+        if (!(i == 0 && self0_done))
+            MLG_TRY(self_block(w.self[i], X, CAT, EF, TASKS, OUTOFF, nt, Npad, att.maxq, live_tokens(), attn_work(false),
+                               i * 100));
         // cross block
         {
             MlgProfScope prof(6, s, 2.0 * live_tokens() * 512 * 256);
-            LG_TRY(mlg_lg_proj(false, CAT, 512, w.cross[i].Wqkv, w.cross[i].bqkv, nullptr, LIVE, Q, nullptr, VT,
-                               Npad, s));
+            MLG_TRY(mlg_lg_proj(false, CAT, 512, w.cross[i].Wqkv, w.cross[i].bqkv, nullptr, LIVE, Q, nullptr, VT,
+                                Npad, s));
         }
         tr_heads(i * 100 + 20, Q, Npad);
         tr_heads(i * 100 + 21, VT, Npad);
-        LG_TRY(attention(true));
+        {
+            MlgProfScope prof(5, s, attn_work(true));
+            MLG_TRY(mlg_attention_varlen(Q, Q, VT, CTX, LG_D, Npad, LG_H, TASKS + nt, OUTOFF + nt, nt, att.maxq, s));
+        }
         tr_rows(i * 100 + 22, CTX, 512, Npad);
         // layer i's heads on the updated tokens: matchability log-sigmoid (the assignment's
         // certainty term) and, before the last layer, confidences + early-stop / prune flags
@@ -1166,7 +1067,10 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         // (depth_confidence <= 0: upstream computes no token confidences, so its pruning
         // mask is matchability alone -- a threshold of -inf drops the "low confidence is
         // never pruned" term; the stop bit is unused then)
-        LG_TRY(ffn(w.cross[i], &heads));
+        {
+            MlgProfScope prof(8, s, 917504.0 * live_tokens());  // priced as the self block's tail
+            MLG_TRY(mlg_lg_ffn(CTX, X, CAT, 512, Npad, w.cross[i], s, &heads));  // + the heads, fused into the tail
+        }
         tr_rows(i * 100 + 23, X, LG_D * 4, Npad);
         tr_rows(i * 100 + 24, CAT, 512, Npad, 1024);
         tr_rows(i * 100 + 25, LZ, 4, Npad);
@@ -1175,7 +1079,7 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         if (last) {
             std::vector<size_t> ks;
             for (size_t k = 0; k < segs.size(); k += 2) ks.push_back(k);
-            LG_TRY(assign(i, ks));
+            MLG_TRY(assign(i, ks));
             break;
         }
         hipLaunchKernelGGL(k_lg_segstats, dim3((unsigned)segs.size()), dim3(256), 0, s, SEGS, KEEP, STATS);
@@ -1185,49 +1089,15 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
                 hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return MLG_EHIP;
-        // early stop per pair; point pruning per segment
-        std::vector<char> stop(segs.size() / 2, 0);
-        std::vector<size_t> stopped;
-        bool any_prune = false;
-        for (size_t k = 0; k < segs.size(); k += 2) {
-            const int p = pair_of[k / 2];
-            if (depth_conf > 0.f) {
-                const float low = (float)(stats[2 * k] + stats[2 * k + 2]);
-                const float ratio = 1.0f - low / (float)orig_total[p];
-                if (ratio > depth_conf) {
-                    stop[k / 2] = 1;
-                    stopped.push_back(k);
-                }
-            }
-            if (!stop[k / 2] && width_conf > 0.f)
-                for (int q = 0; q < 2; ++q)
-                    if (segs[k + q].len > pruning_min && stats[2 * (k + q) + 1] != segs[k + q].len) any_prune = true;
-        }
-        if (!stopped.empty()) LG_TRY(assign(i, stopped));  // the matchability lz came with the confidences
-        if (stopped.empty() && !any_prune) continue;
+        // early stop per pair; point pruning per segment; the compacted layout
+        dec.decide(segs, pair_of, lay.orig_total, stats.data(), depth_conf, width_conf, pruning_min, i);
+        if (!dec.stopped.empty()) MLG_TRY(assign(i, dec.stopped));  // the matchability lz came with the confidences
+        if (!dec.changed()) continue;
         // compact: drop stopped pairs, prune segments above the threshold
-        h_moves.clear();
-        std::vector<Seg> nsegs;
-        std::vector<int> npair;
-        int noff = 0;
-        for (size_t k = 0; k < segs.size(); k += 2) {
-            if (stop[k / 2]) continue;
-            for (int q = 0; q < 2; ++q) {
-                const Seg sg = segs[k + q];
-                const bool prune = width_conf > 0.f && sg.len > pruning_min;
-                const int nl = prune ? stats[2 * (k + q) + 1] : sg.len;
-                h_moves.push_back(make_int4(sg.off, sg.len, noff, prune ? 0 : 1));
-                nsegs.push_back(Seg{noff, nl, sg.frame, 0});
-                noff += (nl + 63) & ~63;
-            }
-            npair.push_back(pair_of[k / 2]);
-        }
-        if (!h_moves.empty()) {
-            if (!stopped.empty() && hipStreamSynchronize(s) != hipSuccess) return MLG_EHIP;  // h_asg in flight
-            if (hipMemcpyAsync(MOVES, h_moves.data(), h_moves.size() * sizeof(int4), hipMemcpyHostToDevice, s) !=
-                hipSuccess)
-                return MLG_EHIP;
-            hipLaunchKernelGGL(k_lg_compact, dim3((unsigned)h_moves.size()), dim3(256), 0, s, MOVES, KEEP, X, EF,
+        if (!dec.moves.empty()) {
+            if (!dec.stopped.empty() && hipStreamSynchronize(s) != hipSuccess) return MLG_EHIP;  // h_asg in flight
+            if (!mlg_upload(MOVES, dec.moves, s)) return MLG_EHIP;
+            hipLaunchKernelGGL(k_lg_compact, dim3((unsigned)dec.moves.size()), dim3(256), 0, s, MOVES, KEEP, X, EF,
                                IND, X2, CAT2, EF2, IND2);
             MLG_LAUNCH_CHECK();
             std::swap(X, X2);
@@ -1235,23 +1105,16 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             std::swap(EF, EF2);
             std::swap(IND, IND2);
         }
-        // an empty side after pruning ends that pair with no matches (reference loop break)
-        segs.clear();
-        pair_of.clear();
-        for (size_t k = 0; k < nsegs.size(); k += 2) {
-            if (nsegs[k].len == 0 || nsegs[k + 1].len == 0) {
-                if (stop_layer) stop_layer[npair[k / 2]] = i + 2;
-                continue;
-            }
-            segs.push_back(nsegs[k]);
-            segs.push_back(nsegs[k + 1]);
-            pair_of.push_back(npair[k / 2]);
-        }
-        Npad = std::max(noff, 64);
+        // the old layout's upload completed before the read-back above: its vectors may go
+        segs.swap(dec.segs);
+        pair_of.swap(dec.pair_of);
+        Npad = dec.Npad;
+        if (stop_layer)
+            for (const auto& pl : dec.stop_layer) stop_layer[pl.first] = pl.second;
         tl = i + 1;
-        if (!h_moves.empty()) tr_tab(tl * 100 + 31, MOVES, h_moves.size() * sizeof(int4));
-        if (!segs.empty()) LG_TRY(upload_layout());
-        if (!h_moves.empty() && !segs.empty()) tr_rows(tl * 100 + 30, X, LG_D * 4, Npad);
+        if (!dec.moves.empty()) tr_tab(tl * 100 + 31, MOVES, dec.moves.size() * sizeof(int4));
+        if (!segs.empty()) MLG_TRY(upload_layout());
+        if (!dec.moves.empty() && !segs.empty()) tr_rows(tl * 100 + 30, X, LG_D * 4, Npad);
         stats.assign(segs.size() * 2, 0);
     }
     if (t_trace) {

@@ -38,11 +38,11 @@
 #include <math.h>
 
 #include <algorithm>
-#include <unordered_map>
 #include <vector>
 
 #include "common.h"
 #include "kernels.h"
+#include "pair_plan.h"
 #include "../../include/mlgate.h"
 
 namespace {
@@ -913,7 +913,7 @@ __global__ __launch_bounds__(64) void k_lf_fine_match(const float* __restrict__ 
     }
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
+using pair_plan::a256;
 
 struct ConvSpec {
     int cin, cout, k, s;
@@ -963,20 +963,14 @@ int conv(const mlg_loftr_weights& w, int idx, const bf16_t* in, int B, int H, in
                          act, sp.cout, (int)M, sp.cout, sp.cin, s);
 }
 
-#define LF_TRY(x)                    \
-    do {                             \
-        int rc_ = (x);               \
-        if (rc_ != MLG_OK) return rc_; \
-    } while (0)
-
 // one BasicBlock: in (f32 x + bf16 xb) -> out (same buffers), stride 1 or 2
 int basic_block(const mlg_loftr_weights& w, int c1, int c2, int cds, int B, int H, int W, float* x, bf16_t* xb,
                 bf16_t* yb, float* rf, const bf16_t* zero, hipStream_t s) {
     const int st = CONVS[c1].s, Ho = (H + st - 1) / st, Wo = (W + st - 1) / st;
-    LF_TRY(conv(w, c1, xb, B, H, W, zero, nullptr, nullptr, yb, 1, s));  // relu(bn1(conv1 x))
+    MLG_TRY(conv(w, c1, xb, B, H, W, zero, nullptr, nullptr, yb, 1, s));  // relu(bn1(conv1 x))
     const float* R = x;
     if (cds >= 0) {  // bn(downsample x) -> rf
-        LF_TRY(conv(w, cds, xb, B, H, W, zero, nullptr, rf, nullptr, 0, s));
+        MLG_TRY(conv(w, cds, xb, B, H, W, zero, nullptr, rf, nullptr, 0, s));
         R = rf;
     }
     // relu(R + bn2(conv2 y)) -> x (f32) + xb; R may alias x (stride 1: same shape)
@@ -999,7 +993,7 @@ int fpn_merge(const mlg_loftr_weights& w, int idx, const bf16_t* in, int B, int 
     if (MLG_LF_FPN_FUSED)
         return mlg_gemm_conv_upadd(in, sp.cin, (const bf16_t*)w.conv_w[idx], w.conv_b[idx], coarser, H / 2, W / 2, out,
                                    B * H * W, sp.cout, sp.cin, s);
-    LF_TRY(conv(w, idx, in, B, H, W, nullptr, nullptr, tf, nullptr, 0, s));
+    MLG_TRY(conv(w, idx, in, B, H, W, nullptr, nullptr, tf, nullptr, 0, s));
     const long n = (long)B * H * W * (sp.cout / 4);
     hipLaunchKernelGGL(k_lf_up_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tf, coarser, B, H / 2, W / 2,
                        sp.cout, out);
@@ -1053,32 +1047,32 @@ int mlg_loftr_features(const mlg_loftr_weights* wp, const uint8_t* frames_in, in
                        C, w.stem_w, w.stem_b, xf, xb);
     MLG_LAUNCH_CHECK();
     // layer1 (1/2, 128)
-    LF_TRY(basic_block(w, 0, 1, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
-    LF_TRY(basic_block(w, 2, 3, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 0, 1, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 2, 3, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
     // x1 (bf16) is needed by the FPN: kept in `fine` (scratch until the end: fine is
     // written last)
     bf16_t* x1b = (bf16_t*)fine;
     if (hipMemcpyAsync(x1b, xb, (size_t)B * H2 * W2 * 128 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return MLG_EHIP;
     // layer2 (1/4, 256p)
-    LF_TRY(basic_block(w, 4, 5, 6, B, H2, W2, xf, xb, yb, rf, zero, s));
-    LF_TRY(basic_block(w, 7, 8, -1, B, H4, W4, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 4, 5, 6, B, H2, W2, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 7, 8, -1, B, H4, W4, xf, xb, yb, rf, zero, s));
     bf16_t* x2b = (bf16_t*)c2;  // bf16 copy of x2 (c2 is free until the FPN needs its f32 slot)
     if (hipMemcpyAsync(x2b, xb, (size_t)B * H4 * W4 * 256 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return MLG_EHIP;
     // layer3 (1/8, 256)
-    LF_TRY(basic_block(w, 9, 10, 11, B, H4, W4, xf, xb, yb, rf, zero, s));
-    LF_TRY(basic_block(w, 12, 13, -1, B, H8, W8, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 9, 10, 11, B, H4, W4, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 12, 13, -1, B, H8, W8, xf, xb, yb, rf, zero, s));
     // FPN: x3_out = outconv3(x3) -> coarse output (f32)
-    LF_TRY(conv(w, 14, xb, B, H8, W8, zero, nullptr, coarse, nullptr, 0, s));
+    MLG_TRY(conv(w, 14, xb, B, H8, W8, zero, nullptr, coarse, nullptr, 0, s));
     // x2_out = outconv2(x2) + up(x3_out) -> bf16 -> conv + BN + leaky -> conv
-    LF_TRY(fpn_merge(w, 15, x2b, B, H4, W4, coarse, tf, yb, s));
-    LF_TRY(conv(w, 16, yb, B, H4, W4, zero, nullptr, nullptr, xb, 2, s));
-    LF_TRY(conv(w, 17, xb, B, H4, W4, zero, nullptr, c2, nullptr, 0, s));  // x2_out f32 (1/4, 256p)
+    MLG_TRY(fpn_merge(w, 15, x2b, B, H4, W4, coarse, tf, yb, s));
+    MLG_TRY(conv(w, 16, yb, B, H4, W4, zero, nullptr, nullptr, xb, 2, s));
+    MLG_TRY(conv(w, 17, xb, B, H4, W4, zero, nullptr, c2, nullptr, 0, s));  // x2_out f32 (1/4, 256p)
     // x1_out = outconv1(x1) + up(x2_out) -> conv + BN + leaky -> conv -> fine
-    LF_TRY(fpn_merge(w, 18, x1b, B, H2, W2, c2, tf, yb, s));
-    LF_TRY(conv(w, 19, yb, B, H2, W2, zero, nullptr, nullptr, xb, 2, s));
-    LF_TRY(conv(w, 20, xb, B, H2, W2, zero, nullptr, fine, nullptr, 0, s));
+    MLG_TRY(fpn_merge(w, 18, x1b, B, H2, W2, c2, tf, yb, s));
+    MLG_TRY(conv(w, 19, yb, B, H2, W2, zero, nullptr, nullptr, xb, 2, s));
+    MLG_TRY(conv(w, 20, xb, B, H2, W2, zero, nullptr, fine, nullptr, 0, s));
     (void)c3;
     return MLG_OK;
 }
@@ -1138,12 +1132,12 @@ int encoder_layer(const mlg_loftr_layer& lw, const LayerBufs& b, int d, long x0,
     // divided once here rather than per (k, v) product in k_lf_kv*)
     const float vl = (float)L;
     if (x0 == src0) {
-        LF_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w, nullptr, nullptr, 0, qkv, 3 * d, nullptr,
+        MLG_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w, nullptr, nullptr, 0, qkv, 3 * d, nullptr,
                              0, 3, 2 * d, (int)rows, 3 * d, d, s, vl));
     } else {
-        LF_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w, nullptr, nullptr, 0, qkv, 3 * d, nullptr,
+        MLG_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w, nullptr, nullptr, 0, qkv, 3 * d, nullptr,
                              0, 3, d, (int)rows, d, d, s));
-        LF_TRY(mlg_gemm_conv(b.cat + src0 * 2 * d, 2 * d, (const bf16_t*)lw.w + (size_t)d * d, nullptr, nullptr, 0,
+        MLG_TRY(mlg_gemm_conv(b.cat + src0 * 2 * d, 2 * d, (const bf16_t*)lw.w + (size_t)d * d, nullptr, nullptr, 0,
                              qkv + d, 3 * d, nullptr, 0, 3, d, (int)rows, 2 * d, d, s, vl));
     }
     float* kv = b.kv + (size_t)(x0 / L) * 8 * dh * dh;
@@ -1192,7 +1186,7 @@ int encoder_layer(const mlg_loftr_layer& lw, const LayerBufs& b, int d, long x0,
         return mlg_lg_ffn(b.msg + x0 * d, b.x + x0 * d, b.cat + x0 * 2 * d, 2 * d, (int)rows, bw, s, nullptr, 2);
     }
     // merge -> norm1 -> bf16 into cat[:, d:]
-    LF_TRY(mlg_gemm_conv(b.msg + x0 * d, d, (const bf16_t*)lw.wmerge, nullptr, nullptr, 0, b.t + x0 * d, d, nullptr,
+    MLG_TRY(mlg_gemm_conv(b.msg + x0 * d, d, (const bf16_t*)lw.wmerge, nullptr, nullptr, 0, b.t + x0 * d, d, nullptr,
                          0, 0, 0, (int)rows, d, d, s));
     const unsigned lnb = (unsigned)((rows + 3) / 4);
     if (d == 256)
@@ -1203,9 +1197,9 @@ int encoder_layer(const mlg_loftr_layer& lw, const LayerBufs& b, int d, long x0,
                            (float*)nullptr, b.cat + x0 * 2 * d + d, 2 * d);
     MLG_LAUNCH_CHECK();
     // MLP: relu([x | msg] W1^T) W2^T -> norm2 -> residual
-    LF_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w1, nullptr, nullptr, 0, nullptr, 0,
+    MLG_TRY(mlg_gemm_conv(b.cat + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w1, nullptr, nullptr, 0, nullptr, 0,
                          b.h + x0 * 2 * d, 2 * d, 1, 2 * d, (int)rows, 2 * d, 2 * d, s));
-    LF_TRY(mlg_gemm_conv(b.h + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w2, nullptr, nullptr, 0, b.t + x0 * d, d, nullptr,
+    MLG_TRY(mlg_gemm_conv(b.h + x0 * 2 * d, 2 * d, (const bf16_t*)lw.w2, nullptr, nullptr, 0, b.t + x0 * d, d, nullptr,
                          0, 0, 0, (int)rows, d, 2 * d, s));
     if (d == 256)
         hipLaunchKernelGGL(k_lf_ln<256>, dim3(lnb), dim3(256), 0, s, b.t + x0 * d, lw.ln2_g, lw.ln2_b, rows, 1,
@@ -1226,10 +1220,10 @@ int transformer(const mlg_loftr_layer* layers, int nl, const LayerBufs& b, int d
     for (int i = first; i < nl; ++i) {
         const TailW* tw = tails ? tails + i : nullptr;
         if (i % 2 == 0) {
-            LF_TRY(encoder_layer(layers[i], b, d, 0, 0, 2 * nseg, L, s, tw));
+            MLG_TRY(encoder_layer(layers[i], b, d, 0, 0, 2 * nseg, L, s, tw));
         } else {
-            LF_TRY(encoder_layer(layers[i], b, d, 0, half, nseg, L, s, tw));
-            LF_TRY(encoder_layer(layers[i], b, d, half, 0, nseg, L, s, tw));
+            MLG_TRY(encoder_layer(layers[i], b, d, 0, half, nseg, L, s, tw));
+            MLG_TRY(encoder_layer(layers[i], b, d, half, 0, nseg, L, s, tw));
         }
     }
     return MLG_OK;
@@ -1411,21 +1405,12 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     if (w.coarse_tails)
         tails_at((char*)w.coarse_tails, tails);  // packed once (mlg_loftr_pack_tails)
     else
-        LF_TRY(pack_tails(w, (char*)at(ML.tails), tails, s));
+        MLG_TRY(pack_tails(w, (char*)at(ML.tails), tails, s));
     const TailW* tw = tails;
     // the distinct frames of the call (first-appearance order) and each pair side's index
-    std::vector<int32_t> h_ufr, h_umap(2 * P);
-    {
-        std::unordered_map<int32_t, int32_t> pos;
-        for (int g = 0; g < 2 * P; ++g) {
-            auto it = pos.find(h_frames[g]);
-            if (it == pos.end()) {
-                it = pos.emplace(h_frames[g], (int32_t)h_ufr.size()).first;
-                h_ufr.push_back(h_frames[g]);
-            }
-            h_umap[g] = it->second;
-        }
-    }
+    const pair_plan::Distinct uf = pair_plan::distinct_frames(h_frames.data(), h_frames.size());
+    const std::vector<int32_t>& h_ufr = uf.unique;
+    const std::vector<int32_t>& h_umap = uf.index;
     const int NU = (int)h_ufr.size();
     if (NU < 2 * P) {
         int32_t* ufr = (int32_t*)at(ML.ufr);
@@ -1437,7 +1422,7 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((urows * 64 + 255) / 256)), dim3(256), 0, s, coarse, ufr, L,
                            pe, bc.x, bc.cat, (int)urows);
         MLG_LAUNCH_CHECK();
-        LF_TRY(encoder_layer(w.coarse[0], bc, 256, 0, 0, NU, L, s, tw));
+        MLG_TRY(encoder_layer(w.coarse[0], bc, 256, 0, 0, NU, L, s, tw));
         // the NU frames' rows aside in the dead q / k / v buffer (2 P L x 3 KiB >= NU L x
         // 1.5 KiB), then laid out per pair side
         float* tx = bc.qkv;
@@ -1448,12 +1433,12 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         hipLaunchKernelGGL(k_lf_gather_rows, dim3((unsigned)((crows * 96 + 255) / 256)), dim3(256), 0, s, tx, tc,
                            umap, L, crows, bc.x, bc.cat);
         MLG_LAUNCH_CHECK();
-        LF_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw, 1));
+        MLG_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw, 1));
     } else {
         hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((crows * 64 + 255) / 256)), dim3(256), 0, s, coarse, frm, L,
                            pe, bc.x, bc.cat, (int)crows);
         MLG_LAUNCH_CHECK();
-        LF_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw));
+        MLG_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw));
     }
     // the coarse similarity: split-bf16 operands (3 bf16 MFMA products at ~6x the exact-f32
     // MFMA's rate) or the exact-f32 MFMA (mlg_set_loftr_similarity(1)).  The split GEMM
@@ -1475,12 +1460,12 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     for (int p0 = 0; p0 < P; p0 += G) {
         const unsigned g = (unsigned)std::min(G, P - p0);
         if (split) {  // the group's g similarities as one tile queue
-            LF_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p0 * L * 512, CS + ((size_t)P + p0) * L * 512, L, Lpad, 256, S,
+            MLG_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p0 * L * 512, CS + ((size_t)P + p0) * L * 512, L, Lpad, 256, S,
                                             lds, L, s, (int)g, (long)L * 512));
         } else {
             for (int q = 0; q < (int)g; ++q) {
                 const int p = p0 + q;
-                LF_TRY(mlg_similarity_f32_loftr(bc.x + (size_t)p * L * 256, L, bc.x + ((size_t)P + p) * L * 256, L, 256,
+                MLG_TRY(mlg_similarity_f32_loftr(bc.x + (size_t)p * L * 256, L, bc.x + ((size_t)P + p) * L * 256, L, 256,
                                                 S + (size_t)q * L * lds, L, s));
             }
         }
@@ -1521,16 +1506,16 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         const long frows = (long)2 * M * 25;
         // merge_feat on [window | down_proj(coarse)]: the window half per token, the
         // coarse half once per (side, match)
-        LF_TRY(mlg_gemm_conv(win, 128, (const bf16_t*)w.merge_wf, nullptr, nullptr, 0, bf.t, 128, nullptr, 0, 0, 0,
+        MLG_TRY(mlg_gemm_conv(win, 128, (const bf16_t*)w.merge_wf, nullptr, nullptr, 0, bf.t, 128, nullptr, 0, 0, 0,
                              (int)frows, 128, 128, s));
-        LF_TRY(mlg_gemm_conv(crow, 256, (const bf16_t*)w.down_w, w.down_b, nullptr, 0, nullptr, 0, cd, 128, 0, 0,
+        MLG_TRY(mlg_gemm_conv(crow, 256, (const bf16_t*)w.down_w, w.down_b, nullptr, 0, nullptr, 0, cd, 128, 0, 0,
                              2 * M, 128, 256, s));
-        LF_TRY(mlg_gemm_conv(cd, 128, (const bf16_t*)w.merge_wc, w.merge_b, nullptr, 0, cm, 128, nullptr, 0, 0, 0,
+        MLG_TRY(mlg_gemm_conv(cd, 128, (const bf16_t*)w.merge_wc, w.merge_b, nullptr, 0, cm, 128, nullptr, 0, 0, 0,
                              2 * M, 128, 128, s));
         hipLaunchKernelGGL(k_lf_fine_tokens, dim3((unsigned)((frows * 32 + 255) / 256)), dim3(256), 0, s, bf.t, cm,
                            frows, bf.x, bf.cat);
         MLG_LAUNCH_CHECK();
-        LF_TRY(transformer(w.fine, 2, bf, 128, M, 25, s));
+        MLG_TRY(transformer(w.fine, 2, bf, 128, M, 25, s));
         hipLaunchKernelGGL(k_lf_fine_match, dim3(M), dim3(64), 0, s, bf.x, M, dmp, dms, mi, mj, mconf, L, wc,
                            (float)H / (float)hc, (float)H / (float)Hf, kpts0, kpts1, conf);
         MLG_LAUNCH_CHECK();
@@ -1599,11 +1584,11 @@ extern "C" int mlg_op_loftr_coarse_layer(const mlg_loftr_weights* w, int layer, 
         if (w->coarse_tails)
             tails_at((char*)w->coarse_tails, tails);
         else
-            LF_TRY(pack_tails(*w, base + M.tails, tails, s));
+            MLG_TRY(pack_tails(*w, base + M.tails, tails, s));
     }
     const TailW* tw = fused ? tails + layer : nullptr;
     const long half = (long)nseg * L;
     if (layer % 2 == 0) return encoder_layer(w->coarse[layer], b, 256, 0, 0, 2 * nseg, L, s, tw);
-    LF_TRY(encoder_layer(w->coarse[layer], b, 256, 0, half, nseg, L, s, tw));
+    MLG_TRY(encoder_layer(w->coarse[layer], b, 256, 0, half, nseg, L, s, tw));
     return encoder_layer(w->coarse[layer], b, 256, half, 0, nseg, L, s, tw);
 }

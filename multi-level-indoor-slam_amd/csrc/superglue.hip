@@ -33,16 +33,18 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "pair_plan.h"
 
 namespace {
 
-struct SgSeg {
-    int off, len, frame, pad;
-};
+using pair_plan::a256;
+using pair_plan::Seg;
+static_assert(sizeof(pair_plan::Task) == sizeof(int4),
+              "the host tables are uploaded by bytes into the kernels' int4 tables");
 
 // k_sg_gather: row r of segment s (token t of frame f) -> X[r] = desc[f][t] (f32),
 // h3[r] = kenc layers 1-3 on (x, y, score) (bf16, 128).  Dead rows: zeros.
-__global__ __launch_bounds__(128) void k_sg_gather(const SgSeg* __restrict__ segs, int nseg, int Npad,
+__global__ __launch_bounds__(128) void k_sg_gather(const Seg* __restrict__ segs, int nseg, int Npad,
                                                    const float* __restrict__ kpts, const float* __restrict__ kscores,
                                                    const float* __restrict__ desc, int kmax, float W, float H,
                                                    const float* __restrict__ w1, const float* __restrict__ b1,
@@ -276,8 +278,6 @@ __global__ __launch_bounds__(1024) void k_sg_select(const SgPair* __restrict__ p
     if (tid == 0) nmatch[pid] = base;
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // pairs per Sinkhorn chunk: S and T of a chunk within SG_CHUNK_MB (larger launches
 // amortise the ramp; 128 MB would keep them in the 256 MB last-level cache), at most 64
 #ifndef SG_CHUNK_MB
@@ -315,7 +315,7 @@ SgLayout sg_layout(int P, int kmax) {
     L.live = take(N);
     L.ef = take(N * 64 * 4);
     L.md = take(N * 256 * 4);
-    L.segs = take((size_t)2 * P * sizeof(SgSeg));
+    L.segs = take((size_t)2 * P * sizeof(Seg));
     L.tasks = take((size_t)4 * P * sizeof(int4));
     L.outoff = take((size_t)4 * P * 4);
     L.S = take(ch * kmax * ldS * 4);
@@ -329,28 +329,6 @@ SgLayout sg_layout(int P, int kmax) {
     L.total = o;
     return L;
 }
-
-__global__ void k_sg_live(const SgSeg* __restrict__ segs, int nseg, uint8_t* __restrict__ live, int Npad) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= Npad) return;
-    int lo = 0, hi = nseg - 1, sg = -1;
-    while (lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        if (segs[mid].off <= r) {
-            sg = mid;
-            lo = mid + 1;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    live[r] = sg >= 0 && r < segs[sg].off + segs[sg].len;
-}
-
-#define SG_TRY(x)                      \
-    do {                               \
-        int rc_ = (x);                 \
-        if (rc_ != MLG_OK) return rc_; \
-    } while (0)
 
 }  // namespace
 
@@ -381,7 +359,7 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     uint8_t* LIVE = (uint8_t*)at(L.live);
     float* EF = (float*)at(L.ef);  // identity rotary factors (lg_fac4 layout)
     float* MD = (float*)at(L.md);
-    SgSeg* SEGS = (SgSeg*)at(L.segs);
+    Seg* SEGS = (Seg*)at(L.segs);
     int4* TASKS = (int4*)at(L.tasks);
     int* OUTOFF = (int*)at(L.outoff);
     float* S = (float*)at(L.S);
@@ -394,41 +372,20 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     int32_t* CIDX = (int32_t*)at(L.cidx);
 
     if (hipMemsetAsync(nmatch, 0, sizeof(int32_t) * P, s) != hipSuccess) return MLG_EHIP;
-    // segments: pair p -> [a | b], empty sides skipped (no matches, as the reference's early exit)
-    std::vector<SgSeg> segs;
-    std::vector<int> pair_of;
-    int off = 0;
-    for (int p = 0; p < P; ++p) {
-        const int la = counts[pa[p]], lb = counts[pb[p]];
-        if (la < 0 || la > kmax || lb < 0 || lb > kmax) return MLG_EINVAL;
-        if (la == 0 || lb == 0) continue;
-        segs.push_back(SgSeg{off, la, pa[p], 0});
-        off += (la + 63) & ~63;
-        segs.push_back(SgSeg{off, lb, pb[p], 0});
-        off += (lb + 63) & ~63;
-        pair_of.push_back(p);
-    }
+    // segments (pair p -> [a | b], empty sides skipped) and the attention tables: pageable
+    // host tables (pair_plan.h), alive until the synchronisation this function ends with
+    pair_plan::Segments lay;
+    pair_plan::AttnTables att;
+    if (!lay.build(counts, pa, pb, P, kmax)) return MLG_EINVAL;
+    const std::vector<Seg>& segs = lay.segs;
+    const std::vector<int>& pair_of = lay.pair_of;
     if (segs.empty()) return hipStreamSynchronize(s) == hipSuccess ? MLG_OK : MLG_EHIP;
-    const int Npad = off, nseg = (int)segs.size(), np = nseg / 2;
-    std::vector<int4> h_tasks;
-    std::vector<int> h_out;
-    int maxq = 0;
-    for (int k = 0; k < nseg; ++k) {
-        h_tasks.push_back(make_int4(segs[k].off, segs[k].len, segs[k].off, segs[k].len));
-        maxq = std::max(maxq, segs[k].len);
-    }
-    for (int k = 0; k < nseg; k += 2) {
-        h_tasks.push_back(make_int4(segs[k].off, segs[k].len, segs[k + 1].off, segs[k + 1].len));
-        h_tasks.push_back(make_int4(segs[k + 1].off, segs[k + 1].len, segs[k].off, segs[k].len));
-    }
-    for (int rep = 0; rep < 2; ++rep)
-        for (int k = 0; k < nseg; ++k) h_out.push_back(segs[k].off);
-    if (hipMemcpyAsync(SEGS, segs.data(), segs.size() * sizeof(SgSeg), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(TASKS, h_tasks.data(), h_tasks.size() * sizeof(int4), hipMemcpyHostToDevice, s) !=
-            hipSuccess ||
-        hipMemcpyAsync(OUTOFF, h_out.data(), h_out.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)
+    const int Npad = lay.Npad, nseg = (int)segs.size(), np = nseg / 2;
+    att.build(segs);
+    const int maxq = att.maxq;
+    if (!mlg_upload(SEGS, segs, s) || !mlg_upload(TASKS, att.tasks, s) || !mlg_upload(OUTOFF, att.out_off, s))
         return MLG_EHIP;
-    hipLaunchKernelGGL(k_sg_live, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, nseg, LIVE, Npad);
+    hipLaunchKernelGGL(k_pair_live<>, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, nseg, LIVE, Npad);
     hipLaunchKernelGGL(k_sg_fill_rot, dim3((unsigned)(((long)Npad * 16 + 255) / 256)), dim3(256), 0, s,
                        (float4*)EF, (long)Npad * 16);
     // keypoint encoder: layers 1-3 on the VALU, 4-5 as GEMMs; x = desc + kenc
@@ -436,18 +393,18 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
                        (float)W, (float)H, w.kenc_w[0], w.kenc_b[0], w.kenc_w[1], w.kenc_b[1], w.kenc_w[2],
                        w.kenc_b[2], X, H3);
     MLG_LAUNCH_CHECK();
-    SG_TRY(mlg_gemm_conv(H3, 128, w.kenc_w4, w.kenc_b4, nullptr, 0, nullptr, 0, H4, 256, 1, 256, Npad, 256, 128, s));
-    SG_TRY(mlg_gemm_conv(H4, 256, w.kenc_w5, w.kenc_b5, X, 256, X, 256, CAT, 512, 0, 0, Npad, 256, 256, s));
+    MLG_TRY(mlg_gemm_conv(H3, 128, w.kenc_w4, w.kenc_b4, nullptr, 0, nullptr, 0, H4, 256, 1, 256, Npad, 256, 128, s));
+    MLG_TRY(mlg_gemm_conv(H4, 256, w.kenc_w5, w.kenc_b5, X, 256, X, 256, CAT, 512, 0, 0, Npad, 256, 256, s));
     // the GNN: 18 layers, self / cross alternating, every projection from the pre-layer states
     for (int l = 0; l < 18; ++l) {
         const bool cross = (l & 1) != 0;
-        SG_TRY(mlg_lg_proj(true, CAT, 512, w.layer[l].Wqkv, w.layer[l].bqkv, EF, LIVE, Q, K, VT, Npad, s));
-        SG_TRY(mlg_attention_varlen(Q, K, VT, CTX, 256, Npad, 4, TASKS + (cross ? nseg : 0),
+        MLG_TRY(mlg_lg_proj(true, CAT, 512, w.layer[l].Wqkv, w.layer[l].bqkv, EF, LIVE, Q, K, VT, Npad, s));
+        MLG_TRY(mlg_attention_varlen(Q, K, VT, CTX, 256, Npad, 4, TASKS + (cross ? nseg : 0),
                                     OUTOFF + (cross ? nseg : 0), nseg, maxq, s));
-        SG_TRY(mlg_lg_ffn(CTX, X, CAT, 512, Npad, w.layer[l], s, nullptr, 1));
+        MLG_TRY(mlg_lg_ffn(CTX, X, CAT, 512, Npad, w.layer[l], s, nullptr, 1));
     }
     // matching descriptors
-    SG_TRY(mlg_gemm_conv(CAT, 512, w.Wfinal, w.bfinal, nullptr, 0, MD, 256, nullptr, 0, 0, 0, Npad, 256, 256, s));
+    MLG_TRY(mlg_gemm_conv(CAT, 512, w.Wfinal, w.bfinal, nullptr, 0, MD, 256, nullptr, 0, 0, 0, Npad, 256, 256, s));
     // per chunk of pairs: scores and their transpose, Sinkhorn, mutual matches
     const int ldS = (kmax + 3) & ~3;
     const long sstride = (long)kmax * ldS;
@@ -455,7 +412,7 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     std::vector<SgPair> hp(np);
     int uo = 0, vo = 0;
     for (int c = 0; c < np; ++c) {
-        const SgSeg a = segs[2 * c], b = segs[2 * c + 1];
+        const Seg a = segs[2 * c], b = segs[2 * c + 1];
         hp[c] = SgPair{a.len, b.len, uo, vo, pair_of[c], 0, 0, 0};
         uo += (a.len + 4) & ~3;  // 16-B aligned vectors
         vo += (b.len + 4) & ~3;
@@ -467,10 +424,10 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
         const int nc = std::min(chunk, np - c0);
         int mm = 0, nn = 0;
         for (int c = 0; c < nc; ++c) {
-            const SgSeg a = segs[2 * (c0 + c)], b = segs[2 * (c0 + c) + 1];
+            const Seg a = segs[2 * (c0 + c)], b = segs[2 * (c0 + c) + 1];
             mm = std::max(mm, a.len);
             nn = std::max(nn, b.len);
-            SG_TRY(mlg_similarity_f32_t(MD + (size_t)a.off * 256, a.len, MD + (size_t)b.off * 256, b.len, 256,
+            MLG_TRY(mlg_similarity_f32_t(MD + (size_t)a.off * 256, a.len, MD + (size_t)b.off * 256, b.len, 256,
                                         S + (size_t)c * sstride, ldS, T + (size_t)c * sstride, ldS, s));
         }
         const SgPair* pc = PAIRS + c0;
@@ -487,6 +444,6 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
                            nmatch);
         MLG_LAUNCH_CHECK();
     }
-    // the segment / task / pair tables are pageable host vectors
+    // the segment / task / pair tables are pageable host vectors still being copied
     return hipStreamSynchronize(s) == hipSuccess ? MLG_OK : MLG_EHIP;
 }

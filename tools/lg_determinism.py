@@ -1,6 +1,8 @@
 """Is LightGlue's output independent of what else runs on the GPU?  (GPU box tool.)
 
     python tools/lg_determinism.py [--keyframes 5000] [--chunk 2048] [--modes single,threads2,noise]
+    python tools/lg_determinism.py --modes trace --trace-pairs 64 --save-trace a.npz   (one build)
+    python tools/lg_determinism.py --modes trace --trace-pairs 64 --against a.npz      (the other)
 
 Builds bench.py's workload once (DeviceGate step: ViT, kNN, SuperPoint), takes the
 unordered LightGlue pairs of the step, and matches them chunk by chunk:
@@ -124,15 +126,37 @@ def differing_tags(ref, got, limit=16):
     return tags[:limit]
 
 
-def trace_mode(gate, kp_all, ds_all, counts, ua, ub, chunk, nch, dev, pairs, repeats):
+def coverage(tags):
+    """Which host-scheduling paths the traced call took, read off its tags: layer 0 per
+    distinct frame (99xx), an early-stopped pair (an x41 assignment table below the last
+    layer), a compaction (x31 move table: a stopped pair dropped or a segment pruned)."""
+    t = np.asarray(tags)
+    return {"repeated_frame": bool(((t >= 9900) & (t < 9990)).any()),
+            "stopped_pair": bool(((t % 100 == 41) & (t // 100 < 8)).any()),
+            "pruned_segment": bool(((t % 100 == 31) & (t < 9900)).any())}
+
+
+def trace_mode(gate, kp_all, ds_all, counts, ua, ub, chunk, nch, dev, pairs, repeats, save=None, against=None):
     """Trace the first `pairs` pairs alone, then again while a second thread runs the
-    other chunks on its own stream; name the first stage whose hashes differ."""
+    other chunks on its own stream; name the first stage whose hashes differ.  `save`
+    writes the single-stream trace to an .npz, `against` compares it with one saved by
+    another run (another build through tools/ab_run.py): res["against"]["identical"]."""
     s0 = torch.cuda.current_stream(dev)
     ta, tb = ua[:pairs], ub[:pairs]
     ref = traced(gate, kp_all, ds_all, counts, ta, tb, s0)
     again = traced(gate, kp_all, ds_all, counts, ta, tb, s0)
-    res = {"alone_again": first_divergence(ref, again)}
+    res = {"alone_again": first_divergence(ref, again), "coverage": coverage(ref[0])}
     res["alone_again"]["differing_tags"] = differing_tags(ref, again)
+    if save:
+        np.savez(save, tags=ref[0], counts=ref[1], hashes=ref[2], num_matches=ref[3])
+    if against:
+        with np.load(against) as z:
+            other = (z["tags"], z["counts"], z["hashes"], z["num_matches"])
+        d = first_divergence(other, ref)
+        d["differing_tags"] = differing_tags(other, ref)
+        d["identical"] = (d["first"] is None and d["stages"] == d["stages_got"] and d["diff_count"] == 0
+                          and not d["differing_tags"])
+        res["against"] = d
     for r in range(repeats):
         st = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
         box = {}
@@ -155,6 +179,9 @@ def main():
     ap.add_argument("--max-pairs", type=int, default=0)
     ap.add_argument("--trace-pairs", type=int, default=512)
     ap.add_argument("--trace-repeats", type=int, default=3)
+    ap.add_argument("--save-trace", metavar="FILE", help="trace mode: write the single-stream trace as .npz")
+    ap.add_argument("--against", metavar="FILE",
+                    help="trace mode: compare the single-stream trace with a saved one; exit 1 on any difference")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     seq, labels = bench.sequence(a.keyframes, 600)
@@ -187,9 +214,11 @@ def main():
     if "trace" in modes:
         t = time.time()
         res["trace"] = trace_mode(gate, kp_all, ds_all, counts, ua, ub, a.chunk, nch, dev, a.trace_pairs,
-                                  a.trace_repeats)
+                                  a.trace_repeats, a.save_trace, a.against)
         res["trace"]["seconds"] = round(time.time() - t, 2)
         print(json.dumps({"trace": res["trace"]}), flush=True)
+        if a.against and not res["trace"]["against"]["identical"]:
+            raise SystemExit(1)
         modes = [m for m in modes if m != "trace"]
         torch.cuda.empty_cache()
     ref = single() if modes else None
