@@ -8,14 +8,20 @@
 // (D = W . A^T per 16x16 tile) so that each lane ends up owning 4 consecutive output
 // columns of one token row: epilogue stores are 8-byte bf16 / 16-byte f32 vectors.
 //
-// Tile 128 x 128 x 64, 256 threads (2 x 2 waves of 64 x 64), register-staged double
-// buffer in LDS (64 KiB -> 2 workgroups per CU), st_16x32-style XOR swizzle
-// (chunk ^ (row >> 1) & 7) that makes every ds_read_b128 fragment read conflict-free,
-// XCD-aware bijective block remap so the N-tiles of one M-panel share an L2.
+// Shared pieces, each defined once: a wave owns 64 columns x 16 JM rows as 4 x JM fragments
+// (zero_acc, frag_epilogue); LDS rows are XOR-swizzled (chunk ^ (row >> 1) & (chunks - 1))
+// so every ds_read_b128 fragment read is conflict-free (frag, mma_stage), the LDS-DMA
+// kernels swizzle at the per-lane source (DmaLane, lane_offsets); tiles go to workgroups
+// XCD-locally, so the N-tiles of an M-panel share an L2 (xcd_remap, or TileWalk +
+// persistent_grid for one workgroup per CU walking a range).  Rows >= M are clamped on load
+// and masked on store.  k_gemm_nt: 128 x 128 x 64, register-staged (N % 128 == 0);
+// dma::k_gemm: 128 x 256 x BK, three LDS-DMA stages; dma::k_gemm256: persistent 256 x 256 x
+// 64, two stages; k_gemm256s: its split-bf16 form; k_gemm256q: its 4-deep ring of 32-wide
+// K-tiles; k_conv256: its implicit-GEMM convolution.  What stays written out per kernel,
+// and the measurement behind each case: profiles/r07c_isa_gemm_skeleton.txt.
 //
-// Requirements (checked by the host launcher): K % 64 == 0, N % 128 == 0,
-// 16-byte aligned A / W rows.  M is arbitrary (rows >= M are clamped on load and
-// masked on store).
+// Requirements (checked by the host launchers): K % 64 == 0, N % 128 == 0, 16-byte
+// aligned A / W rows.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -408,6 +414,41 @@ struct EpiPatch {  // patch tokens: X[b, 1 + p, :] = acc + b + pos[1 + p]
     }
 };
 
+// ------------------------------------------------- pieces every kernel shares
+// XCD-aware bijective remap of a one-tile-per-workgroup grid of nwg blocks: hardware
+// blocks b, b+8, ... (one XCD) get consecutive logical ids, so the N-tiles of an M-panel
+// run on one XCD and share its L2.
+__device__ __forceinline__ int xcd_remap(int nwg) {
+    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
+// A wave's accumulators: acc[i][j] is the 16 x 16 fragment of n-tile i (of 4) and m-tile j
+// (of JM); a lane holds 4 consecutive columns of one row.
+template <int JM>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[4][JM]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < JM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Plain epilogue of a wave's 16 JM x 64 block at (mw, nw): one epi() call per fragment,
+// rows >= M masked.  (epi by value: through a reference k_gemm<EpiResidual> scheduled its
+// read-modify-write differently and ran 4-9 % slower.)
+template <int JM, class Epi>
+__device__ __forceinline__ void frag_epilogue(const Epi epi, const f32x4 (&acc)[4][JM], int mw, int nw, int M,
+                                              int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < JM; ++j) {
+            const int n = nw + i * 16 + (lane >> 4) * 4;
+            const int m = mw + j * 16 + (lane & 15);
+            if (m < M) epi(m, n, acc[i][j]);
+        }
+}
+
 // ---------------------------------------------------------------------- kernel
 template <class Epi>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
@@ -417,8 +458,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const bf16_t* __restrict__ A
     const int nN = N / BN, nM = (M + BM - 1) / BM, nwg = nN * nM;
     // XCD-aware bijective remap: hardware blocks b, b+8, ... (one XCD) get consecutive
     // logical ids, so the N-tiles of an M-panel run on one XCD and share its L2.
-    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    const int wgid = xcd_remap(nwg);
     const int mt = wgid / nN, nt = wgid - mt * nN;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -426,7 +466,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const bf16_t* __restrict__ A
     const int srow = tid >> 3, sch = tid & 7;
     const bf16_t* pa = A + (size_t)min(m0 + srow, M - 1) * lda + sch * 8;
     const bf16_t* pw = W + (size_t)(n0 + srow) * ldw + sch * 8;
-    const size_t a32 = (size_t)lda * 32, w32 = (size_t)ldw * 32;
+    const size_t w32 = (size_t)ldw * 32;
     // rows >= M are clamped to M - 1 (their products are never stored)
     const int ar1 = min(m0 + srow + 32, M - 1) - min(m0 + srow, M - 1);
     const int ar2 = min(m0 + srow + 64, M - 1) - min(m0 + srow, M - 1);
@@ -457,7 +497,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const bf16_t* __restrict__ A
         *reinterpret_cast<uint4*>(b_ + TILE_BYTES + so2) = rw2;                     \
         *reinterpret_cast<uint4*>(b_ + TILE_BYTES + so3) = rw3;                     \
     }
-    (void)a32;
 
     const int wn = wave >> 1, wm = wave & 1;
     f32x4 acc[4][4];
@@ -499,31 +538,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const bf16_t* __restrict__ A
         cur ^= 1;
     }
 
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-            const int m = m0 + wm * 64 + j * 16 + (lane & 15);
-            if (m < M) epi(m, n, acc[i][j]);
-        }
+    frag_epilogue(epi, acc, m0 + wm * 64, n0 + wn * 64, M, lane);
 #undef GEMM_GLOAD
 #undef GEMM_LSTORE
 }
 
 // ------------------------------------------------------- LDS-DMA kernels
-// 128 x 256 x BK tile, 512 threads = 8 waves (2 along M x 4 along N, 64 x 64 each),
-// STAGES LDS stages filled by LDS-DMA (global_load_lds_dwordx4, 1 KiB per
-// wave-instruction), K-tile t+2 prefetched while t is computed.  The XOR swizzle
-// (chunk ^ (row >> 1) & (chunks/row - 1), conflict-free for every ds_read_b128
-// fragment read at BK = 32 and 64 -- checked by script) moves to the per-lane SOURCE
-// address since the DMA writes lane-linear; fragment reads apply the same involution.
-// Waits are counted (s_waitcnt vmcnt(#DMA per tile): the newest tile's DMAs stay in
-// flight across the raw s_barrier); each stage is its own __shared__ object and the
-// loop is unrolled by 3 so stage addresses are constants.
-//   BK = 64: 3 x 48 KiB stages, one workgroup per CU.
-//   BK = 32: 3 x 24 KiB stages, two workgroups per CU (16 waves): one workgroup's
-//            epilogue / prologue overlaps the other's MFMA main loop.
 namespace dma {
 constexpr int BM = 128, BN = 256;
 typedef __attribute__((address_space(3))) char lds_char;
@@ -549,7 +569,97 @@ template <int BK>
 __device__ __forceinline__ int soff(int row, int chunk) {
     return row * (BK * 2) + ((chunk ^ ((row >> 1) & (BK / 8 - 1))) << 4);
 }
+template <int BK>
+__device__ __forceinline__ bf16x8 frag(const char* tile, int row, int chunk) {
+    return *reinterpret_cast<const bf16x8*>(tile + soff<BK>(row, chunk));
+}
 
+// A lane's place in the DMA wave-instructions that fill a BK-wide operand tile: 64 lanes x
+// 16 B land lane-linear, i.e. RPI rows of CH chunks, so in row group g (RPI rows) of the
+// tile the lane fills tile row `row(g)`, and it reads that row's chunk `chunk(row)` (an
+// element offset): soff's swizzle applied at the source.
+template <int BK>
+struct DmaLane {
+    static constexpr int CH = BK / 8, RPI = 64 / CH;
+    int lr, lp;
+    __device__ __forceinline__ explicit DmaLane(int lane) : lr(lane >> __builtin_ctz(CH)), lp(lane & (CH - 1)) {}
+    __device__ __forceinline__ int row(int g) const { return g * RPI + lr; }
+    __device__ __forceinline__ int chunk(int row) const { return (lp ^ ((row >> 1) & (CH - 1))) * 8; }
+    // A row read for tile row `row` of the M-tile at m0: rows >= M (the ragged last tile)
+    // re-read row M - 1; their products are never stored.
+    __device__ __forceinline__ static int src_row(int m0, int row, int M) { return min(m0 + row, M - 1); }
+};
+
+// dma16s byte offsets of a wave's N row groups (N * wave ..) from the wave-uniform base
+// of a tile with rows `ld` elements apart: W rows, and A rows of the M-tile at m0.
+template <int BK, int N>
+__device__ __forceinline__ void lane_offsets(const DmaLane<BK>& dl, int wave, int ld, unsigned (&o)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int row = dl.row(N * wave + i);
+        o[i] = (unsigned)(row * ld + dl.chunk(row)) * 2u;
+    }
+}
+template <int BK, int N>
+__device__ __forceinline__ void lane_offsets(const DmaLane<BK>& dl, int wave, int ld, int m0, int M,
+                                             unsigned (&o)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int row = dl.row(N * wave + i);
+        o[i] = (unsigned)((dl.src_row(m0, row, M) - m0) * ld + dl.chunk(row)) * 2u;
+    }
+}
+
+// One LDS stage's fragment reads and MFMAs for a wave block of 16 JM rows x 64 columns:
+// `a` / `w` are the stage's A / W tiles, ar / wr the block's first row in each.  W
+// fragments are read first and the MFMAs run m-tile outer.
+template <int BK, int JM>
+__device__ __forceinline__ void mma_stage(f32x4 (&acc)[4][JM], const char* a, const char* w, int ar, int wr,
+                                          int lane) {
+#pragma unroll
+    for (int s = 0; s < BK / 32; ++s) {
+        bf16x8 af[JM], wf[4];
+        const int ch = s * 4 + (lane >> 4), r = lane & 15;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wf[i] = frag<BK>(w, wr + i * 16 + r, ch);
+#pragma unroll
+        for (int j = 0; j < JM; ++j) af[j] = frag<BK>(a, ar + j * 16 + r, ch);
+#pragma unroll
+        for (int j = 0; j < JM; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// The walk of a persistent kernel (grid = persistent_grid(ntiles), a multiple of 8) over
+// the output tiles: XCD x owns the contiguous range [x tx, (x + 1) tx) (N fastest, so the
+// workgroups of an XCD share A panels in its L2), which its `step` workgroups stride.
+struct TileWalk {
+    int tile, end, step;
+    __device__ __forceinline__ explicit TileWalk(int ntiles) {
+        const int xcd = blockIdx.x & 7, tx = (ntiles + 7) >> 3;
+        step = gridDim.x >> 3;
+        end = min((xcd + 1) * tx, ntiles);
+        tile = xcd * tx + (blockIdx.x >> 3);
+    }
+    __device__ __forceinline__ bool done() const { return tile >= end; }
+    // the tile this workgroup takes after t, or t itself when none follows
+    __device__ __forceinline__ int next(int t) const { return t + step < end ? t + step : t; }
+};
+
+// 128 x 256 x BK tile, 512 threads = 8 waves (2 along M x 4 along N, 64 x 64 each),
+// STAGES LDS stages filled by LDS-DMA (global_load_lds_dwordx4, 1 KiB per
+// wave-instruction), K-tile t+2 prefetched while t is computed.  The XOR swizzle
+// (chunk ^ (row >> 1) & (chunks/row - 1), conflict-free for every ds_read_b128
+// fragment read at BK = 32 and 64 -- checked by script) moves to the per-lane SOURCE
+// address since the DMA writes lane-linear; fragment reads apply the same involution.
+// Waits are counted (s_waitcnt vmcnt(#DMA per tile): the newest tile's DMAs stay in
+// flight across the raw s_barrier); each stage is its own __shared__ object and the
+// loop is unrolled by 3 so stage addresses are constants.
+//   BK = 64: 3 x 48 KiB stages, one workgroup per CU.
+//   BK = 32: 3 x 24 KiB stages, two workgroups per CU (16 waves): one workgroup's
+//            epilogue / prologue overlaps the other's MFMA main loop.
 template <class Epi, int BK>
 __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void k_gemm(const bf16_t* __restrict__ A,
                                                                  const bf16_t* __restrict__ W, int M, int N, int K,
@@ -564,8 +674,7 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void k_gemm(const bf16_t* __
     __shared__ __attribute__((aligned(16))) char st2[STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nN = N / BN, nM = (M + BM - 1) / BM, nwg = nN * nM;
-    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    const int wgid = xcd_remap(nwg);
     const int mt = wgid / nN, nt = wgid - mt * nN;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -594,10 +703,7 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void k_gemm(const bf16_t* __
 
     const int wm = wave & 1, wn = wave >> 1;
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
 #define DMA_COMPUTE(ST)                                                                                    \
     _Pragma("unroll") for (int s = 0; s < BK / 32; ++s) {                                                  \
@@ -640,14 +746,7 @@ __global__ __launch_bounds__(512, BK == 32 ? 4 : 2) void k_gemm(const bf16_t* __
 #undef DMA_COMPUTE
 #undef DMA_ISSUE
 
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-            const int m = m0 + wm * 64 + j * 16 + (lane & 15);
-            if (m < M) epi(m, n, acc[i][j]);
-        }
+    frag_epilogue(epi, acc, m0 + wm * 64, n0 + wn * 64, M, lane);
 }
 // 256 x 256 x 64 tile, 8 waves (2 along M x 4 along N, 128 x 64 each: 32 accumulators),
 // two 64 KiB LDS stages (K-tile t+1 lands while t is computed), one workgroup per CU,
@@ -710,11 +809,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const bf16_t* __restrict__ A
     __shared__ __attribute__((aligned(16))) char st1[STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nN = N / TN, nM = (M + TM - 1) / TM, ntiles = nN * nM;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;  // grid is a multiple of 8
-    const int tx = (ntiles + 7) >> 3;
-    const int tile_end = min((xcd + 1) * tx, ntiles);
-    int tile = xcd * tx + (blockIdx.x >> 3);
-    if (tile >= tile_end) return;
+    TileWalk walk(ntiles);
+    if (walk.done()) return;
 
     const int lr = lane >> 3, lp = lane & 7;
     const int wm = wave & 1, wn = wave >> 1;
@@ -741,9 +837,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const bf16_t* __restrict__ A
     auto a_base = [&](int t) { return A + (size_t)((t / nN) * TM) * lda; };
     auto b_base = [&](int t) { return W + (size_t)((t % nN) * TN) * ldw; };
     unsigned oa[NA];
-    const bf16_t* sa = a_base(tile);
-    const bf16_t* sb = b_base(tile);
-    a_offsets(tile, oa);
+    const bf16_t* sa = a_base(walk.tile);
+    const bf16_t* sb = b_base(walk.tile);
+    a_offsets(walk.tile, oa);
 #define D256_DMA(ST, OA, SA, SB, t)                                                                        \
     {                                                                                                      \
         const unsigned b_ = lds_addr(ST);                                                                  \
@@ -771,18 +867,15 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const bf16_t* __restrict__ A
     D256_DMA(st0, oa, sa, sb, 0);
     __builtin_amdgcn_s_waitcnt(0xF70);
     __builtin_amdgcn_s_barrier();
-    for (; tile < tile_end; tile += per_xcd) {
-        const int next = tile + per_xcd < tile_end ? tile + per_xcd : tile;
+    for (; walk.tile < walk.end; walk.tile += walk.step) {
+        const int tile = walk.tile, next = walk.next(tile);
         unsigned na[NA];
         a_offsets(next, na);
         const bf16_t* nsa = a_base(next);
         const bf16_t* nsb = b_base(next);
         const int kn = next != tile ? 0 : nk - 1;  // K-tile of the last DMA (no next tile: harmless re-read)
         f32x4 acc[4][8];  // [n-tile][m-tile]
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         for (int t = 0; t < nk; t += 2) {
             D256_DMA(st1, oa, sa, sb, t + 1);
             D256_COMPUTE(st0);
@@ -803,14 +896,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const bf16_t* __restrict__ A
                                                      M, lane);
             __syncthreads();  // every wave's image read: the next tile DMAs into st1
         } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-                    const int m = m0 + wm * 128 + j * 16 + (lane & 15);
-                    if (m < M) epi(m, n, acc[i][j]);
-                }
+            frag_epilogue(epi, acc, m0 + wm * 128, n0 + wn * 64, M, lane);
         }
 #pragma unroll
         for (int i = 0; i < NA; ++i) oa[i] = na[i];
@@ -854,37 +940,28 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
     // nb > 1 (staged-f32 epilogues only): nb independent products of one shape in one
     // persistent launch, problem z at A + z sA, W + z sW, its output rows z M + m (the
     // LoFTR similarity of a pair group: one tile queue instead of a 2-3-tile tail per pair)
-    const int nN = N / TN, nM = (M + TM - 1) / TM, nMN = nN * nM, ntiles = nb * nMN;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int tx = (ntiles + 7) >> 3;
-    const int tile_end = min((xcd + 1) * tx, ntiles);
-    int tile = xcd * tx + (blockIdx.x >> 3);
-    if (tile >= tile_end) return;
+    const int nN = N / TN, nM = (M + TM - 1) / TM, nMN = nN * nM;
+    TileWalk walk(nb * nMN);
+    if (walk.done()) return;
 
-    const int lr = lane >> 2, lp = lane & 3;  // 16 rows x 4 chunks of 16 B per DMA wave-instruction
+    const DmaLane<BK> dl(lane);  // 16 rows x 4 chunks of 16 B per DMA wave-instruction
     const int wm = wave & 1, wn = wave >> 1;
     const int nk = K0 / BK;  // even (checked by the launcher)
     const int drow = 2 * wave * 1024;  // this wave's 32 rows of every plane
+    // (this kernel sits at 256 VGPRs: the B offsets through lane_offsets spill 4 B more)
     unsigned ob[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int row = (2 * wave + i) * 16 + lr;
-        ob[i] = (unsigned)(row * ldw + ((lp ^ ((row >> 1) & 3)) * 8)) * 2u;
+        const int row = dl.row(2 * wave + i);
+        ob[i] = (unsigned)(row * ldw + dl.chunk(row)) * 2u;
     }
-    auto a_offsets = [&](int t, unsigned* oa) {
-        const int m0 = ((t % nMN) / nN) * TM;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (2 * wave + i) * 16 + lr;
-            oa[i] = (unsigned)((min(m0 + row, M - 1) - m0) * lda + ((lp ^ ((row >> 1) & 3)) * 8)) * 2u;
-        }
-    };
+    auto a_offsets = [&](int t, unsigned (&o)[2]) { lane_offsets(dl, wave, lda, ((t % nMN) / nN) * TM, M, o); };
     auto a_base = [&](int t) { return A + (t / nMN) * sA + (size_t)(((t % nMN) / nN) * TM) * lda; };
     auto b_base = [&](int t) { return W + (t / nMN) * sW + (size_t)((t % nN) * TN) * ldw; };
     unsigned oa[2];
-    const bf16_t* sa = a_base(tile);
-    const bf16_t* sb = b_base(tile);
-    a_offsets(tile, oa);
+    const bf16_t* sa = a_base(walk.tile);
+    const bf16_t* sb = b_base(walk.tile);
+    a_offsets(walk.tile, oa);
 #define S256_DMA(ST, OA, SA, SB, t)                                                                        \
     {                                                                                                      \
         const unsigned b_ = lds_addr(ST) + drow;                                                           \
@@ -897,29 +974,27 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
             dma16s(ob[i], wh_ + K0, b_ + 3 * PLANE + i * 1024);                                            \
         }                                                                                                  \
     }
+    // the three products of a K-step: hi * hi and lo * hi on the A_hi fragments, then the
+    // A fragments reloaded as A_lo for hi * lo
 #define S256_COMPUTE(ST)                                                                                   \
     {                                                                                                      \
         bf16x8 af[8], wh[4], wl[4];                                                                        \
         const int ch = lane >> 4;                                                                          \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
             const int row = wn * 64 + i * 16 + (lane & 15);                                                \
-            wh[i] = *reinterpret_cast<const bf16x8*>((ST) + 2 * PLANE + soff<32>(row, ch));                \
-            wl[i] = *reinterpret_cast<const bf16x8*>((ST) + 3 * PLANE + soff<32>(row, ch));                \
+            wh[i] = frag<BK>((ST) + 2 * PLANE, row, ch);                                                   \
+            wl[i] = frag<BK>((ST) + 3 * PLANE, row, ch);                                                   \
         }                                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                    \
-            const int row = wm * 128 + j * 16 + (lane & 15);                                               \
-            af[j] = *reinterpret_cast<const bf16x8*>((ST) + soff<32>(row, ch));                            \
-        }                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                      \
+            af[j] = frag<BK>((ST), wm * 128 + j * 16 + (lane & 15), ch);                                   \
         __builtin_amdgcn_s_setprio(1);                                                                     \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i) {      \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], af[j], acc[i][j], 0, 0, 0);         \
         }                                                                                                  \
         __builtin_amdgcn_s_setprio(0);                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                    \
-            const int row = wm * 128 + j * 16 + (lane & 15);                                               \
-            af[j] = *reinterpret_cast<const bf16x8*>((ST) + PLANE + soff<32>(row, ch));                    \
-        }                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                      \
+            af[j] = frag<BK>((ST) + PLANE, wm * 128 + j * 16 + (lane & 15), ch);                           \
         __builtin_amdgcn_s_setprio(1);                                                                     \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i)        \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
@@ -929,18 +1004,15 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
     S256_DMA(st0, oa, sa, sb, 0);
     __builtin_amdgcn_s_waitcnt(0xF70);
     __builtin_amdgcn_s_barrier();
-    for (; tile < tile_end; tile += per_xcd) {
-        const int next = tile + per_xcd < tile_end ? tile + per_xcd : tile;
+    for (; walk.tile < walk.end; walk.tile += walk.step) {
+        const int tile = walk.tile, next = walk.next(tile);
         unsigned na[2];
         a_offsets(next, na);
         const bf16_t* nsa = a_base(next);
         const bf16_t* nsb = b_base(next);
         const int kn = next != tile ? 0 : nk - 1;  // no next tile: harmless re-read
         f32x4 acc[4][8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         for (int t = 0; t < nk; t += 2) {
             S256_DMA(st1, oa, sa, sb, t + 1);
             S256_COMPUTE(st0);
@@ -1110,56 +1182,37 @@ __global__ __launch_bounds__(512, 2) void k_gemm256q(const bf16_t* __restrict__ 
     constexpr int WAIT2 = 0xF70 | (2 * (NA + NB));                     // two newer K-tiles may fly
     __shared__ __attribute__((aligned(16))) char ringbuf[4 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nN = N / TN, nM = (M + TM - 1) / TM, ntiles = nN * nM;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int tx = (ntiles + 7) >> 3;
-    const int tile_end = min((xcd + 1) * tx, ntiles);
-    int tile = xcd * tx + (blockIdx.x >> 3);
-    if (tile >= tile_end) return;
+    const int nN = N / TN, nM = (M + TM - 1) / TM;
+    TileWalk walk(nN * nM);
+    if (walk.done()) return;
 
-    const int lr = lane >> 2, lp = lane & 3;  // 16 rows x 4 chunks of 16 B per DMA wave-instruction
+    const DmaLane<BK> dl(lane);  // 16 rows x 4 chunks of 16 B per DMA wave-instruction
     const int wm = wave & 1, wn = wave >> 1;
     const int da = NA * wave * 1024, db = A_BYTES + NB * wave * 1024;
     const int nk = K / BK;  // >= 3 (checked by the launcher)
-    unsigned ob[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const int row = (NB * wave + i) * 16 + lr;
-        ob[i] = (unsigned)(row * ldw + ((lp ^ ((row >> 1) & 3)) * 8)) * 2u;
-    }
-    auto a_offsets = [&](int t, unsigned* oa) {
-        const int m0 = (t / nN) * TM;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int row = (NA * wave + i) * 16 + lr;
-            oa[i] = (unsigned)((min(m0 + row, M - 1) - m0) * lda + ((lp ^ ((row >> 1) & 3)) * 8)) * 2u;
-        }
-    };
     auto a_base = [&](int t) { return A + (size_t)((t / nN) * TM) * lda; };
     auto b_base = [&](int t) { return W + (size_t)((t % nN) * TN) * ldw; };
-#define Q256_DMA(ST, OA, SA, SB, k0)                                                                       \
-    {                                                                                                      \
-        const unsigned b_ = lds_addr(ST);                                                                  \
-        const bf16_t* sa_ = (SA) + (k0);                                                                   \
-        const bf16_t* sb_ = (SB) + (k0);                                                                   \
-        _Pragma("unroll") for (int i = 0; i < NA; ++i) dma16s((OA)[i], sa_, b_ + da + i * 1024);           \
-        _Pragma("unroll") for (int i = 0; i < NB; ++i) dma16s(ob[i], sb_, b_ + db + i * 1024);             \
-    }
     // the K-tile stream: (tile, k) pairs in order, the fetch position runs 3 ahead
-    int ftile = tile, fk = 0;
-    unsigned foa[NA];
-    a_offsets(ftile, foa);
-    const bf16_t* fsa = a_base(ftile);
-    const bf16_t* fsb = b_base(ftile);
-    int fslot = 0;
-    auto fetch_next = [&]() {
-        Q256_DMA(ringbuf + fslot * STAGE, foa, fsa, fsb, fk * BK);
+    int ftile = walk.tile, fk = 0, fslot = 0;
+    unsigned ob[NB], foa[NA];
+    lane_offsets(dl, wave, ldw, ob);
+    lane_offsets(dl, wave, lda, (ftile / nN) * TM, M, foa);
+    const bf16_t *fsa = a_base(ftile), *fsb = b_base(ftile);
+    auto fetch_next = [&]() __attribute__((always_inline)) {
+        const unsigned b_ = lds_addr(ringbuf + fslot * STAGE);
+        const bf16_t* sa_ = fsa + fk * BK;
+        const bf16_t* sb_ = fsb + fk * BK;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) dma16s(foa[i], sa_, b_ + da + i * 1024);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) dma16s(ob[i], sb_, b_ + db + i * 1024);
         fslot = (fslot + 1) & 3;
         if (++fk == nk) {  // continue with the next output tile of this workgroup (or re-read)
-            fk = 0;
-            if (ftile + per_xcd < tile_end) {
-                ftile += per_xcd;
-                a_offsets(ftile, foa);
+            const int nt = walk.next(ftile);
+            if (nt != ftile) {
+                fk = 0;
+                ftile = nt;
+                lane_offsets(dl, wave, lda, (ftile / nN) * TM, M, foa);
                 fsa = a_base(ftile);
                 fsb = b_base(ftile);
             } else {
@@ -1173,48 +1226,21 @@ __global__ __launch_bounds__(512, 2) void k_gemm256q(const bf16_t* __restrict__ 
     __builtin_amdgcn_s_waitcnt(WAIT2);
     __builtin_amdgcn_s_barrier();
     int cslot = 0;
-    for (; tile < tile_end; tile += per_xcd) {
+    for (; walk.tile < walk.end; walk.tile += walk.step) {
         f32x4 acc[4][8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         for (int t = 0; t < nk; ++t) {
             fetch_next();  // K-tile t + 3 of the stream, into the slot computed last step
-            const char* ST = ringbuf + cslot * STAGE;
-            bf16x8 af[8], wf[4];
-            const int ch = lane >> 4;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = wn * 64 + i * 16 + (lane & 15);
-                wf[i] = *reinterpret_cast<const bf16x8*>(ST + A_BYTES + soff<32>(row, ch));
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int row = wm * 128 + j * 16 + (lane & 15);
-                af[j] = *reinterpret_cast<const bf16x8*>(ST + soff<32>(row, ch));
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
+            const char* st = ringbuf + cslot * STAGE;
+            mma_stage<BK, 8>(acc, st, st + A_BYTES, wm * 128, wn * 64, lane);
             cslot = (cslot + 1) & 3;
             __builtin_amdgcn_s_waitcnt(WAIT2);  // K-tile t + 1 has landed (t + 2, t + 3 may fly)
             __builtin_amdgcn_s_barrier();
         }
-        const int mt = tile / nN, m0 = mt * TM, n0 = (tile - mt * nN) * TN;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-                const int m = m0 + wm * 128 + j * 16 + (lane & 15);
-                if (m < M) epi(m, n, acc[i][j]);
-            }
+        const int mt = walk.tile / nN, m0 = mt * TM, n0 = (walk.tile - mt * nN) * TN;
+        frag_epilogue(epi, acc, m0 + wm * 128, n0 + wn * 64, M, lane);
     }
     __builtin_amdgcn_s_waitcnt(0xF70);
-#undef Q256_DMA
 }
 // Implicit-GEMM convolution on the persistent 256 x TN x 64 tile of k_gemm256 (LoFTR's
 // ResNetFPN, loftr.hip): A[m, k] is never materialised.  Row m = output pixel (b, oy, ox)
@@ -1240,24 +1266,17 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
     __shared__ __attribute__((aligned(16))) char st0[STAGE];
     __shared__ __attribute__((aligned(16))) char st1[STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nN = N / TN, nM = (M + TM - 1) / TM, ntiles = nN * nM;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int tx = (ntiles + 7) >> 3;
-    const int tile_end = min((xcd + 1) * tx, ntiles);
-    int tile = xcd * tx + (blockIdx.x >> 3);
-    if (tile >= tile_end) return;
+    const int nN = N / TN, nM = (M + TM - 1) / TM;
+    TileWalk walk(nN * nM);
+    if (walk.done()) return;
 
-    const int lr = lane >> 3, lp = lane & 7;
+    const DmaLane<BK> dl(lane);
     const int wm = wave % WM, wn = wave / WM;
     const int da = NA * wave * 1024, db = A_BYTES + NB * wave * 1024;
     const int nk = K / BK;  // even (checked by the launcher)
 
     unsigned ob[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const int row = (NB * wave + i) * 8 + lr;
-        ob[i] = (unsigned)(row * K + ((lp ^ ((row >> 1) & 7)) * 8)) * 2u;
-    }
+    lane_offsets(dl, wave, K, ob);
     // per row: (b, oy, ox) packed 10 / 11 / 11 bits (H, W <= 2048 and B <= 1024, checked
     // by the launcher) -- one VGPR per row instead of three
     unsigned pk[NA];
@@ -1265,8 +1284,7 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
         const int m0 = (t / nN) * TM;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            const int row = (NA * wave + i) * 8 + lr;
-            const int m = min(m0 + row, M - 1);
+            const int m = dl.src_row(m0, dl.row(NA * wave + i), M);
             const int ox = m % g.Wo, r = m / g.Wo, oy = r % g.Ho, b = r / g.Ho;
             pk[i] = ((unsigned)b << 22) | ((unsigned)oy << 11) | (unsigned)ox;
         }
@@ -1276,61 +1294,46 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
         const int ty = tap / g.kw, tx_ = tap - ty * g.kw;
         const int b = (int)(pk[i] >> 22), oy = (int)((pk[i] >> 11) & 2047u), ox = (int)(pk[i] & 2047u);
         const int iy = oy * g.s - g.pad + ty, ix = ox * g.s - g.pad + tx_;
-        const int row = (NA * wave + i) * 8 + lr;
-        const int ch = (lp ^ ((row >> 1) & 7)) * 8;
         if ((unsigned)iy >= (unsigned)g.H || (unsigned)ix >= (unsigned)g.W) return g.zero;
-        return g.in + ((size_t)((b * g.H + iy) * g.W + ix)) * g.C + c0 + ch;
+        return g.in + ((size_t)((b * g.H + iy) * g.W + ix)) * g.C + c0 + dl.chunk(dl.row(NA * wave + i));
     };
     auto b_base = [&](int t) { return W + (size_t)((t % nN) * TN) * K; };
-    const bf16_t* sb = b_base(tile);
-    rows_of(tile);
-#define C256_DMA(ST, SB, k0)                                                                               \
+    const bf16_t* sb = b_base(walk.tile);
+    rows_of(walk.tile);
+    // K-tile kt (a tile index, as in the GEMMs) of the rows in pk and the W tile at SB.  A
+    // macro: as a lambda, hipcc either computed the dma16s base in VGPRs (which does not
+    // assemble) or, kept scalar, spilled 32 B more at TN = 256.
+#define C256_DMA(ST, SB, kt)                                                                               \
     {                                                                                                      \
         const unsigned b_ = lds_addr(ST);                                                                  \
-        const bf16_t* sb_ = (SB) + (k0);                                                                   \
-        _Pragma("unroll") for (int i = 0; i < NA; ++i) dma16(a_src(i, k0), b_ + da + i * 1024);            \
+        const bf16_t* sb_ = (SB) + (kt) * BK;                                                              \
+        _Pragma("unroll") for (int i = 0; i < NA; ++i) dma16(a_src(i, (kt) * BK), b_ + da + i * 1024);     \
         _Pragma("unroll") for (int i = 0; i < NB; ++i) dma16s(ob[i], sb_, b_ + db + i * 1024);             \
-    }
-#define C256_COMPUTE(ST)                                                                                   \
-    _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                        \
-        bf16x8 af[JM], wf[4];                                                                              \
-        const int ch = s * 4 + (lane >> 4);                                                                \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
-            const int row = wn * 64 + i * 16 + (lane & 15);                                                \
-            wf[i] = *reinterpret_cast<const bf16x8*>((ST) + A_BYTES + soff<64>(row, ch));                  \
-        }                                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < JM; ++j) {                                                   \
-            const int row = wm * RM + j * 16 + (lane & 15);                                                \
-            af[j] = *reinterpret_cast<const bf16x8*>((ST) + soff<64>(row, ch));                            \
-        }                                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < JM; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i)       \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);         \
     }
 
     C256_DMA(st0, sb, 0);
     __builtin_amdgcn_s_waitcnt(0xF70);
     __builtin_amdgcn_s_barrier();
-    for (; tile < tile_end; tile += per_xcd) {
-        const int next = tile + per_xcd < tile_end ? tile + per_xcd : tile;
+    for (; walk.tile < walk.end; walk.tile += walk.step) {
+        const int tile = walk.tile, next = walk.next(tile);
         const bf16_t* nsb = b_base(next);
-        const int kn = next != tile ? 0 : nk - 1;  // K-tile of the last DMA (no next tile: harmless re-read)
+        // K-tile of the last DMA.  No next tile: a harmless re-read of this tile's last K-tile
+        // (this used to pass the tile index nk - 1 as an element offset)
+        const int kn = next != tile ? 0 : nk - 1;
         f32x4 acc[4][JM];  // [n-tile][m-tile]
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < JM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         for (int t = 0; t < nk; t += 2) {
-            C256_DMA(st1, sb, (t + 1) * BK);
-            C256_COMPUTE(st0);
+            C256_DMA(st1, sb, t + 1);
+            mma_stage<BK, JM>(acc, st0, st0 + A_BYTES, wm * RM, wn * 64, lane);
             __builtin_amdgcn_s_waitcnt(0xF70);
             __builtin_amdgcn_s_barrier();
             if (t + 2 < nk) {
-                C256_DMA(st0, sb, (t + 2) * BK);
+                C256_DMA(st0, sb, t + 2);
             } else {
                 rows_of(next);  // this tile's A rows are no longer needed
-                C256_DMA(st0, nsb, kn);     // K-tile 0 of the next output tile
+                C256_DMA(st0, nsb, kn);  // K-tile 0 of the next output tile
             }
-            C256_COMPUTE(st1);
+            mma_stage<BK, JM>(acc, st1, st1 + A_BYTES, wm * RM, wn * 64, lane);
             __builtin_amdgcn_s_waitcnt(0xF70);
             __builtin_amdgcn_s_barrier();
         }
@@ -1343,7 +1346,6 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
         sb = nsb;
     }
     __builtin_amdgcn_s_waitcnt(0xF70);
-#undef C256_COMPUTE
 #undef C256_DMA
 }
 }  // namespace dma
@@ -1356,7 +1358,6 @@ __global__ __launch_bounds__(512, 2) void k_conv256(ConvGeom g, const bf16_t* __
 #define MLG_GEMM_VARIANT 4
 #endif
 int g_variant = MLG_GEMM_VARIANT;
-int g_num_cus = 256;  // multiple of 8 (refreshed from the device on first use)
 
 int num_cus() {
     static int cached = [] {
@@ -1369,23 +1370,24 @@ int num_cus() {
     return cached;
 }
 
+// Grid of a persistent kernel (dma::TileWalk): one workgroup per CU, fewer when the tiles
+// are fewer, a multiple of 8 so that every XCD gets the same number.
+unsigned persistent_grid(long ntiles) { return (unsigned)std::min<long>(num_cus(), (ntiles + 7) / 8 * 8); }
+
 template <class Epi>
 int launch(const bf16_t* A, const bf16_t* W, int M, int N, int K, int lda, int ldw, Epi epi, hipStream_t s,
            int variant = -1) {
     if (variant < 0) variant = g_variant;
-    g_num_cus = num_cus();
     if (M <= 0 || N <= 0 || K <= 0 || (K % BK) || (lda % 8) || (ldw % 8) || lda < K || ldw < K)
         return MLG_EINVAL;
     if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return MLG_EINVAL;
     const long nwg_dma = (long)(N / dma::BN) * ((M + dma::BM - 1) / dma::BM);
     if (variant == 5 && N % 256 == 0 && K % 32 == 0 && K / 32 >= 3) {
-        const long ntiles = (long)(N / 256) * ((M + 255) / 256);
-        const long grid = std::min<long>(g_num_cus, (ntiles + 7) / 8 * 8);  // persistent: <= 1 per CU
-        hipLaunchKernelGGL(dma::k_gemm256q<Epi>, dim3((unsigned)grid), dim3(512), 0, s, A, W, M, N, K, lda, ldw, epi);
+        const unsigned grid = persistent_grid((long)(N / 256) * ((M + 255) / 256));
+        hipLaunchKernelGGL(dma::k_gemm256q<Epi>, dim3(grid), dim3(512), 0, s, A, W, M, N, K, lda, ldw, epi);
     } else if ((variant == 4 || variant == 5) && N % 256 == 0 && (K / 64) % 2 == 0) {
-        const long ntiles = (long)(N / 256) * ((M + 255) / 256);
-        const long grid = std::min<long>(g_num_cus, (ntiles + 7) / 8 * 8);  // persistent: <= 1 per CU
-        hipLaunchKernelGGL(dma::k_gemm256<Epi>, dim3((unsigned)grid), dim3(512), 0, s, A, W, M, N, K, lda, ldw, epi);
+        const unsigned grid = persistent_grid((long)(N / 256) * ((M + 255) / 256));
+        hipLaunchKernelGGL(dma::k_gemm256<Epi>, dim3(grid), dim3(512), 0, s, A, W, M, N, K, lda, ldw, epi);
     } else if (variant == 3 && N % dma::BN == 0 && (K / 32) % 3 == 0) {
         hipLaunchKernelGGL((dma::k_gemm<Epi, 32>), dim3((unsigned)nwg_dma), dim3(512), 0, s, A, W, M, N, K, lda, ldw,
                            epi);
@@ -1407,7 +1409,6 @@ int launch(const bf16_t* A, const bf16_t* W, int M, int N, int K, int lda, int l
 template <class Epi>
 int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda, int ldw, Epi epi, hipStream_t s,
                  int nb = 1, long sA = 0, long sW = 0) {
-    g_num_cus = num_cus();
     if (M <= 0 || K0 <= 0 || K0 % 64 || lda < 2 * K0 || ldw < 2 * K0 || (lda % 8) || (ldw % 8)) return MLG_EINVAL;
     if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return MLG_EINVAL;
     // batched products: staged-f32 epilogues only (their row index is the only per-problem
@@ -1416,8 +1417,7 @@ int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda
     if (N % 256) return MLG_EINVAL;
     const long ntiles = (long)nb * (N / 256) * ((M + 255) / 256);
     if (ntiles > INT32_MAX) return MLG_EINVAL;
-    const long grid = std::min<long>(g_num_cus, (ntiles + 7) / 8 * 8);
-    hipLaunchKernelGGL(dma::k_gemm256s<Epi>, dim3((unsigned)grid), dim3(512), 0, s, A, W, M, N, K0, lda, ldw, epi, nb,
+    hipLaunchKernelGGL(dma::k_gemm256s<Epi>, dim3(persistent_grid(ntiles)), dim3(512), 0, s, A, W, M, N, K0, lda, ldw, epi, nb,
                        sA, sW);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
@@ -1525,15 +1525,12 @@ int mlg_conv_implicit(const bf16_t* in, const bf16_t* zero, int B, int H, int W,
     const int M = B * Ho * Wo;
     const dma::ConvGeom g{in, zero, H, W, C, k, s, k / 2, Ho, Wo};
     const EpiConv epi{bias, R, ldr, X, ldx, Cout, ldc, act, act_cols};
-    const int cus = num_cus();
     if (N % 256 == 0) {
-        const long ntiles = (long)(N / 256) * ((M + 255) / 256);
-        const long grid = std::min<long>(cus, (ntiles + 7) / 8 * 8);
-        hipLaunchKernelGGL((dma::k_conv256<EpiConv, 256>), dim3((unsigned)grid), dim3(512), 0, st, g, Wt, M, N, K, epi);
+        const unsigned grid = persistent_grid((long)(N / 256) * ((M + 255) / 256));
+        hipLaunchKernelGGL((dma::k_conv256<EpiConv, 256>), dim3(grid), dim3(512), 0, st, g, Wt, M, N, K, epi);
     } else {
-        const long ntiles = (long)(N / 128) * ((M + 255) / 256);
-        const long grid = std::min<long>(cus, (ntiles + 7) / 8 * 8);
-        hipLaunchKernelGGL((dma::k_conv256<EpiConv, 128>), dim3((unsigned)grid), dim3(512), 0, st, g, Wt, M, N, K, epi);
+        const unsigned grid = persistent_grid((long)(N / 128) * ((M + 255) / 256));
+        hipLaunchKernelGGL((dma::k_conv256<EpiConv, 128>), dim3(grid), dim3(512), 0, st, g, Wt, M, N, K, epi);
     }
     MLG_LAUNCH_CHECK();
     return MLG_OK;

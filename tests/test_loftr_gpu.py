@@ -181,6 +181,41 @@ def test_implicit_conv_matches_float64_conv(dev, B, H, W, C, k, s, N):
     assert err <= 1e-5 * float(ref.abs().max()), err
 
 
+@pytest.mark.parametrize("B,H,W,C,k,s,N", [(1, 258, 258, 128, 1, 1, 512), (1, 258, 258, 128, 1, 1, 128),
+                                           (2, 131, 127, 128, 3, 1, 512)])
+def test_implicit_conv_walking_tiles_matches_float64_conv(dev, B, H, W, C, k, s, N):
+    """test_implicit_conv_matches_float64_conv with more output tiles than CUs, so that a
+    k_conv256 workgroup walks: it takes a second tile, recomputes its rows' pixel origins
+    and prefetches that tile's first K-tile in the last K-step of the one before.  522
+    tiles of 256 x 256 (the last M-tile of 4 rows), 261 of 256 x 128, and 260 with 3 x 3
+    taps and zero padding (the last M-tile of 250 rows).  The float64 reference is the
+    im2col product on the device (unfold of the same bf16 values, float64 matmul).  Same
+    bar: |err| <= 1e-5 of the output scale."""
+    from mlgate import _native
+    Ho, Wo = (H + s - 1) // s, (W + s - 1) // s
+    ntiles = ((B * Ho * Wo + 255) // 256) * (N // (256 if N % 256 == 0 else 128))
+    assert ntiles > torch.cuda.get_device_properties(dev).multi_processor_count
+    g = torch.Generator().manual_seed(B * 1000 + H + k + s)
+    x = torch.randn(B, H, W, C, generator=g).to(torch.bfloat16)
+    w = (torch.randn(N, k, k, C, generator=g) / (k * (C ** 0.5))).to(torch.bfloat16)
+    bias = torch.randn(N, generator=g) * 0.1
+    xd, wd, bd = x.to(dev), w.reshape(N, -1).contiguous().to(dev), bias.to(dev)
+    zero = torch.zeros(8, dtype=torch.bfloat16, device=dev)
+    out = torch.full((B, Ho, Wo, N), float("nan"), device=dev)
+    P = _native.ptr
+    rc = _native.lib().mlg_op_conv2d_nhwc(P(xd), P(zero), B, H, W, C, k, s, P(wd), P(bd), P(out), N,
+                                          torch.cuda.current_stream(dev).cuda_stream)
+    assert rc == 0
+    # unfold orders a patch (c, ty, tx): the weights go the same way
+    cols = torch.nn.functional.unfold(xd.double().permute(0, 3, 1, 2), k, padding=k // 2, stride=s)
+    wm = w.to(dev).double().permute(0, 3, 1, 2).reshape(N, -1)
+    ref = (cols.transpose(1, 2) @ wm.T + bd.double()).reshape(B, Ho, Wo, N)
+    got = out.double()
+    assert got.shape == ref.shape and torch.isfinite(got).all()
+    err = float((got - ref).abs().max())
+    assert err <= 1e-5 * float(ref.abs().max()), err
+
+
 @pytest.mark.parametrize("layer", [0, 1])
 def test_fused_coarse_tail_equals_unfused_layer(dev, setup, layer):
     """the fused coarse block tail (merge, norm1, ReLU MLP, norm2, residual in

@@ -109,3 +109,19 @@ def test_precise_batch_split_bit_identical(dev, sd, frames):
     d4 = VitB14(sd, device="cuda", max_batch=4, precise=True).forward(x)
     torch.cuda.synchronize()
     assert torch.equal(d2, d4)
+
+
+def test_precise_batch_split_bit_identical_walking_tiles(dev, sd, frames):
+    """The same with more output tiles than CUs, so that the persistent split GEMM
+    (gemm_bf16.hip k_gemm256s) walks: a workgroup takes a second 256 x 256 tile and its
+    last K-step prefetches that tile's operands.  16 frames in one batch are M = 8480
+    token rows = 34 M-tiles (the last of 32 rows): qkv has 306 tiles and fc1 408."""
+    x = torch.from_numpy(np.tile(frames, (4, 1, 1, 1))).to(dev)
+    e16 = VitB14(sd, device="cuda", max_batch=16, precise=True)
+    m_tiles = (len(x) * (e16.n_patches + 1) + 255) // 256
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    assert m_tiles * (3 * 768 // 256) > cus and m_tiles * (4 * 768 // 256) > cus
+    d16 = e16.forward(x)
+    d4 = VitB14(sd, device="cuda", max_batch=4, precise=True).forward(x)
+    torch.cuda.synchronize()
+    assert torch.equal(d16, d4)
