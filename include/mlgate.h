@@ -35,7 +35,7 @@ extern "C" {
 #define MLG_VIT_PATCH_K 768 /* 3*14*14 = 588 patch inputs, zero-padded to 12 K-tiles of 64 */
 
 /* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_salad_weights,
- * mlg_rn_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
+ * mlg_rn_weights, mlg_mixvpr_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
  * mlg_orb_params) begins with a head: struct_size = sizeof(the struct) and abi_version =
  * MLG_ABI_VERSION, both set by initialising it with MLG_STRUCT_INIT(type).  A struct whose
  * head disagrees -- built against another version of this header (a shorter or longer
@@ -320,6 +320,44 @@ int mlg_resnet50_forward(const mlg_rn_weights* w, const uint8_t* frames, int B, 
  * (workspace sized by mlg_resnet50_workspace_bytes). */
 int mlg_op_pillow_resize_224(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, void* workspace,
                              size_t workspace_bytes, uint8_t* out, void* stream);
+
+/* -------------------------------------------------------------- MixVPR --
+ * MixVPR's native branch (scripts/semantic_gating/place_recognition.py:227-239, 308-332):
+ * MixVPRModel(backbone='resnet50', out_dim=4096).  cv2.resize INTER_LINEAR to 320x320 ->
+ * gray / BGRA / BGR -> RGB -> /255 -> ImageNet normalise -> torchvision resnet50 cropped
+ * after layer3 ([B, 1024, 20, 20], eval BatchNorm folded by the caller) -> 4 feature-mixer
+ * blocks x += Linear2(ReLU(Linear1(LayerNorm400(x)))) along the 400 spatial features ->
+ * channel_proj (1024 -> 1024) -> row_proj (400 -> 4) -> L2 norm -> [B, 4096], index o*4 + r.
+ * The kernels apply row_proj before channel_proj (both are linear), hence row_s.
+ * Packing (mlgate/mixvpr.py pack_head): Linear weights [400][400] zero-padded to
+ * [416][416], bf16, k-step-major [26][416][16]; per-feature vectors zero-padded to 512. */
+typedef struct mlg_mixvpr_weights {
+    uint32_t struct_size, abi_version; /* MLG_STRUCT_INIT(mlg_mixvpr_weights) */
+    const float* stem_w;    /* f32 [64][7][7][3] */
+    const float* stem_b;    /* f32 [64] */
+    mlg_rn_block blocks[13]; /* layer1 (3), layer2 (4), layer3 (6) */
+    const uint16_t* mix_w;  /* bf16 [4 blocks][2 (Linear1, Linear2)][26][416][16] */
+    const float* mix_p;     /* f32 [4 blocks][4 (LayerNorm weight, bias, Linear1 bias, Linear2 bias)][512] */
+    const float* row_w;     /* f32 [4][512]: row_proj.weight */
+    const float* chan_w;    /* f32 [1024][1024]: channel_proj.weight */
+    const float* chan_b;    /* f32 [1024]: channel_proj.bias */
+    const float* row_s;     /* f32 [4]: sum_i row_proj.weight[r][i] */
+    const float* row_b;     /* f32 [4]: row_proj.bias */
+} mlg_mixvpr_weights;
+#define MLG_MIXVPR_DIM 4096
+#define MLG_MIXVPR_SIZE 320
+/* 0 for B, H or W <= 0 */
+size_t mlg_mixvpr_workspace_bytes(int B, int H, int W);
+/* frames: device uint8 [B] x (H x W x C), C in {1, 3 (BGR), 4 (BGRA)}; desc: device f32
+ * [B, MLG_MIXVPR_DIM], unit rows. */
+int mlg_mixvpr_forward(const mlg_mixvpr_weights* w, const uint8_t* frames, int B, int H, int W, int C,
+                       long frame_stride, void* workspace, size_t workspace_bytes, float* desc, void* stream);
+/* Parity entries.  The preprocessing alone -> f32 NHWC [B, 320, 320, 3] (RGB); the head
+ * alone on f32 layer3 features [B, 400, 1024] (NHWC) -> [B, 4096] (reads only the head
+ * fields of w; no workspace). */
+int mlg_op_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, float* out,
+                             void* stream);
+int mlg_op_mixvpr_head(const mlg_mixvpr_weights* w, const float* features, int B, float* desc, void* stream);
 
 /* -------------------------------------------------------- SuperPoint --
  * Replaces the extractor half of LightGlue._detect_and_match_native

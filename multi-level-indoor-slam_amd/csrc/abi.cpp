@@ -392,6 +392,55 @@ int mlg_op_pillow_resize_224(const uint8_t* frames, int B, int H, int W, int C, 
                             (hipStream_t)stream);
 }
 
+static_assert(offsetof(mlg_mixvpr_weights, mix_w) + sizeof(mlg_mix_weights_i) == sizeof(mlg_mixvpr_weights),
+              "MixVPR head weight tables must match");
+
+size_t mlg_mixvpr_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return mlg_resnet50_l3_ws_bytes(B, MLG_MIXVPR_SIZE);
+}
+
+static bool mixvpr_head_ok(const mlg_mixvpr_weights* w) {
+    return w->mix_w && w->mix_p && w->row_w && w->chan_w && w->chan_b && w->row_s && w->row_b;
+}
+
+int mlg_mixvpr_forward(const mlg_mixvpr_weights* w, const uint8_t* frames, int B, int H, int W, int C,
+                       long frame_stride, void* workspace, size_t workspace_bytes, float* desc, void* stream) {
+    if (!mlg_head_ok(w, MLG_ABI_VERSION) || !frames || !workspace || !desc || !w->stem_w || !w->stem_b ||
+        !mixvpr_head_ok(w))
+        return MLG_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || frame_stride < (long)H * W * C)
+        return MLG_EINVAL;
+    mlg_rn_weights_i rn{};
+    rn.stem_w = w->stem_w;
+    rn.stem_b = w->stem_b;
+    for (int i = 0; i < 13; ++i) {
+        const mlg_rn_block& b = w->blocks[i];
+        if (!b.w1 || !b.b1 || !b.w2 || !b.b2 || !b.w3 || !b.b3) return MLG_EINVAL;
+        const bool first = i == 0 || i == 3 || i == 7;
+        if (first != (b.wd != nullptr) || (b.wd && !b.bd)) return MLG_EINVAL;
+        rn.blocks[i] = {b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, b.wd, b.bd};
+    }
+    if (workspace_bytes < mlg_mixvpr_workspace_bytes(B, H, W)) return MLG_ENOMEM;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(mlg_mixvpr_preprocess(frames, B, H, W, C, frame_stride, mlg_resnet50_l3_image(workspace, B, MLG_MIXVPR_SIZE),
+                              s));
+    float* feat = nullptr;
+    TRY(mlg_resnet50_l3_run(rn, B, MLG_MIXVPR_SIZE, workspace, workspace_bytes, &feat, s));
+    return mlg_mixvpr_head(*reinterpret_cast<const mlg_mix_weights_i*>(&w->mix_w), feat, B, desc, s);
+}
+
+int mlg_op_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, float* out,
+                             void* stream) {
+    return mlg_mixvpr_preprocess(frames, B, H, W, C, frame_stride, out, (hipStream_t)stream);
+}
+
+int mlg_op_mixvpr_head(const mlg_mixvpr_weights* w, const float* features, int B, float* desc, void* stream) {
+    if (!mlg_head_ok(w, MLG_ABI_VERSION) || !mixvpr_head_ok(w)) return MLG_EINVAL;
+    return mlg_mixvpr_head(*reinterpret_cast<const mlg_mix_weights_i*>(&w->mix_w), features, B, desc,
+                           (hipStream_t)stream);
+}
+
 size_t mlg_superpoint_workspace_bytes(int B, int H, int W) { return mlg_superpoint_ws_bytes(B, H, W); }
 
 int mlg_superpoint(const mlg_sp_weights* w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,

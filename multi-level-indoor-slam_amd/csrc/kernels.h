@@ -244,6 +244,31 @@ size_t mlg_resnet50_ws_bytes(int B, int H, int W);
 int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                      int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s);
 
+// The same trunk cropped after layer3 at input side S (320: MixVPR's native branch): the
+// caller writes the normalised f32 NHWC image [B, S, S, 3] at mlg_resnet50_l3_image(ws),
+// the run leaves *feat -> the f32 residual stream [B, (S/16)^2, 1024] inside ws.
+// w.blocks[13..15] are not read.
+size_t mlg_resnet50_l3_ws_bytes(int B, int S);
+float* mlg_resnet50_l3_image(void* ws, int B, int S);
+int mlg_resnet50_l3_run(const mlg_rn_weights_i& w, int B, int S, void* ws, size_t ws_bytes, float** feat,
+                        hipStream_t s);
+
+// mixvpr.hip -- MixVPR's native branch: cv2 preprocessing to 320 x 320 and the fused
+// feature-mixer head (4 mixer blocks + row_proj per 64-row tile, then channel_proj + L2 norm)
+struct mlg_mix_weights_i {
+    const bf16_t* mix_w;   // bf16 [4 blocks][2][26][416][16]: Linear1 / Linear2 k-step-major, zero-padded 400 -> 416
+    const float* mix_p;    // f32 [4 blocks][4][512]: LayerNorm gamma, beta, bias1, bias2 (zero past 400)
+    const float* row_w;    // f32 [4][512]: row_proj.weight (zero past 400)
+    const float* chan_w;   // f32 [1024][1024]: channel_proj.weight
+    const float* chan_b;   // f32 [1024]: channel_proj.bias
+    const float* row_s;    // f32 [4]: sum_i row_proj.weight[r][i]
+    const float* row_b;    // f32 [4]: row_proj.bias
+};
+int mlg_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, float* out,
+                          hipStream_t s);
+// feat f32 [B, 400, 1024] (NHWC layer3 stream) -> desc f32 [B, 4096], L2-normalised
+int mlg_mixvpr_head(const mlg_mix_weights_i& w, const float* feat, int B, float* desc, hipStream_t s);
+
 // plane.hip -- batched LiDAR ground-plane RANSAC
 size_t mlg_plane_ws_bytes(int S, int H);
 int mlg_plane_ransac_run(const float* pts, const int32_t* offs, int S, int H, uint64_t seed, double thr, void* ws,

@@ -12,6 +12,10 @@
 // activation matrix, 3x3 convs on an im2col copy (k = tap * Cin + c).  The residual
 // stream stays f32 (the conv3 epilogue adds bias + shortcut, applies ReLU and writes
 // the bf16 copy the next GEMM reads).
+//
+// The trunk (stem, max-pool, bottleneck stages) is parameterised on the input side S:
+// 224 for the fallback above, 320 for MixVPR's native branch (mixvpr.hip), which stops
+// after layer3 and takes the f32 residual stream [B, (S/16)^2, 1024] instead of the pool.
 #include <math.h>
 
 #include <map>
@@ -77,8 +81,10 @@ __global__ void k_rn_resize_v(const uint8_t* __restrict__ tmp, int H, const int*
     }
 }
 
-// stem: 7x7 stride-2 pad-3 conv 3 -> 64 (folded BN) + ReLU, f32 math -> bf16 [B,112,112,64]
-// and f32 copy is not needed (max-pool follows).  One thread per output pixel.
+// stem: 7x7 stride-2 pad-3 conv 3 -> 64 (folded BN) + ReLU, f32 math -> bf16 [B,S/2,S/2,64]
+// and f32 copy is not needed (max-pool follows).  One thread per output pixel.  S is a
+// template argument so the index arithmetic keeps its constants.
+template <int S>
 __global__ __launch_bounds__(256) void k_rn_stem(const float* __restrict__ img, const float* __restrict__ w,
                                                  const float* __restrict__ bias, bf16_t* __restrict__ out, int B) {
     __shared__ float sw[64 * 147];
@@ -87,16 +93,17 @@ __global__ __launch_bounds__(256) void k_rn_stem(const float* __restrict__ img, 
     if (threadIdx.x < 64) sb[threadIdx.x] = bias[threadIdx.x];
     __syncthreads();
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)B * 112 * 112) return;
-    const int x = (int)(e % 112), y = (int)((e / 112) % 112), b = (int)(e / (112 * 112));
+    constexpr int S2 = S / 2;
+    if (e >= (long)B * S2 * S2) return;
+    const int x = (int)(e % S2), y = (int)((e / S2) % S2), b = (int)(e / (S2 * S2));
     float acc[64];
 #pragma unroll
     for (int co = 0; co < 64; ++co) acc[co] = 0.f;
     for (int ky = 0; ky < 7; ++ky)
         for (int kx = 0; kx < 7; ++kx) {
             const int yy = 2 * y - 3 + ky, xx = 2 * x - 3 + kx;
-            const bool ok = yy >= 0 && yy < RN_S && xx >= 0 && xx < RN_S;
-            const float* p = img + (((size_t)b * RN_S + (ok ? yy : 0)) * RN_S + (ok ? xx : 0)) * 3;
+            const bool ok = yy >= 0 && yy < S && xx >= 0 && xx < S;
+            const float* p = img + (((size_t)b * S + (ok ? yy : 0)) * S + (ok ? xx : 0)) * 3;
             for (int c = 0; c < 3; ++c) {
                 const float v = ok ? p[c] : 0.f;
                 const int k = (ky * 7 + kx) * 3 + c;
@@ -115,18 +122,20 @@ __global__ __launch_bounds__(256) void k_rn_stem(const float* __restrict__ img, 
     }
 }
 
-// 3x3 stride-2 pad-1 max-pool, bf16 [B,112,112,64] -> f32 + bf16 [B,56,56,64]
+// 3x3 stride-2 pad-1 max-pool, bf16 [B,S/2,S/2,64] -> f32 + bf16 [B,S/4,S/4,64]
+template <int S>
 __global__ void k_rn_maxpool(const bf16_t* __restrict__ in, float* __restrict__ outf, bf16_t* __restrict__ outb,
                              int B) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;  // (b, y, x, c)
-    if (e >= (long)B * 56 * 56 * 64) return;
-    const int c = (int)(e % 64), x = (int)((e / 64) % 56), y = (int)((e / (64 * 56)) % 56), b = (int)(e / (64 * 56 * 56));
+    constexpr int S2 = S / 2, S4 = S / 4;
+    if (e >= (long)B * S4 * S4 * 64) return;
+    const int c = (int)(e % 64), x = (int)((e / 64) % S4), y = (int)((e / (64 * S4)) % S4), b = (int)(e / (64 * S4 * S4));
     float m = -INFINITY;
     for (int ky = 0; ky < 3; ++ky)
         for (int kx = 0; kx < 3; ++kx) {
             const int yy = 2 * y - 1 + ky, xx = 2 * x - 1 + kx;
-            if (yy >= 0 && yy < 112 && xx >= 0 && xx < 112)
-                m = fmaxf(m, bf16_to_f32(in[(((size_t)b * 112 + yy) * 112 + xx) * 64 + c]));
+            if (yy >= 0 && yy < S2 && xx >= 0 && xx < S2)
+                m = fmaxf(m, bf16_to_f32(in[(((size_t)b * S2 + yy) * S2 + xx) * 64 + c]));
         }
     outf[e] = m;
     outb[e] = f32_to_bf16(m);
@@ -223,7 +232,9 @@ struct RnLayout {
     size_t tables, tmp, img, stem, xf0, xf1, xb0, xb1, t1, t2, col, sub, total;
 };
 
-RnLayout rn_layout(int B, int H) {
+// S: the trunk's input side (a multiple of 32); H: the source height of the Pillow resize
+// (0: the caller supplies the normalised image, no tables / intermediate)
+RnLayout rn_layout(int B, int H, int S) {
     RnLayout L;
     size_t o = 0;
     auto take = [&](size_t bytes) {
@@ -231,20 +242,19 @@ RnLayout rn_layout(int B, int H) {
         o += a256(bytes);
         return r;
     };
-    const size_t m56 = (size_t)B * 56 * 56;
-    L.tables = take((size_t)4 * (2 * RN_S + RN_S * 64) * 2 + 4096);  // generous: two (xmin, xcnt, kk) sets
+    const size_t m4 = (size_t)B * (S / 4) * (S / 4), m8 = (size_t)B * (S / 8) * (S / 8);
+    L.tables = take(H ? (size_t)4 * (2 * RN_S + RN_S * 64) * 2 + 4096 : 0);  // generous: two (xmin, xcnt, kk) sets
     L.tmp = take((size_t)B * H * RN_S * 3);
-    L.img = take((size_t)B * RN_S * RN_S * 3 * 4);
-    L.stem = take((size_t)B * 112 * 112 * 64 * 2);
-    L.xf0 = take(m56 * 256 * 4);  // largest residual tensor: stage 1, 56x56x256
-    L.xf1 = take(m56 * 256 * 4);
-    L.xb0 = take(m56 * 256 * 2);
-    L.xb1 = take(m56 * 256 * 2);
-    L.t1 = take(m56 * 128 * 2);   // bottleneck conv1 out (<= 56x56x64 padded to 128, 28x28x128 ...)
-    L.t2 = take(m56 * 128 * 2);   // conv2 out
-    L.col = take(m56 * 9 * 64 * 2 > (size_t)B * 28 * 28 * 9 * 128 * 2 ? m56 * 9 * 64 * 2
-                                                                          : (size_t)B * 28 * 28 * 9 * 128 * 2);
-    L.sub = take((size_t)B * 28 * 28 * 256 * 2);
+    L.img = take((size_t)B * S * S * 3 * 4);
+    L.stem = take((size_t)B * (S / 2) * (S / 2) * 64 * 2);
+    L.xf0 = take(m4 * 256 * 4);  // largest residual tensor: stage 1, S/4 x S/4 x 256
+    L.xf1 = take(m4 * 256 * 4);
+    L.xb0 = take(m4 * 256 * 2);
+    L.xb1 = take(m4 * 256 * 2);
+    L.t1 = take(m4 * 128 * 2);   // bottleneck conv1 out (<= S/4 x S/4 x 64 padded to 128, S/8 x S/8 x 128 ...)
+    L.t2 = take(m4 * 128 * 2);   // conv2 out
+    L.col = take(m4 * 9 * 64 * 2 > m8 * 9 * 128 * 2 ? m4 * 9 * 64 * 2 : m8 * 9 * 128 * 2);
+    L.sub = take(m8 * 256 * 2);
     L.total = o;
     return L;
 }
@@ -263,35 +273,12 @@ struct CoeffCache {
 
 }  // namespace
 
-size_t mlg_resnet50_ws_bytes(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return rn_layout(B, H).total;
-}
-
-int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
-                     int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s) {
-    if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || D <= 0) return MLG_EINVAL;
-    const RnLayout L = rn_layout(B, H);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* base = (char*)ws;
-    const Coeffs& ch = g_coeffs.get(W);
-    const Coeffs& cv = g_coeffs.get(H);
-    int* tb = (int*)(base + L.tables);
-    int* hx0 = tb;
-    int* hxc = hx0 + RN_S;
-    int* hkk = hxc + RN_S;
-    int* vy0 = hkk + (size_t)RN_S * ch.ksize;
-    int* vyc = vy0 + RN_S;
-    int* vkk = vyc + RN_S;
-    if ((size_t)((char*)(vkk + (size_t)RN_S * cv.ksize) - (char*)tb) > L.tmp - L.tables) return MLG_EINVAL;
-    if (hipMemcpyAsync(hx0, ch.xmin.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(hxc, ch.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(hkk, ch.kk.data(), ch.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(vy0, cv.xmin.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(vyc, cv.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(vkk, cv.kk.data(), cv.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return MLG_EHIP;
-    uint8_t* tmp = (uint8_t*)(base + L.tmp);
+// Stem, max-pool and the first `nstages` bottleneck stages over the normalised image at
+// base + L.img (f32 NHWC [B, S, S, 3]); *xout: the f32 residual stream
+// [B, side, side, C] it ends with (inside the workspace).
+template <int S>
+static int rn_trunk(const mlg_rn_weights_i& w, int B, int nstages, char* base, const RnLayout& L, hipStream_t s,
+             float** xout, int* side) {
     float* img = (float*)(base + L.img);
     bf16_t* stem = (bf16_t*)(base + L.stem);
     float* xf[2] = {(float*)(base + L.xf0), (float*)(base + L.xf1)};
@@ -301,26 +288,16 @@ int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, in
     bf16_t* col = (bf16_t*)(base + L.col);
     bf16_t* sub = (bf16_t*)(base + L.sub);
 
-    const long nh = (long)B * H * RN_S;
-    hipLaunchKernelGGL(k_rn_resize_h, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, frames, frame_stride, H, W,
-                       C, hx0, hxc, hkk, ch.ksize, tmp, B);
-    const long nv = (long)B * RN_S * RN_S;
-    hipLaunchKernelGGL(k_rn_resize_v, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, tmp, H, vy0, vyc, vkk,
-                       cv.ksize, img, resized_u8, B);
-    if (resized_u8) {  // parity entry: stop after the resize
-        MLG_LAUNCH_CHECK();
-        return MLG_OK;
-    }
-    const long ns = (long)B * 112 * 112;
-    hipLaunchKernelGGL(k_rn_stem, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, img, w.stem_w, w.stem_b, stem,
-                       B);
-    const long np = (long)B * 56 * 56 * 64;
-    hipLaunchKernelGGL(k_rn_maxpool, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, stem, xf[0], xb[0], B);
+    const long ns = (long)B * (S / 2) * (S / 2);
+    hipLaunchKernelGGL(k_rn_stem<S>, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, img, w.stem_w, w.stem_b,
+                       stem, B);
+    const long np = (long)B * (S / 4) * (S / 4) * 64;
+    hipLaunchKernelGGL(k_rn_maxpool<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, stem, xf[0], xb[0], B);
     MLG_LAUNCH_CHECK();
 
-    int cur = 0, Hc = 56, Cc = 64, blk = 0;
+    int cur = 0, Hc = S / 4, Cc = 64, blk = 0;
     const int widths[4] = {64, 128, 256, 512}, nblocks[4] = {3, 4, 6, 3};
-    for (int st = 0; st < 4; ++st) {
+    for (int st = 0; st < nstages; ++st) {
         const int width = widths[st], wpad = width < 128 ? 128 : width;
         for (int bi = 0; bi < nblocks[st]; ++bi, ++blk) {
             const mlg_rn_block_i& bw = w.blocks[blk];
@@ -369,9 +346,73 @@ int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, in
             Cc = 4 * width;
         }
     }
+    *xout = xf[cur];
+    *side = Hc;
+    return MLG_OK;
+}
+
+size_t mlg_resnet50_ws_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return rn_layout(B, H, RN_S).total;
+}
+
+int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+                     int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s) {
+    if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || D <= 0) return MLG_EINVAL;
+    const RnLayout L = rn_layout(B, H, RN_S);
+    if (ws_bytes < L.total) return MLG_EINVAL;
+    char* base = (char*)ws;
+    const Coeffs& ch = g_coeffs.get(W);
+    const Coeffs& cv = g_coeffs.get(H);
+    int* tb = (int*)(base + L.tables);
+    int* hx0 = tb;
+    int* hxc = hx0 + RN_S;
+    int* hkk = hxc + RN_S;
+    int* vy0 = hkk + (size_t)RN_S * ch.ksize;
+    int* vyc = vy0 + RN_S;
+    int* vkk = vyc + RN_S;
+    if ((size_t)((char*)(vkk + (size_t)RN_S * cv.ksize) - (char*)tb) > L.tmp - L.tables) return MLG_EINVAL;
+    if (hipMemcpyAsync(hx0, ch.xmin.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(hxc, ch.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(hkk, ch.kk.data(), ch.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(vy0, cv.xmin.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(vyc, cv.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(vkk, cv.kk.data(), cv.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return MLG_EHIP;
+    uint8_t* tmp = (uint8_t*)(base + L.tmp);
+    float* img = (float*)(base + L.img);
+
+    const long nh = (long)B * H * RN_S;
+    hipLaunchKernelGGL(k_rn_resize_h, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, frames, frame_stride, H, W,
+                       C, hx0, hxc, hkk, ch.ksize, tmp, B);
+    const long nv = (long)B * RN_S * RN_S;
+    hipLaunchKernelGGL(k_rn_resize_v, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, tmp, H, vy0, vyc, vkk,
+                       cv.ksize, img, resized_u8, B);
+    if (resized_u8) {  // parity entry: stop after the resize
+        MLG_LAUNCH_CHECK();
+        return MLG_OK;
+    }
+    float* x = nullptr;
+    int Hc = 0;
+    MLG_TRY(rn_trunk<RN_S>(w, B, 4, base, L, s, &x, &Hc));
     const long nd = (long)B * D;
-    hipLaunchKernelGGL(k_rn_avgpool, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, xf[cur], B, Hc * Hc, D,
-                       desc);
+    hipLaunchKernelGGL(k_rn_avgpool, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, x, B, Hc * Hc, D, desc);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
+}
+
+size_t mlg_resnet50_l3_ws_bytes(int B, int S) {
+    if (B <= 0 || S != 320) return 0;
+    return rn_layout(B, 0, S).total;
+}
+
+float* mlg_resnet50_l3_image(void* ws, int B, int S) { return (float*)((char*)ws + rn_layout(B, 0, S).img); }
+
+int mlg_resnet50_l3_run(const mlg_rn_weights_i& w, int B, int S, void* ws, size_t ws_bytes, float** feat,
+                        hipStream_t s) {
+    if (B <= 0 || S != 320 || !feat) return MLG_EINVAL;  // one instantiation per supported side
+    const RnLayout L = rn_layout(B, 0, S);
+    if (ws_bytes < L.total) return MLG_ENOMEM;
+    int side = 0;
+    return rn_trunk<320>(w, B, 3, (char*)ws, L, s, feat, &side);
 }

@@ -651,6 +651,84 @@ Tensor pillow_resize_224(const Tensor& frames) {
     return out;
 }
 
+// ------------------------------------------------------------------ MixVPR
+// head = [mix_w bf16, mix_p, row_w, chan_w, chan_b, row_s, row_b] (mlgate/mixvpr.py pack_head)
+void mixvpr_head_weights(at::TensorList head, mlg_mixvpr_weights& s) {
+    TORCH_CHECK(head.size() == 7, "mixvpr head weights: expected 7 tensors");
+    const int64_t numel[7] = {4LL * 2 * 26 * 416 * 16, 4 * 4 * 512, 4 * 512, 1024 * 1024, 1024, 4, 4};
+    for (int i = 0; i < 7; ++i) {
+        want(head[i], i == 0 ? at::kBFloat16 : at::kFloat, "mixvpr head weight");
+        TORCH_CHECK(head[i].numel() == numel[i], "mixvpr head weight ", i, ": expected ", numel[i], " elements");
+    }
+    s.mix_w = cp<uint16_t>(head[0]);
+    s.mix_p = cp<float>(head[1]);
+    s.row_w = cp<float>(head[2]);
+    s.chan_w = cp<float>(head[3]);
+    s.chan_b = cp<float>(head[4]);
+    s.row_s = cp<float>(head[5]);
+    s.row_b = cp<float>(head[6]);
+}
+
+// frames uint8 [B, H, W, C] -> desc f32 [B, 4096]; trunk = [stem_w, stem_b] + 13 x mlg_rn_block
+Tensor mixvpr_forward(const Tensor& frames, at::TensorList trunk, at::TensorList head, int64_t max_batch) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    TORCH_CHECK(trunk.size() == 2 + 13 * 8, "mixvpr trunk weights: expected 106 tensors");
+    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    mlg_mixvpr_weights s = MLG_STRUCT_INIT(mlg_mixvpr_weights);
+    s.stem_w = cp<float>(trunk[0]);
+    s.stem_b = cp<float>(trunk[1]);
+    for (int b = 0; b < 13; ++b) {
+        const Tensor* t = &trunk[2 + 8 * b];
+        mlg_rn_block& o = s.blocks[b];
+        o.w1 = cp<uint16_t>(t[0]); o.b1 = cp<float>(t[1]);
+        o.w2 = cp<uint16_t>(t[2]); o.b2 = cp<float>(t[3]);
+        o.w3 = cp<uint16_t>(t[4]); o.b3 = cp<float>(t[5]);
+        o.wd = cp<uint16_t>(t[6]); o.bd = cp<float>(t[7]);
+    }
+    mixvpr_head_weights(head, s);
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    c10::DeviceGuard g(frames.device());
+    Tensor desc = at::empty({B, MLG_MIXVPR_DIM}, frames.options().dtype(at::kFloat));
+    const int64_t nb_max = std::min(B, max_batch);
+    Tensor ws = workspace(mlg_mixvpr_workspace_bytes((int)nb_max, (int)H, (int)W), frames);
+    const long stride = (long)(H * W * C);
+    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
+        const int nb = (int)std::min(max_batch, B - b0);
+        check_rc(mlg_mixvpr_forward(&s, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
+                                    ws.data_ptr(), (size_t)ws.numel(), mp<float>(desc) + b0 * MLG_MIXVPR_DIM,
+                                    stream_of(frames)),
+                 "mlg_mixvpr_forward");
+    }
+    return desc;
+}
+
+// f32 layer3 features [B, 400, 1024] (NHWC) -> desc f32 [B, 4096]
+Tensor mixvpr_head(const Tensor& feat, at::TensorList head) {
+    want(feat, at::kFloat, "features");
+    TORCH_CHECK(feat.dim() == 3 && feat.size(1) == 400 && feat.size(2) == 1024, "features must be [B, 400, 1024]");
+    mlg_mixvpr_weights s = MLG_STRUCT_INIT(mlg_mixvpr_weights);
+    mixvpr_head_weights(head, s);
+    c10::DeviceGuard g(feat.device());
+    Tensor desc = at::empty({feat.size(0), MLG_MIXVPR_DIM}, feat.options());
+    check_rc(mlg_op_mixvpr_head(&s, cp<float>(feat), (int)feat.size(0), mp<float>(desc), stream_of(feat)),
+             "mlg_op_mixvpr_head");
+    return desc;
+}
+
+// frames uint8 [B, H, W, C] -> f32 [B, 320, 320, 3] (RGB, normalised)
+Tensor mixvpr_preprocess(const Tensor& frames) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    c10::DeviceGuard g(frames.device());
+    Tensor out = at::empty({B, MLG_MIXVPR_SIZE, MLG_MIXVPR_SIZE, 3}, frames.options().dtype(at::kFloat));
+    check_rc(mlg_op_mixvpr_preprocess(cp<uint8_t>(frames), (int)B, (int)H, (int)W, (int)C, (long)(H * W * C),
+                                      mp<float>(out), stream_of(frames)),
+             "mlg_op_mixvpr_preprocess");
+    return out;
+}
+
 // ---------------------------------------------------- LiDAR plane RANSAC
 std::tuple<Tensor, Tensor, Tensor> plane_ransac(const Tensor& pts, const Tensor& offsets, int64_t iterations,
                                                 int64_t seed, double threshold) {
@@ -919,6 +997,9 @@ TORCH_LIBRARY(mlgate, m) {
           "int hypotheses, int seed, bool with_pose) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("recover_pose(Tensor k1, Tensor k2, Tensor offsets, Tensor K, int k_stride, Tensor E, Tensor mask) -> Tensor");
     m.def("resnet50(Tensor frames, Tensor[] weights, int descriptor_dim) -> Tensor");
+    m.def("mixvpr_forward(Tensor frames, Tensor[] trunk, Tensor[] head, int max_batch) -> Tensor");
+    m.def("mixvpr_head(Tensor features, Tensor[] head) -> Tensor");
+    m.def("mixvpr_preprocess(Tensor frames) -> Tensor");
     m.def("loftr_features(Tensor frames, Tensor[] weights) -> (Tensor, Tensor)");
     m.def("loftr_pack_tails(Tensor[] weights) -> Tensor");
     m.def("loftr_coarse_layer(Tensor(a!) x, Tensor(b!) cat, Tensor[] weights, int layer, int fused, int nseg, int L) -> ()");
@@ -963,6 +1044,9 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("ransac_epipolar", &ransac_epipolar);
     m.impl("recover_pose", &recover_pose);
     m.impl("resnet50", &resnet50);
+    m.impl("mixvpr_forward", &mixvpr_forward);
+    m.impl("mixvpr_head", &mixvpr_head);
+    m.impl("mixvpr_preprocess", &mixvpr_preprocess);
     m.impl("loftr_features", &loftr_features);
     m.impl("loftr_pack_tails", &loftr_pack_tails);
     m.impl("loftr_coarse_layer", &loftr_coarse_layer);

@@ -3,41 +3,16 @@
 // GeM pooling of the CricaVPR descriptor.
 #include "common.h"
 #include "kernels.h"
+#include "resize_cv.h"
 
 namespace {
 
 // ----------------------------------------------------------- preprocessing ---
 // CricaVPR._preprocess (place_recognition.py:781-803) fused with the patch-embed
-// im2col: cv2.resize INTER_LINEAR on uint8 (OpenCV fixed-point generic path:
-// 11-bit weights, 128-bit vector vertical pass + scalar tail -- the same restatement
-// as oracle/csrc/oracle.c), BGR/BGRA/gray -> RGB, float32 /255, float64
+// im2col: cv2.resize INTER_LINEAR on uint8 (OpenCV's fixed-point generic path,
+// resize_cv.h), BGR/BGRA/gray -> RGB, float32 /255, float64
 // (x - mean) / std, -> bf16 patch rows A[b*P + p, k], k = c*196 + ky*14 + kx
 // (Conv2d weight order), zero for k in [588, Kpad).
-
-__device__ __forceinline__ int16_t sat16(int v) { return (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-
-__device__ __forceinline__ void axis_lookup(int d, int ssize, int dsize, bool clamp, int& s0, int& s1, int& w0,
-                                            int& w1) {
-    const double scale = 1.0 / ((double)dsize / ssize);
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-    }
-    w0 = sat16((int)__builtin_rintf((1.f - f) * 2048.f));
-    w1 = sat16((int)__builtin_rintf(f * 2048.f));
-    s0 = min(max(s, 0), ssize - 1);
-    s1 = min(max(s + 1, 0), ssize - 1);
-}
-
-__device__ __forceinline__ int resize_vec_end(int wb) {
-    int x = 0;
-    if (wb >= 16) x = ((wb - 16) / 16 + 1) * 16;
-    while (x < wb - 8) x += 8;
-    return x;
-}
 
 struct PrepParams {
     const uint8_t* img;  // [B, H, W, C]
@@ -52,10 +27,7 @@ __global__ __launch_bounds__(256) void k_preprocess_patches(PrepParams pp, int t
     __shared__ float lut[3][256];
     for (int i = threadIdx.x; i < 768; i += 256) {
         const int c = i >> 8, u = i & 255;
-        const double mean = c == 0 ? 0.485 : (c == 1 ? 0.456 : 0.406);
-        const double std = c == 0 ? 0.229 : (c == 1 ? 0.224 : 0.225);
-        const float x = (float)u / 255.0f;
-        lut[c][u] = (float)(((double)x - mean) / std);
+        lut[c][u] = imagenet_norm(c, u);
     }
     __syncthreads();
     const int kchunks = pp.Kpad / 8;
@@ -77,22 +49,7 @@ __global__ __launch_bounds__(256) void k_preprocess_patches(PrepParams pp, int t
                     const int c = k / 196, rem = k - c * 196, ky = rem / 14, kx = rem - ky * 14;
                     const int y = py * 14 + ky, x = px * 14 + kx;
                     const int sc = pp.C == 1 ? 0 : (pp.swap_rb ? 2 - c : c);  // RGB c <- BGR(A) 2-c
-                    int sx0, sx1, ax0, ax1, sy0, sy1, by0, by1;
-                    axis_lookup(x, pp.W, pp.S, true, sx0, sx1, ax0, ax1);
-                    axis_lookup(y, pp.H, pp.S, false, sy0, sy1, by0, by1);
-                    const uint8_t* r0 = src + (size_t)sy0 * pp.W * pp.C;
-                    const uint8_t* r1 = src + (size_t)sy1 * pp.W * pp.C;
-                    const int h0 = r0[sx0 * pp.C + sc] * ax0 + r0[sx1 * pp.C + sc] * ax1;
-                    const int h1 = r1[sx0 * pp.C + sc] * ax0 + r1[sx1 * pp.C + sc] * ax1;
-                    int q;
-                    if (x * pp.C + sc < vend) {  // universal-intrinsic vertical pass
-                        const int a0 = sat16(h0 >> 4), a1 = sat16(h1 >> 4);
-                        int t = (int16_t)(((a0 * by0) >> 16) + ((a1 * by1) >> 16));
-                        q = (t + 2) >> 2;
-                    } else {  // scalar tail
-                        q = (h0 * by0 + h1 * by1 + (1 << 21)) >> 22;
-                    }
-                    q = min(max(q, 0), 255);
+                    const int q = resize_cv_sample(src, pp.H, pp.W, pp.C, pp.S, y, x, sc, vend);
                     val = lut[c][q];
                 }
                 v2[u] = val;

@@ -25,6 +25,40 @@ def fold_bn(w, sd, p):
     return w.astype(np.float32), (b - m * sc).astype(np.float32)
 
 
+def pack_trunk(sd, device, stages=RESNET_STAGES):
+    """torchvision resnet50 tensors -> the flat list behind mlg_rn_weights: the folded stem
+    (f32) and 8 tensors per bottleneck of ``stages`` (bf16 weights, f32 biases; BLOCK_ORDER)."""
+    def t(a, dtype):
+        return torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dtype).contiguous().to(device)
+
+    bf, f32 = torch.bfloat16, torch.float32
+    sw, sb = fold_bn(sd["conv1.weight"], sd, "bn1")
+    w = [t(sw.transpose(0, 2, 3, 1).reshape(64, 147), f32),  # [co][ky][kx][c]
+         t(sb, f32)]
+    empty = torch.empty(0, dtype=bf, device=device)
+    cin = 64
+    for li, (width, blocks, _) in enumerate(stages, 1):
+        wpad = max(width, 128)
+        for bi in range(blocks):
+            p = f"layer{li}.{bi}."
+            blk = {"wd": empty, "bd": empty.float()}
+            w1, b1 = fold_bn(np.asarray(sd[p + "conv1.weight"]).reshape(width, cin), sd, p + "bn1")
+            w2, b2 = fold_bn(sd[p + "conv2.weight"], sd, p + "bn2")
+            w2 = w2.transpose(0, 2, 3, 1).reshape(width, 9 * width)  # k = tap * width + c
+            pad = lambda a: np.concatenate([a, np.zeros((wpad - a.shape[0],) + a.shape[1:], np.float32)])  # noqa
+            blk["w1"], blk["b1"] = t(pad(w1), bf), t(pad(b1[:, None])[:, 0], f32)
+            blk["w2"], blk["b2"] = t(pad(w2), bf), t(pad(b2[:, None])[:, 0], f32)
+            w3, b3 = fold_bn(np.asarray(sd[p + "conv3.weight"]).reshape(4 * width, width), sd, p + "bn3")
+            blk["w3"], blk["b3"] = t(w3, bf), t(b3, f32)
+            if bi == 0:
+                wd, bd = fold_bn(np.asarray(sd[p + "downsample.0.weight"]).reshape(4 * width, cin), sd,
+                                 p + "downsample.1")
+                blk["wd"], blk["bd"] = t(wd, bf), t(bd, f32)
+            w += [blk[f] for f in BLOCK_ORDER]
+            cin = 4 * width
+    return w
+
+
 class ResNet50GPU:
     """Batched ResNet-50 GAP descriptors, zero-padded / truncated to descriptor_dim."""
 
@@ -36,37 +70,8 @@ class ResNet50GPU:
             self.weights_source = "given"
         self._w = self._pack(state_dict)
 
-    def _t(self, a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dtype).contiguous().to(self.device)
-
     def _pack(self, sd):
-        bf, f32 = torch.bfloat16, torch.float32
-        sw, sb = fold_bn(sd["conv1.weight"], sd, "bn1")
-        w = [self._t(sw.transpose(0, 2, 3, 1).reshape(64, 147), f32),  # [co][ky][kx][c]
-             self._t(sb, f32)]
-        empty = torch.empty(0, dtype=bf, device=self.device)
-        cin, k = 64, 0
-        for li, (width, blocks, _) in enumerate(RESNET_STAGES, 1):
-            wpad = max(width, 128)
-            for bi in range(blocks):
-                p = f"layer{li}.{bi}."
-                blk = {"wd": empty, "bd": empty.float()}
-                w1, b1 = fold_bn(np.asarray(sd[p + "conv1.weight"]).reshape(width, cin), sd, p + "bn1")
-                w2, b2 = fold_bn(sd[p + "conv2.weight"], sd, p + "bn2")
-                w2 = w2.transpose(0, 2, 3, 1).reshape(width, 9 * width)  # k = tap * width + c
-                pad = lambda a: np.concatenate([a, np.zeros((wpad - a.shape[0],) + a.shape[1:], np.float32)])  # noqa
-                blk["w1"], blk["b1"] = self._t(pad(w1), bf), self._t(pad(b1[:, None])[:, 0], f32)
-                blk["w2"], blk["b2"] = self._t(pad(w2), bf), self._t(pad(b2[:, None])[:, 0], f32)
-                w3, b3 = fold_bn(np.asarray(sd[p + "conv3.weight"]).reshape(4 * width, width), sd, p + "bn3")
-                blk["w3"], blk["b3"] = self._t(w3, bf), self._t(b3, f32)
-                if bi == 0:
-                    wd, bd = fold_bn(np.asarray(sd[p + "downsample.0.weight"]).reshape(4 * width, cin), sd,
-                                     p + "downsample.1")
-                    blk["wd"], blk["bd"] = self._t(wd, bf), self._t(bd, f32)
-                w += [blk[f] for f in BLOCK_ORDER]
-                cin = 4 * width
-                k += 1
-        return w
+        return pack_trunk(sd, self.device)
 
     def forward_device(self, frames, descriptor_dim):
         """frames: device uint8 [B, H, W, C] -> device f32 [B, descriptor_dim]."""

@@ -13,7 +13,8 @@ behaviour as the reference; the compute runs on the mlgate HIP kernels:
   * MixVPR / SALAD -> the reference resolves both to a torchvision ResNet-50 GAP
     fallback (place_recognition.py:241-306, 370-378); here that network runs on the
     GPU (mlgate.resnet: Pillow-exact resize, HIP stem, MFMA bottlenecks, GAP, zero-pad).
-    SALAD's native branch (DINOv2 + Sinkhorn aggregation) is opt-in: mlgate.salad.
+    SALAD's native branch (DINOv2 + Sinkhorn aggregation) is opt-in: mlgate.salad;
+    so is MixVPR's (cropped ResNet-50 + feature mixer at 320^2): mlgate.mixvpr.
 
 Weights: the hub checkpoint cannot be fetched offline.  ``pretrained_path`` (or
 MLGATE_DINOV2_WEIGHTS) may point at a local hub-format dinov2_vitb14 state_dict;
@@ -247,10 +248,43 @@ class _ResNetFallback(BasePlaceRecognition):
 
 
 class MixVPR(_ResNetFallback):
+    """place_recognition.py:209-332.  By default what the reference executes: the ``mixvpr``
+    package does not import, so the ResNet-50 GAP fallback runs (:241-306).
+    ``MLGATE_MIXVPR_NATIVE=1`` (or ``.native = True``) selects the model its native branch
+    names (:227-239): MixVPRModel(backbone='resnet50', out_dim=4096), the cropped ResNet-50
+    + feature-mixer head at 320 x 320 on the GPU (mlgate.mixvpr, csrc/mixvpr.hip); weights
+    from ``pretrained_path`` / MLGATE_MIXVPR_WEIGHTS, else seeded synthetic ones."""
+
     def __init__(self, backbone: str = 'resnet50', descriptor_dim: int = 4096, device: str = 'cuda',
                  pretrained_path: Optional[str] = None):
         super().__init__(descriptor_dim, device, pretrained_path)
         self.backbone_name = backbone
+        self.native = None  # None: MLGATE_MIXVPR_NATIVE decides; True / False force it
+        self._mix = None
+
+    def _load_model(self):
+        if self._model_loaded:
+            return
+        native = self.native if self.native is not None else os.environ.get("MLGATE_MIXVPR_NATIVE") == "1"
+        if not native:
+            return super()._load_model()
+        from .mixvpr import DESC_DIM, MixVprGPU
+        if self.backbone_name != 'resnet50':
+            raise ValueError(f"native MixVPR: only the resnet50 backbone has MI355X kernels, not {self.backbone_name}")
+        if self.descriptor_dim != DESC_DIM:
+            raise ValueError(f"native MixVPR produces {DESC_DIM}-dim descriptors, not {self.descriptor_dim}")
+        self._mix = MixVprGPU(device=self.device, pretrained_path=self.pretrained_path)
+        if self._mix.weights_source.startswith("synthetic"):
+            warnings.warn("MixVPR weights not configured (pretrained_path / MLGATE_MIXVPR_WEIGHTS); using seeded "
+                          "synthetic weights")
+        self._model_loaded = True
+        self._is_fallback = False
+
+    def extract_descriptors(self, images) -> np.ndarray:
+        self._load_model()
+        if self._mix is None:
+            return super().extract_descriptors(images)
+        return self._mix.forward(_device_frames(images, self._mix.device)).cpu().numpy()
 
 
 class SALAD(_ResNetFallback):

@@ -623,3 +623,73 @@ def resolve_salad_state_dict(path=None, seed=0):
     if path:
         return load_salad_state_dict(path), path
     return salad_state_dict(seed), f"synthetic(seed={seed})"
+
+
+# ----------------------------------------------------------------- MixVPR
+# amaralibey/MixVPR VPRModel state dict (MixVPR's native branch, place_recognition.py:
+# 227-239): MixVPRModel(backbone='resnet50', out_dim=4096) -- torchvision resnet50 cropped
+# after layer3 under ``backbone.model.`` and the feature-mixer aggregator (in_channels 1024,
+# 20 x 20 positions, mix_depth 4, mlp_ratio 1, out_channels 1024, out_rows 4).
+MIXVPR_HW, MIXVPR_CHANNELS, MIXVPR_DEPTH, MIXVPR_ROWS = 400, 1024, 4, 4
+MIXVPR_STAGES = RESNET_STAGES[:3]
+
+
+def mixvpr_aggregator_shapes():
+    hw, c = MIXVPR_HW, MIXVPR_CHANNELS
+    shapes = {}
+    for i in range(MIXVPR_DEPTH):
+        p = f"mix.{i}.mix."
+        shapes.update({p + "0.weight": (hw,), p + "0.bias": (hw,),          # LayerNorm(400)
+                       p + "1.weight": (hw, hw), p + "1.bias": (hw,),       # Linear(400, 400), then ReLU
+                       p + "3.weight": (hw, hw), p + "3.bias": (hw,)})      # Linear(400, 400)
+    shapes.update({"channel_proj.weight": (c, c), "channel_proj.bias": (c,),
+                   "row_proj.weight": (MIXVPR_ROWS, hw), "row_proj.bias": (MIXVPR_ROWS,)})
+    return shapes
+
+
+def mixvpr_keys():
+    trunk = [k for k in resnet50_keys() if not k.startswith("layer4.")]
+    return ["backbone.model." + k for k in trunk] + ["aggregator." + k for k in mixvpr_aggregator_shapes()]
+
+
+def mixvpr_state_dict(seed=0):
+    """Seeded float32 weights with the checkpoint's key names and shapes.  The trunk is
+    ``resnet50_state_dict``'s layers 1-3.  The aggregator is NOT drawn as upstream
+    initialises it (std 0.02, zero biases: the mixer would be almost an identity and a test
+    on it would prove little): Linear weights at std 1 / sqrt(fan_in), biases at std 0.1 (0.3
+    for the two projections), LayerNorm weight 1 + 0.3 N(0, 1) and bias 0.3 N(0, 1), so every
+    tensor moves the descriptor (tests/test_mixvpr_cpu.py measures each)."""
+    rn = resnet50_state_dict(seed)
+    sd = {"backbone.model." + k: v for k, v in rn.items() if not k.startswith("layer4.")}
+    rng = np.random.default_rng(seed + 11)
+    for k, shp in mixvpr_aggregator_shapes().items():
+        norm = ".mix.0." in k
+        if k.endswith("bias"):
+            std = 0.3 if (norm or "_proj" in k) else 0.1
+            v = rng.standard_normal(shp, dtype=np.float32) * np.float32(std)
+        elif norm:
+            v = np.float32(1.0) + rng.standard_normal(shp, dtype=np.float32) * np.float32(0.3)
+        else:
+            v = rng.standard_normal(shp, dtype=np.float32) * np.float32(1.0 / np.sqrt(shp[1]))
+        sd["aggregator." + k] = v
+    return sd
+
+
+def load_mixvpr_state_dict(path):
+    """amaralibey/MixVPR checkpoint (a Lightning file: the state dict bare or under
+    'state_dict') from a local file, weights only; layer4 / fc keys are ignored."""
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
+        sd = sd["state_dict"]
+    missing = [k for k in mixvpr_keys() if k not in sd]
+    if missing:
+        raise KeyError(f"checkpoint {path} lacks MixVPR keys, e.g. {missing[:3]}")
+    return {k: sd[k].float().cpu().numpy() for k in mixvpr_keys()}
+
+
+def resolve_mixvpr_state_dict(path=None, seed=0):
+    path = path or os.environ.get("MLGATE_MIXVPR_WEIGHTS")
+    if path:
+        return load_mixvpr_state_dict(path), path
+    return mixvpr_state_dict(seed), f"synthetic(seed={seed})"
