@@ -217,6 +217,15 @@ int mlg_op_gemm_bias_gelu(const uint16_t* A, const uint16_t* W, const float* bia
                           int K, void* stream);
 int mlg_op_gemm_residual(const uint16_t* A, const uint16_t* W, const float* bias, const float* gamma, float* X,
                          int M, int N, int K, void* stream);
+/* The split-bf16 GEMM of the ViT's precise path (test access; no product path calls these):
+ * A rows [A_hi | A_lo] of K0 bf16 each (M x 2 K0), W rows [W_hi | W_lo] (N x 2 K0), the
+ * product A_hi W_hi^T + A_lo W_hi^T + A_hi W_lo^T in f32; K0 % 64 == 0, N % 256 == 0.
+ * residual: X (M x N f32) += gamma * (product + bias).  bias_gelu: C (M x 2 N bf16) =
+ * [hi | lo] of gelu(product + bias), hi = bf16(y), lo = bf16(y - hi). */
+int mlg_op_gemm_residual_split(const uint16_t* A, const uint16_t* W, const float* bias, const float* gamma, float* X,
+                               int M, int N, int K0, void* stream);
+int mlg_op_gemm_bias_gelu_split(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* C, int M, int N,
+                                int K0, void* stream);
 int mlg_op_layernorm_bf16(const float* X, const float* g, const float* b, uint16_t* Y, int M, void* stream);
 /* ViT attention (hub Attention.forward, 12 heads x 64) on the pipelined tile: Q, K bf16
  * [12][B * Tpad][64], Vt bf16 [12][B * Tpad / 64][64 d][64 keys] (keys >= T finite), O bf16

@@ -576,6 +576,14 @@ int mlg_op_gemm_residual(const uint16_t* A, const uint16_t* W, const float* bias
                          int M, int N, int K, void* stream) {
     return mlg_gemm_residual(A, W, bias, gamma, X, M, N, K, (hipStream_t)stream);
 }
+int mlg_op_gemm_residual_split(const uint16_t* A, const uint16_t* W, const float* bias, const float* gamma, float* X,
+                               int M, int N, int K0, void* stream) {
+    return mlg_gemm_residual_split(A, W, bias, gamma, X, M, N, K0, (hipStream_t)stream);
+}
+int mlg_op_gemm_bias_gelu_split(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* C, int M, int N,
+                                int K0, void* stream) {
+    return mlg_gemm_bias_gelu_split(A, W, bias, C, M, N, K0, (hipStream_t)stream);
+}
 int mlg_op_layernorm_bf16(const float* X, const float* g, const float* b, uint16_t* Y, int M, void* stream) {
     return mlg_layernorm_bf16(X, g, b, Y, M, (hipStream_t)stream);
 }

@@ -912,10 +912,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const bf16_t* __restrict__ A
 // accumulation.  A rows are [A_hi | A_lo] (K0 each, lda >= 2 K0), W rows [W_hi | W_lo]
 // (ldw >= 2 K0).  The persistent, XCD-local 256 x 256 tile of k_gemm256 with K-steps of
 // 32: one LDS stage holds the four 256 x 32 planes of a K-step (64 KiB, two stages), each
-// wave reads its W_hi / W_lo / A_hi fragments, issues the hi*hi and lo*hi MFMAs, then
-// reloads its A fragments as A_lo for the hi*lo MFMAs -- 96 MFMAs per 24 fragment reads
-// per wave and K-step, and every operand byte fetched once (a K-concatenated [hi|lo|hi]
-// GEMM re-reads A_hi and W_hi: 3 planes each instead of 2).
+// wave reads its W_hi / W_lo fragments once per K-step and its A_hi / A_lo fragments two
+// accumulator columns at a time, in four phases of 24 MFMAs (hi*hi, lo*hi, hi*lo) -- 96
+// MFMAs per 24 fragment reads per wave and K-step, and every operand byte fetched once (a
+// K-concatenated [hi|lo|hi] GEMM re-reads A_hi and W_hi: 3 planes each instead of 2).  The
+// phased loop, its counted waits and the tile hand-over are derived at the loop.
 // Epi::STAGED (k_gemm256s): 1 = a bf16 hi / lo pair per element written from an LDS image
 // as whole rows (stage2 / put), 2 = an f32 row update (stage4 / load4 / put4), 0 = none
 template <class E, class = void>
@@ -932,10 +933,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
     constexpr int BK = 32, TM = 256, TN = 256;
     constexpr int PLANE = TM * BK * 2;  // 16 KiB: one 256 x 32 bf16 operand plane
     constexpr int STAGE = 4 * PLANE;    // A_hi, A_lo, W_hi, W_lo
-    __shared__ __attribute__((aligned(16))) char st0[STAGE];
-    __shared__ __attribute__((aligned(16))) char st1[STAGE];
     constexpr int STG = staged_of<Epi>::value;
-    __shared__ size_t skey[STG == 1 ? 8 : 1][32];  // staged form: the pass's row keys per wave
+    // ONE __shared__ object for both stages and the row keys: a second object beside an
+    // LDS-DMA staging array can make hipcc drain vmcnt(0) before the fragment reads
+    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE + (STG == 1 ? 8 * 32 * sizeof(size_t) : 0)];
+    char* const st1 = lds + STAGE;  // K-steps 1, 3, ..; the staged epilogues' image
+    size_t (*const skey)[32] = reinterpret_cast<size_t (*)[32]>(lds + 2 * STAGE);  // staged form: row keys per wave
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // nb > 1 (staged-f32 epilogues only): nb independent products of one shape in one
     // persistent launch, problem z at A + z sA, W + z sW, its output rows z M + m (the
@@ -947,86 +950,185 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
     const DmaLane<BK> dl(lane);  // 16 rows x 4 chunks of 16 B per DMA wave-instruction
     const int wm = wave & 1, wn = wave >> 1;
     const int nk = K0 / BK;  // even (checked by the launcher)
-    const int drow = 2 * wave * 1024;  // this wave's 32 rows of every plane
-    // (this kernel sits at 256 VGPRs: the B offsets through lane_offsets spill 4 B more)
+    // What a wave stages (wave-uniform, in SGPRs).  A DMA wave-instruction fills one row
+    // group: 16 rows of one plane, 1 KiB.
+    //   W: row groups 2 wave, 2 wave + 1 of W_hi and of W_lo (4 per K-step);
+    //   A: per phase slice q = 0..3 (the rows the phase-q MFMAs read: row groups 2q, 2q + 1
+    //      and 8 + 2q, 8 + 2q + 1 of both planes, 8 wave-instructions) one row group:
+    //      plane wave & 1, row group 2q + agrp (4 per K-step).
+    const int uw = __builtin_amdgcn_readfirstlane(wave);
+    const int grp = uw >> 2;                           // barrier stagger group (below)
+    const int apl = uw & 1;                            // A plane: hi / lo
+    const int agrp = ((uw >> 1) & 1) + 8 * (uw >> 2);  // + 2q: row group of slice q
+    const unsigned lbase = lds_addr(lds);
+    const unsigned dw = lbase + 2 * PLANE + 2 * uw * 1024;            // + stage + i KiB (+ PLANE: W_lo)
+    const unsigned da = lbase + apl * PLANE + agrp * 1024;            // + stage + 2q KiB
     unsigned ob[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = dl.row(2 * wave + i);
         ob[i] = (unsigned)(row * ldw + dl.chunk(row)) * 2u;
     }
-    auto a_offsets = [&](int t, unsigned (&o)[2]) { lane_offsets(dl, wave, lda, ((t % nMN) / nN) * TM, M, o); };
-    auto a_base = [&](int t) { return A + (t / nMN) * sA + (size_t)(((t % nMN) / nN) * TM) * lda; };
+    // A offsets: the lane's tile row in slice q is arow + 32 q (the same chunk: 32 rows on,
+    // the swizzle repeats), clamped to the tile's last row inside M (rmax, wave-uniform; 255
+    // but for the ragged last M-tile).  Computed at the issue, two VALU a DMA: as per-tile
+    // tables of four they were twelve VGPRs in the loop and four across the epilogue, which
+    // has none to spare.
+    const int arow = dl.row(((wave >> 1) & 1) + 8 * (wave >> 2));
+    const unsigned ach = (unsigned)dl.chunk(arow) * 2u;
+    auto a_rmax = [&](int t) { return M - 1 - ((t % nMN) / nN) * TM; };
+    // tile bases: A at this wave's plane
+    auto a_base = [&](int t) { return A + (t / nMN) * sA + (size_t)(((t % nMN) / nN) * TM) * lda + apl * K0; };
     auto b_base = [&](int t) { return W + (t / nMN) * sW + (size_t)((t % nN) * TN) * ldw; };
-    unsigned oa[2];
     const bf16_t* sa = a_base(walk.tile);
     const bf16_t* sb = b_base(walk.tile);
-    a_offsets(walk.tile, oa);
-#define S256_DMA(ST, OA, SA, SB, t)                                                                        \
+    int rm = a_rmax(walk.tile);
+    // Fragment reads: the lane's byte offset of its row 0 fragment in a plane, per stage
+    // (16 rows on is + 1 KiB, the swizzle repeats).  Stage 1's is its own register, hidden
+    // from constant folding: folded onto stage 0's its reads' offsets pass the 64 KiB of the
+    // ds_read offset field and hipcc keeps one address VGPR for each of the 24.
+    unsigned fa[2], fw[2];
+    fa[0] = soff<BK>(wm * 128 + (lane & 15), lane >> 4);
+    fw[0] = soff<BK>(wn * 64 + (lane & 15), lane >> 4);
+    fa[1] = fa[0] + STAGE;
+    fw[1] = fw[0] + STAGE;
+    asm volatile("" : "+v"(fa[1]), "+v"(fw[1]));
+    // DMA pieces into the stage at byte offset ST (0 / STAGE); PA / PB are the tile bases
+    // advanced to the K-step.  W row group i, both planes; A slice q.
+#define S256_DMA_W(ST, PB, i)                                                                              \
     {                                                                                                      \
-        const unsigned b_ = lds_addr(ST) + drow;                                                           \
-        const bf16_t* ah_ = (SA) + (t) * BK;                                                               \
-        const bf16_t* wh_ = (SB) + (t) * BK;                                                               \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                    \
-            dma16s((OA)[i], ah_, b_ + i * 1024);                                                           \
-            dma16s((OA)[i], ah_ + K0, b_ + PLANE + i * 1024);                                              \
-            dma16s(ob[i], wh_, b_ + 2 * PLANE + i * 1024);                                                 \
-            dma16s(ob[i], wh_ + K0, b_ + 3 * PLANE + i * 1024);                                            \
-        }                                                                                                  \
+        dma16s(ob[i], (PB), dw + (ST) + (i) * 1024);                                                       \
+        dma16s(ob[i], (PB) + K0, dw + (ST) + PLANE + (i) * 1024);                                          \
     }
-    // the three products of a K-step: hi * hi and lo * hi on the A_hi fragments, then the
-    // A fragments reloaded as A_lo for hi * lo
-#define S256_COMPUTE(ST)                                                                                   \
+#define S256_DMA_A(ST, RM, PA, q) \
+    dma16s((unsigned)(min(arow + 32 * (q), (RM)) * lda) * 2u + ach, (PA), da + (ST) + (q) * 2048)
+    // never 0 inside the loop: the derivation of the 8 is at the loop
+#define S256_VMCNT8 asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
+    // One phase of a K-step in stage ST: the fragment reads of slice p (phase 0: also the
+    // K-step's W_hi / W_lo fragments, held for its four phases), this phase's slice of the
+    // prefetch and its counted wait (the trailing statements), then between two barriers
+    // the 24 MFMAs on accumulator columns 2p, 2p + 1: per accumulator hi * hi, lo * hi,
+    // hi * lo as ever, the three products as three sweeps so that dependent MFMAs are
+    // eight issues apart.
+#define S256_PHASE(ST, p, ...)                                                                             \
     {                                                                                                      \
-        bf16x8 af[8], wh[4], wl[4];                                                                        \
-        const int ch = lane >> 4;                                                                          \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
-            const int row = wn * 64 + i * 16 + (lane & 15);                                                \
-            wh[i] = frag<BK>((ST) + 2 * PLANE, row, ch);                                                   \
-            wl[i] = frag<BK>((ST) + 3 * PLANE, row, ch);                                                   \
+        bf16x8 ah[2], al[2];                                                                               \
+        if ((p) == 0) {                                                                                    \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
+                wh[i] = *reinterpret_cast<const bf16x8*>(lds + fw[(ST) / STAGE] + 2 * PLANE + i * 1024);   \
+                wl[i] = *reinterpret_cast<const bf16x8*>(lds + fw[(ST) / STAGE] + 3 * PLANE + i * 1024);   \
+            }                                                                                              \
         }                                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                      \
-            af[j] = frag<BK>((ST), wm * 128 + j * 16 + (lane & 15), ch);                                   \
-        __builtin_amdgcn_s_setprio(1);                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i) {      \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], af[j], acc[i][j], 0, 0, 0);         \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                                 \
+            ah[jj] = *reinterpret_cast<const bf16x8*>(lds + fa[(ST) / STAGE] + (2 * (p) + jj) * 1024);     \
+            al[jj] = *reinterpret_cast<const bf16x8*>(lds + fa[(ST) / STAGE] + PLANE + (2 * (p) + jj) * 1024); \
         }                                                                                                  \
-        __builtin_amdgcn_s_setprio(0);                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                      \
-            af[j] = frag<BK>((ST) + PLANE, wm * 128 + j * 16 + (lane & 15), ch);                           \
+        __VA_ARGS__                                                                                        \
+        __builtin_amdgcn_s_barrier();                                                                      \
+        __builtin_amdgcn_s_waitcnt(0xc07f); /* lgkmcnt(0) */                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
         __builtin_amdgcn_s_setprio(1);                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) _Pragma("unroll") for (int i = 0; i < 4; ++i)        \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], af[j], acc[i][j], 0, 0, 0);         \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) _Pragma("unroll") for (int i = 0; i < 4; ++i)     \
+            acc[i][2 * (p) + jj] =                                                                         \
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], ah[jj], acc[i][2 * (p) + jj], 0, 0, 0);     \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) _Pragma("unroll") for (int i = 0; i < 4; ++i)     \
+            acc[i][2 * (p) + jj] =                                                                         \
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], ah[jj], acc[i][2 * (p) + jj], 0, 0, 0);     \
+        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) _Pragma("unroll") for (int i = 0; i < 4; ++i)     \
+            acc[i][2 * (p) + jj] =                                                                         \
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], al[jj], acc[i][2 * (p) + jj], 0, 0, 0);     \
         __builtin_amdgcn_s_setprio(0);                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        __builtin_amdgcn_s_barrier();                                                                      \
     }
 
-    S256_DMA(st0, oa, sa, sb, 0);
-    __builtin_amdgcn_s_waitcnt(0xF70);
-    __builtin_amdgcn_s_barrier();
+    // The phased K loop.  K-step u lives in stage u & 1 and runs as four phases (u, p); the
+    // K-steps of a workgroup's successive tiles form one stream (K-step nk of a tile is
+    // K-step 0 of its next tile).  A phase is {reads, DMA slice, [wait]} barrier {lgkmcnt(0),
+    // 24 MFMAs} barrier.  Waves 4-7 (grp 1; they share SIMDs with waves 0-3) pass one extra
+    // barrier before the loop and waves 0-3 one after it, so one group's reads and DMA
+    // issue run beside the other's MFMA cluster.  Barriers cut time into intervals that all
+    // waves share; with I = 8u + 2p + grp, a wave issues the reads / DMAs / wait of (u, p)
+    // in interval I and its MFMAs in I + 1, after the lgkmcnt(0) that retires the reads.
+    //
+    // What a wave issues, in order (8 wave-DMAs per K-step as before, 1 + 1 + 3 + 3):
+    //   (u, 0): A_2(u + 1)           (u, 2): W rg 0 hi, lo (u + 2), A_0(u + 2)
+    //   (u, 1): A_3(u + 1), wait B   (u, 3): W rg 1 hi, lo (u + 2), A_1(u + 2), wait A
+    // so K-step v is issued during phases (v - 2, 2) .. (v - 1, 1): 1.25 - 1.5 K-steps
+    // before its first read (the two-stage loop before this one issued it one K-step
+    // ahead and drained to vmcnt(0) every K-step).
+    //
+    // Restage (WAR).  A region's last reads are issued by grp 1 in interval J and retired by
+    // that wave's lgkmcnt(0) in J + 1, before the barrier that closes J + 1; a DMA into it
+    // may be issued from J + 2 on (one phase after the reading phase).  Stage u & 1:
+    //   W(u) is read in (u, 0), J = 8u + 1: free from 8u + 3; W(u + 2) is issued in (u, 2),
+    //     (u, 3), at 8u + 4 at the earliest.
+    //   A_q(u) is read in (u, q), J = 8u + 2q + 1: free from 8u + 2q + 3.  A_0(u + 2) goes
+    //     out in (u, 2) >= 8u + 4 (free 8u + 3), A_1(u + 2) in (u, 3) >= 8u + 6 (8u + 5),
+    //     A_2(u + 2) in (u + 1, 0) >= 8u + 8 (8u + 7), A_3(u + 2) in (u + 1, 1) >= 8u + 10
+    //     (8u + 9).
+    // Read (RAW).  LDS-DMA data is ordered for a ds_read only by the issuing wave's vmcnt
+    // followed by a barrier that the reader passes before it reads: a wait in interval
+    // <= J - 1 for a first read in J.
+    //   wait A in (v - 1, 3), intervals 8v - 2, 8v - 1, retires W(v), A_0(v), A_1(v): first
+    //     read by grp 0 in (v, 0) = 8v.  Issued after them, in order: A_2(v), A_3(v),
+    //     3 + 3 of K-step v + 1 -> vmcnt(8).
+    //   wait B in (v, 1), intervals 8v + 2, 8v + 3, retires A_2(v), A_3(v): first read in
+    //     (v, 2) = 8v + 4.  Issued after them: 3 + 3 of v + 1, A_2(v + 1), A_3(v + 1) ->
+    //     vmcnt(8).
+    // Prologue.  K-step 0's eight DMAs (W x 4, A_0 .. A_3), then at the top of every tile
+    // the six of K-step 1 that (-1, 2), (-1, 3) would have issued, vmcnt(8) -- wait A for
+    // K-step 0: behind W(0), A_0(0), A_1(0) are A_2(0), A_3(0) and these six -- and a
+    // barrier; the stream then stands as in steady state before (0, 0).
+    // Hand-over and drain.  The last K-step pair of a tile prefetches the whole K-step 0 of
+    // the next tile into stage 0 by the same schedule and the same counts (no next tile:
+    // a re-read of this tile's K-step 0, so the counts hold).  The six DMAs of the next
+    // tile's K-step 1 that (nk - 1, 2), (nk - 1, 3) would issue into stage 1 are held
+    // back with their wait A: they are the tile-top six above, issued after the epilogue.
+    // So from the barrier that closes the loop (every wave's reads of stage 1 retired) to
+    // the epilogue's closing barrier no DMA in flight or yet to be issued targets stage 1,
+    // and the staged epilogues keep it as their image; in flight there are the eight
+    // DMAs of the next tile's K-step 0, all into stage 0, which nobody reads or writes
+    // until the next (0, 0).  The tile-top vmcnt(8) then is K-step 0's wait A as in the
+    // prologue.  nk = 2: the prologue's stream runs straight into the drain; the counts
+    // above do not depend on nk.
+    S256_DMA_W(0, sb, 0)
+    S256_DMA_W(0, sb, 1)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) S256_DMA_A(0, rm, sa, q);
     for (; walk.tile < walk.end; walk.tile += walk.step) {
         const int tile = walk.tile, next = walk.next(tile);
-        unsigned na[2];
-        a_offsets(next, na);
-        const bf16_t* nsa = a_base(next);
+        const int nrm = a_rmax(next);
+        const bf16_t* nsa = a_base(next);  // no next tile: next == tile
         const bf16_t* nsb = b_base(next);
-        const int kn = next != tile ? 0 : nk - 1;  // no next tile: harmless re-read
+        S256_DMA_W(STAGE, sb + BK, 0)
+        S256_DMA_W(STAGE, sb + BK, 1)
+        S256_DMA_A(STAGE, rm, sa + BK, 0);
+        S256_DMA_A(STAGE, rm, sa + BK, 1);
+        S256_VMCNT8;
+        __builtin_amdgcn_s_barrier();
+        if (grp) __builtin_amdgcn_s_barrier();
         f32x4 acc[4][8];
         zero_acc(acc);
         for (int t = 0; t < nk; t += 2) {
-            S256_DMA(st1, oa, sa, sb, t + 1);
-            S256_COMPUTE(st0);
-            __builtin_amdgcn_s_waitcnt(0xF70);
-            __builtin_amdgcn_s_barrier();
-            if (t + 2 < nk) {
-                S256_DMA(st0, oa, sa, sb, t + 2);
-            } else {
-                S256_DMA(st0, na, nsa, nsb, kn);  // K-step 0 of the next output tile
-            }
-            S256_COMPUTE(st1);
-            __builtin_amdgcn_s_waitcnt(0xF70);
-            __builtin_amdgcn_s_barrier();
+            const bool more = t + 2 < nk;  // else: K-step t + 2 is the next tile's K-step 0
+            const bf16_t* a1 = sa + (t + 1) * BK;
+            const bf16_t* a2 = more ? sa + (t + 2) * BK : nsa;
+            const bf16_t* b2 = more ? sb + (t + 2) * BK : nsb;
+            const bf16_t* a3 = sa + (t + 3) * BK;  // used if (more)
+            const bf16_t* b3 = sb + (t + 3) * BK;
+            const int r2 = more ? rm : nrm;
+            bf16x8 wh[4], wl[4];
+            S256_PHASE(0, 0, S256_DMA_A(STAGE, rm, a1, 2);)
+            S256_PHASE(0, 1, S256_DMA_A(STAGE, rm, a1, 3); S256_VMCNT8;)
+            S256_PHASE(0, 2, S256_DMA_W(0, b2, 0) S256_DMA_A(0, r2, a2, 0);)
+            S256_PHASE(0, 3, S256_DMA_W(0, b2, 1) S256_DMA_A(0, r2, a2, 1); S256_VMCNT8;)
+            S256_PHASE(STAGE, 0, S256_DMA_A(0, r2, a2, 2);)
+            S256_PHASE(STAGE, 1, S256_DMA_A(0, r2, a2, 3); S256_VMCNT8;)
+            S256_PHASE(STAGE, 2, if (more) { S256_DMA_W(STAGE, b3, 0) S256_DMA_A(STAGE, rm, a3, 0); })
+            S256_PHASE(STAGE, 3, if (more) { S256_DMA_W(STAGE, b3, 1) S256_DMA_A(STAGE, rm, a3, 1); S256_VMCNT8; })
         }
+        if (!grp) __builtin_amdgcn_s_barrier();
         const int tz = tile / nMN, lt = tile - tz * nMN, mz = tz * M;
         const int mt = lt / nN, m0 = mt * TM, n0 = (lt - mt * nN) * TN;
         // batched epilogue: every column's (bias, ...) and every row's index data first, then
@@ -1158,14 +1260,21 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
             if (m0 + TM <= M) epilogue(std::false_type{});
             else epilogue(std::true_type{});
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) oa[i] = na[i];
+        rm = nrm;
         sa = nsa;
         sb = nsb;
+        // The epilogue's own loads and stores have drained the VM queue already (hipcc waits
+        // vmcnt(0) for them, and the eight DMAs of the next K-step 0 are older).  Saying so
+        // here keeps hipcc from putting that wait behind the tile-top DMAs instead, where
+        // it would be a full round trip (an epilogue load whose result a ragged row drops
+        // stays pending for it until its register is written again).
+        __builtin_amdgcn_s_waitcnt(0xF70);
     }
-    __builtin_amdgcn_s_waitcnt(0xF70);
-#undef S256_COMPUTE
-#undef S256_DMA
+    __builtin_amdgcn_s_waitcnt(0xF70);  // vmcnt(0): the last tile's re-read prefetch
+#undef S256_PHASE
+#undef S256_VMCNT8
+#undef S256_DMA_A
+#undef S256_DMA_W
 }
 
 // Variant 5: the 256 x 256 persistent tile of k_gemm256 with K-tiles of 32 in a 4-deep
