@@ -34,7 +34,7 @@ extern "C" {
 #define MLG_VIT_EMBED 768
 #define MLG_VIT_PATCH_K 768 /* 3*14*14 = 588 patch inputs, zero-padded to 12 K-tiles of 64 */
 
-/* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_salad_weights,
+/* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_salad_weights, mlg_vlad_vocab,
  * mlg_rn_weights, mlg_mixvpr_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
  * mlg_orb_params) begins with a head: struct_size = sizeof(the struct) and abi_version =
  * MLG_ABI_VERSION, both set by initialising it with MLG_STRUCT_INIT(type).  A struct whose
@@ -148,6 +148,48 @@ size_t mlg_salad_workspace_bytes(int batch, int image_size);
 int mlg_salad_forward(const mlg_vit_weights* w, const mlg_salad_weights* sw, const uint8_t* frames, int batch,
                       int H, int W, int C, long frame_stride, int image_size, void* workspace,
                       size_t workspace_bytes, float* desc_out, void* stream);
+
+/* ------------------------------------------------------------------ AnyLoc --
+ * AnyLoc's native branch: the descriptor its class declares (place_recognition.py:413-505,
+ * "DINOv2 + VLAD aggregation", num_clusters 64 x 768 = 49152) and never builds (:484-485
+ * mean-pools).  Hard-assignment VLAD as upstream AnyLoc's VLAD(norm_descs=True,
+ * vlad_mode='hard', intra_norm=True), per frame over tokens x_i (i < P) and stored centres
+ * c_k (k < K):
+ *   x^_i = x_i / max(|x_i|, 1e-12);  a_i = argmax_k x^_i . c_k / max(|c_k|, 1e-12), ties to
+ *   the lowest k;  V_k = sum_{a_i = k} (x^_i - c_k) (the stored centre; an empty cluster
+ *   gives zeros);  V_k /= max(|V_k|, 1e-12);  flatten k-major;  divide by max(|.|, 1e-12).
+ * The assignment runs on the exact-f32 MFMA; every sum has a fixed order and there are no
+ * floating-point atomics, so a frame's descriptor does not depend on the batch around it. */
+#define MLG_VLAD_MAX_CLUSTERS 128
+typedef struct mlg_vlad_vocab {
+    uint32_t struct_size, abi_version; /* MLG_STRUCT_INIT(mlg_vlad_vocab) */
+    const float* centers;              /* device f32 [num_clusters][768], 16-byte aligned */
+    int num_clusters;                  /* a multiple of 16 in 16 .. MLG_VLAD_MAX_CLUSTERS */
+} mlg_vlad_vocab;
+/* 0 for arguments outside the supported range (B in 1 .. 65535, P >= 1, K as above).  The
+ * entry points below return MLG_EINVAL for a foreign struct head (before anything else is
+ * read), such arguments, null or misaligned (16 bytes) pointers and a short workspace. */
+size_t mlg_vlad_workspace_bytes(int B, int P, int K);
+/* tokens: device f32 [B, P, 768] -> desc: device f32 [B, K * 768], unit rows; labels
+ * (optional): device int32 [B, P], the assignments a_i. */
+int mlg_op_vlad(const mlg_vlad_vocab* vocab, const float* tokens, int B, int P, void* workspace,
+                size_t workspace_bytes, float* desc, int32_t* labels_or_null, void* stream);
+size_t mlg_anyloc_workspace_bytes(int B, int image_size, int K);
+/* mlg_vit_forward's trunk and final norm at image_size (AnyLoc: 518, flags MLG_VIT_KEEP_CHANNELS
+ * | MLG_VIT_SPLIT; MLG_VIT_POOL_MEAN is implied) with the patch tokens local_out would
+ * receive kept in the workspace, then the VLAD head over them: desc f32 [B, K * 768]. */
+int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, const uint8_t* frames, int B, int H,
+                       int W, int C, long frame_stride, int image_size, int flags, void* workspace,
+                       size_t workspace_bytes, float* desc, void* stream);
+/* One Lloyd iteration of the vocabulary fit (spherical k-means as AnyLoc fits it: cosine
+ * assignment, centres = means of the unit tokens).  tokens: device f32 [M, 768]; centers
+ * in-out [K, 768]; labels int32 [M]: in, the previous assignment (any values before the
+ * first step), out, a_i against the incoming centres; *changed (device): labels that
+ * moved; counts [K]: members per cluster.  An empty cluster keeps its centre.  The means
+ * are per-split partial sums in token order, summed in split order (f32). */
+size_t mlg_kmeans_workspace_bytes(long M, int K);
+int mlg_kmeans_step(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
+                    int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------- retrieval --
  * SemanticPlaceRecognition.find_loop_closures (place_recognition.py:851-911) for

@@ -258,6 +258,57 @@ int mlg_salad_forward(const mlg_vit_weights* w, const mlg_salad_weights* sw, con
     return MLG_OK;
 }
 
+size_t mlg_vlad_workspace_bytes(int B, int P, int K) { return mlg_vlad_ws_bytes(B, P, K); }
+
+int mlg_op_vlad(const mlg_vlad_vocab* vocab, const float* tokens, int B, int P, void* workspace,
+                size_t workspace_bytes, float* desc, int32_t* labels_or_null, void* stream) {
+    if (!mlg_head_ok(vocab, MLG_ABI_VERSION)) return MLG_EINVAL;
+    return mlg_vlad_run(vocab->centers, vocab->num_clusters, tokens, B, P, workspace, workspace_bytes, desc,
+                        labels_or_null, (hipStream_t)stream);
+}
+
+// the ViT buffers, then the patch tokens [B, P, 768] f32, the mean-pooled rows the final
+// norm kernel also writes (unused), then the VLAD head's workspace
+size_t mlg_anyloc_workspace_bytes(int B, int image_size, int K) {
+    const size_t vit = mlg_vit_workspace_bytes(B, image_size);
+    if (!vit || image_size < 2 * PATCH) return 0;
+    const VitGeom g(B, image_size);
+    const size_t head = mlg_vlad_ws_bytes(B, g.T - 2, K);
+    if (!head) return 0;
+    return vit + align_up((size_t)B * (g.T - 2) * 768 * 4) + align_up((size_t)B * 768 * 4) + head;
+}
+
+int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, const uint8_t* frames, int B, int H,
+                       int W, int C, long frame_stride, int image_size, int flags, void* workspace,
+                       size_t workspace_bytes, float* desc, void* stream) {
+    if (!mlg_head_ok(w, MLG_ABI_VERSION) || !mlg_head_ok(vocab, MLG_ABI_VERSION) || !frames || !workspace || !desc)
+        return MLG_EINVAL;
+    if (w->packing != ((flags & MLG_VIT_SPLIT) ? MLG_VIT_SPLIT : 0)) return MLG_EINVAL;
+    const size_t need = mlg_anyloc_workspace_bytes(B, image_size, vocab->num_clusters);
+    if (!need || workspace_bytes < need) return MLG_EINVAL;
+    const VitGeom g(B, image_size);
+    VitWorkspace ws;
+    char* p = (char*)workspace + carve(g, (char*)workspace, &ws);
+    float* tokens = (float*)p;
+    p += align_up((size_t)B * (g.T - 2) * 768 * 4);
+    float* pooled = (float*)p;
+    p += align_up((size_t)B * 768 * 4);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s,
+                  (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    TRY(mlg_final_norm_gem(ws.x, w->norm_w, w->norm_b, tokens, ws.partial, pooled, g.B, g.T, /*mean_pool=*/1, s));
+    return mlg_vlad_run(vocab->centers, vocab->num_clusters, tokens, B, g.T - 2, p,
+                        workspace_bytes - (size_t)(p - (char*)workspace), desc, nullptr, s);
+}
+
+size_t mlg_kmeans_workspace_bytes(long M, int K) { return mlg_kmeans_ws_bytes(M, K); }
+
+int mlg_kmeans_step(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
+                    int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    return mlg_kmeans_step_run(tokens, M, centers, K, labels, changed, counts, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
 size_t mlg_knn_workspace_bytes(int N, int D, int Q) {
     if (N <= 0 || D <= 0 || Q <= 0) return 0;
     return align_up((size_t)N * D * 4) + align_up((size_t)Q * D * 4) + align_up((size_t)Q * N * 4);

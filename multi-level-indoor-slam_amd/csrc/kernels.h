@@ -269,6 +269,16 @@ int mlg_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, lon
 // feat f32 [B, 400, 1024] (NHWC layer3 stream) -> desc f32 [B, 4096], L2-normalised
 int mlg_mixvpr_head(const mlg_mix_weights_i& w, const float* feat, int B, float* desc, hipStream_t s);
 
+// vlad.hip -- AnyLoc's native branch: hard-assignment VLAD over f32 tokens [B, P, 768] and
+// one Lloyd update of its vocabulary.  Both validate their arguments (MLG_EINVAL) and
+// return 0 bytes for an unsupported shape.  labels may be null for mlg_vlad_run.
+size_t mlg_vlad_ws_bytes(int B, int P, int K);
+int mlg_vlad_run(const float* centers, int K, const float* tokens, int B, int P, void* ws, size_t ws_bytes,
+                 float* desc, int32_t* labels, hipStream_t s);
+size_t mlg_kmeans_ws_bytes(long M, int K);
+int mlg_kmeans_step_run(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
+                        int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
+
 // plane.hip -- batched LiDAR ground-plane RANSAC
 size_t mlg_plane_ws_bytes(int S, int H);
 int mlg_plane_ransac_run(const float* pts, const int32_t* offs, int S, int H, uint64_t seed, double thr, void* ws,

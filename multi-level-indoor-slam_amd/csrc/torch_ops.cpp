@@ -729,6 +729,92 @@ Tensor mixvpr_preprocess(const Tensor& frames) {
     return out;
 }
 
+// ------------------------------------------------------------------ AnyLoc
+mlg_vlad_vocab vlad_vocab(const Tensor& centers) {
+    want(centers, at::kFloat, "centers");
+    TORCH_CHECK(centers.dim() == 2 && centers.size(1) == MLG_VIT_EMBED, "centers must be [K, 768]");
+    const int64_t K = centers.size(0);
+    TORCH_CHECK(K >= 16 && K <= MLG_VLAD_MAX_CLUSTERS && K % 16 == 0, "centers: K = ", K,
+                " is not a multiple of 16 in 16 .. ", MLG_VLAD_MAX_CLUSTERS);
+    mlg_vlad_vocab v = MLG_STRUCT_INIT(mlg_vlad_vocab);
+    v.centers = cp<float>(centers);
+    v.num_clusters = (int)K;
+    return v;
+}
+
+// tokens f32 [B, P, 768], centers f32 [K, 768] -> (desc f32 [B, K * 768], labels int32 [B, P])
+std::tuple<Tensor, Tensor> vlad(const Tensor& tokens, const Tensor& centers) {
+    want(tokens, at::kFloat, "tokens");
+    TORCH_CHECK(tokens.dim() == 3 && tokens.size(0) > 0 && tokens.size(1) > 0 && tokens.size(2) == MLG_VIT_EMBED,
+                "tokens must be [B, P, 768]");
+    const mlg_vlad_vocab v = vlad_vocab(centers);
+    TORCH_CHECK(centers.device() == tokens.device(), "centers and tokens must be on one device");
+    const int64_t B = tokens.size(0), P = tokens.size(1), K = centers.size(0);
+    c10::DeviceGuard g(tokens.device());
+    Tensor desc = at::empty({B, K * MLG_VIT_EMBED}, tokens.options());
+    Tensor labels = at::empty({B, P}, tokens.options().dtype(at::kInt));
+    const size_t nbytes = mlg_vlad_workspace_bytes((int)B, (int)P, (int)K);
+    TORCH_CHECK(nbytes > 0 && B * P < (1LL << 31), "vlad: unsupported shape");
+    Tensor ws = workspace(nbytes, tokens);
+    check_rc(mlg_op_vlad(&v, cp<float>(tokens), (int)B, (int)P, ws.data_ptr(), (size_t)ws.numel(), mp<float>(desc),
+                         mp<int32_t>(labels), stream_of(tokens)),
+             "mlg_op_vlad");
+    return {desc, labels};
+}
+
+// frames uint8 [B, H, W, C] -> desc f32 [B, K * 768]
+Tensor anyloc_forward(const Tensor& frames, at::TensorList w, const Tensor& centers, int64_t image_size,
+                      int64_t flags, int64_t max_batch) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    std::vector<Tensor> wv(w.begin(), w.end());
+    const mlg_vit_weights s = vit_weights(wv, (flags & MLG_VIT_SPLIT) != 0);
+    const mlg_vlad_vocab v = vlad_vocab(centers);
+    TORCH_CHECK(centers.device() == frames.device(), "centers and frames must be on one device");
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    const int64_t D = centers.size(0) * MLG_VIT_EMBED;
+    c10::DeviceGuard g(frames.device());
+    Tensor desc = at::empty({B, D}, frames.options().dtype(at::kFloat));
+    const int64_t nb_max = std::min(B, max_batch);
+    const size_t nbytes = mlg_anyloc_workspace_bytes((int)nb_max, (int)image_size, v.num_clusters);
+    TORCH_CHECK(nbytes > 0, "anyloc_forward: unsupported image_size / batch");
+    Tensor ws = workspace(nbytes, frames);
+    const long stride = (long)(H * W * C);
+    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
+        const int nb = (int)std::min(max_batch, B - b0);
+        check_rc(mlg_anyloc_forward(&s, &v, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
+                                    (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
+                                    mp<float>(desc) + b0 * D, stream_of(frames)),
+                 "mlg_anyloc_forward");
+    }
+    return desc;
+}
+
+// One Lloyd iteration: tokens f32 [M, 768]; centers f32 [K, 768] and labels int32 [M] are
+// updated in place -> (changed int64 [1], counts int32 [K])
+std::tuple<Tensor, Tensor> kmeans_step(const Tensor& tokens, const Tensor& centers, const Tensor& labels) {
+    want(tokens, at::kFloat, "tokens");
+    TORCH_CHECK(tokens.dim() == 2 && tokens.size(0) > 0 && tokens.size(1) == MLG_VIT_EMBED, "tokens must be [M, 768]");
+    const mlg_vlad_vocab v = vlad_vocab(centers);
+    want(labels, at::kInt, "labels");
+    TORCH_CHECK(labels.dim() == 1 && labels.size(0) == tokens.size(0), "labels must be [M]");
+    TORCH_CHECK(centers.device() == tokens.device() && labels.device() == tokens.device(),
+                "tokens, centers and labels must be on one device");
+    const int64_t M = tokens.size(0);
+    c10::DeviceGuard g(tokens.device());
+    Tensor changed = at::empty({1}, tokens.options().dtype(at::kLong));
+    Tensor counts = at::empty({v.num_clusters}, tokens.options().dtype(at::kInt));
+    const size_t nbytes = mlg_kmeans_workspace_bytes((long)M, v.num_clusters);
+    TORCH_CHECK(nbytes > 0, "kmeans_step: unsupported shape");
+    Tensor ws = workspace(nbytes, tokens);
+    check_rc(mlg_kmeans_step(cp<float>(tokens), (long)M, mp<float>(centers), v.num_clusters, mp<int32_t>(labels),
+                             mp<int64_t>(changed), mp<int32_t>(counts), ws.data_ptr(), (size_t)ws.numel(),
+                             stream_of(tokens)),
+             "mlg_kmeans_step");
+    return {changed, counts};
+}
+
 // ---------------------------------------------------- LiDAR plane RANSAC
 std::tuple<Tensor, Tensor, Tensor> plane_ransac(const Tensor& pts, const Tensor& offsets, int64_t iterations,
                                                 int64_t seed, double threshold) {
@@ -1000,6 +1086,9 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("mixvpr_forward(Tensor frames, Tensor[] trunk, Tensor[] head, int max_batch) -> Tensor");
     m.def("mixvpr_head(Tensor features, Tensor[] head) -> Tensor");
     m.def("mixvpr_preprocess(Tensor frames) -> Tensor");
+    m.def("vlad(Tensor tokens, Tensor centers) -> (Tensor, Tensor)");
+    m.def("anyloc_forward(Tensor frames, Tensor[] weights, Tensor centers, int image_size, int flags, int max_batch) -> Tensor");
+    m.def("kmeans_step(Tensor tokens, Tensor(a!) centers, Tensor(b!) labels) -> (Tensor, Tensor)");
     m.def("loftr_features(Tensor frames, Tensor[] weights) -> (Tensor, Tensor)");
     m.def("loftr_pack_tails(Tensor[] weights) -> Tensor");
     m.def("loftr_coarse_layer(Tensor(a!) x, Tensor(b!) cat, Tensor[] weights, int layer, int fused, int nseg, int L) -> ()");
@@ -1047,6 +1136,9 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("mixvpr_forward", &mixvpr_forward);
     m.impl("mixvpr_head", &mixvpr_head);
     m.impl("mixvpr_preprocess", &mixvpr_preprocess);
+    m.impl("vlad", &vlad);
+    m.impl("anyloc_forward", &anyloc_forward);
+    m.impl("kmeans_step", &kmeans_step);
     m.impl("loftr_features", &loftr_features);
     m.impl("loftr_pack_tails", &loftr_pack_tails);
     m.impl("loftr_coarse_layer", &loftr_coarse_layer);

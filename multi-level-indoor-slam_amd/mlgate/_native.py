@@ -19,7 +19,7 @@ TORCH_LIB_PATH = os.path.join(_HERE, "libmlgate_torch.so")
 OPS = ("vit_forward_into", "salad_forward", "knn_gate", "knn_query", "row_normalize", "similarity", "xcorr_score", "xcorr_batch",
        "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
-       "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess",
+       "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess", "vlad", "anyloc_forward", "kmeans_step",
        "prof_enable", "prof_reset", "prof_read")
 
 
@@ -71,6 +71,14 @@ EXPORTS = {
                                    c_void_p, c_void_p]),
     "mlg_op_mixvpr_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     "mlg_op_mixvpr_head": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mlg_vlad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mlg_op_vlad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mlg_anyloc_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mlg_anyloc_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_int,
+                                   c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mlg_kmeans_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "mlg_kmeans_step": (c_int, [c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
     "mlg_superpoint_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mlg_superpoint": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_float, c_int, c_int, c_int,
                                c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

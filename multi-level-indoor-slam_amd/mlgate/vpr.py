@@ -7,7 +7,8 @@ behaviour as the reference; the compute runs on the mlgate HIP kernels:
     keyframe feeds both the descriptor and the local-feature cache (the reference runs
     the same forward twice, place_recognition.py:765/777).
   * AnyLoc   -> the same ViT at 518^2 with mean pooling and unswapped channels
-    (place_recognition.py:467-505).
+    (place_recognition.py:467-505); opt-in (MLGATE_ANYLOC_NATIVE=1) the VLAD descriptor
+    the class declares, over the same tokens: mlgate.anyloc.
   * retrieval (find_loop_closures / query / pairwise similarities / cross-correlation
     rerank) -> mlg_knn_gate / mlg_knn_query / mlg_xcorr_score.
   * MixVPR / SALAD -> the reference resolves both to a torchvision ResNet-50 GAP
@@ -374,6 +375,86 @@ class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
         self.num_clusters = num_clusters
         self._model_loaded = False
         self._vit = None
+        self.native = None  # None: MLGATE_ANYLOC_NATIVE decides; True / False force it
+        self._anyloc = None
+        self._vocabulary = None
+
+    def _native_selected(self):
+        return self.native if self.native is not None else os.environ.get("MLGATE_ANYLOC_NATIVE") == "1"
+
+    def _check_native_dims(self):
+        from .weights import VLAD_CLUSTERS, VLAD_DIM
+        if self.num_clusters not in VLAD_CLUSTERS:
+            raise ValueError(f"native AnyLoc: num_clusters = {self.num_clusters} is not a multiple of 16 in 16..128 "
+                             f"(descriptor_dim = {self.descriptor_dim})")
+        if self.descriptor_dim != self.num_clusters * VLAD_DIM:
+            raise ValueError(f"native AnyLoc produces num_clusters x {VLAD_DIM} = {self.num_clusters * VLAD_DIM}-dim "
+                             f"descriptors (num_clusters = {self.num_clusters}), not {self.descriptor_dim}")
+
+    def _build_engine(self, vocabulary):
+        self._check_native_dims()
+        if self.backbone_name != 'dinov2_vitb14':
+            raise ValueError(f"{self.backbone_name}: only the dinov2_vitb14 backbone has MI355X kernels")
+        from .anyloc import AnyLocGPU
+        from .weights import resolve_state_dict
+        sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None))
+        if source.startswith('synthetic'):
+            warnings.warn("DINOv2 hub weights are not available offline; using seeded synthetic "
+                          "dinov2_vitb14 weights (set MLGATE_DINOV2_WEIGHTS to a local hub checkpoint for "
+                          "real descriptors).")
+        self.feat_dim = 768
+        self._model_loaded = True
+        return AnyLocGPU(sd, vocabulary, device=self.device, image_size=self._image_size)
+
+    def _native_engine(self):
+        """The AnyLocGPU engine when the native branch is selected, else None."""
+        if not self._native_selected():
+            return None
+        if self._anyloc is None:
+            self._check_native_dims()
+            vocab = self._vocabulary
+            if vocab is None:
+                from .weights import resolve_vocabulary
+                vocab, source = resolve_vocabulary(None, self.num_clusters)
+                if source.startswith('synthetic'):
+                    warnings.warn("AnyLoc vocabulary not configured (set_vocabulary / fit_vocabulary / "
+                                  "MLGATE_ANYLOC_VOCAB); using a seeded synthetic vocabulary")
+                self._vocabulary = vocab
+            self._anyloc = self._build_engine(vocab)
+        return self._anyloc
+
+    def set_vocabulary(self, centers):
+        """VLAD cluster centres [num_clusters, 768] for the native branch (mlgate extension)."""
+        from .weights import check_vocabulary
+        if hasattr(centers, 'detach'):
+            centers = centers.detach().float().cpu().numpy()
+        self._vocabulary = check_vocabulary(centers, self.num_clusters)
+        if self._anyloc is not None:
+            self._anyloc.set_vocabulary(self._vocabulary)
+
+    def fit_vocabulary(self, images, seed=0, max_iter=100):
+        """Fit the VLAD vocabulary on the tokens of ``images`` (k-means on the device),
+        install it and return the centres [num_clusters, 768] (mlgate extension)."""
+        from .anyloc import fit_vocabulary
+        eng = self._anyloc
+        if eng is None:  # the engine needs some vocabulary to exist; the fit replaces it
+            eng = self._build_engine(np.zeros((self.num_clusters, 768), np.float32))
+        centers = fit_vocabulary((eng, _device_frames(images, eng.device)), self.num_clusters, seed, max_iter)
+        self._anyloc = eng
+        self.set_vocabulary(centers)
+        return centers
+
+    def extract_descriptors(self, images) -> np.ndarray:
+        eng = self._native_engine()
+        if eng is None:
+            return super().extract_descriptors(images)
+        return eng.forward(_device_frames(images, eng.device)).cpu().numpy()
+
+    def extract_descriptor(self, image: np.ndarray) -> np.ndarray:
+        eng = self._native_engine()
+        if eng is None:
+            return super().extract_descriptor(image)
+        return eng.forward(_device_frames([image], eng.device))[0].cpu().numpy().flatten()
 
 
 class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):

@@ -693,3 +693,58 @@ def resolve_mixvpr_state_dict(path=None, seed=0):
     if path:
         return load_mixvpr_state_dict(path), path
     return mixvpr_state_dict(seed), f"synthetic(seed={seed})"
+
+
+# ------------------------------------------------------------- AnyLoc vocabulary
+VLAD_DIM = EMBED  # token width of the ViT-B/14 final layer
+VLAD_CLUSTERS = tuple(range(16, 129, 16))  # include/mlgate.h MLG_VLAD_MAX_CLUSTERS
+
+
+def check_vocabulary(centers, num_clusters=None):
+    """float32 [K, 768] C-contiguous copy of a VLAD vocabulary; ValueError on any other
+    shape, on a K the kernels do not take, or on K != num_clusters when that is given."""
+    c = np.asarray(centers)
+    if c.ndim != 2 or c.shape[1] != VLAD_DIM or c.shape[0] not in VLAD_CLUSTERS:
+        raise ValueError(f"VLAD vocabulary must be [K, {VLAD_DIM}] with K a multiple of 16 in 16..128, "
+                         f"got {tuple(c.shape)}")
+    if num_clusters is not None and c.shape[0] != num_clusters:
+        raise ValueError(f"VLAD vocabulary has {c.shape[0]} centres, expected {num_clusters}")
+    c = np.ascontiguousarray(c, dtype=np.float32)
+    if not np.isfinite(c).all():
+        raise ValueError("VLAD vocabulary holds non-finite values")
+    return c
+
+
+def load_vocabulary(path, num_clusters=None):
+    """Cluster centres from a local file: a .npy array, or a torch.save'd tensor or dict
+    with 'c_centers' (the cache file upstream AnyLoc's VLAD writes, c_centers.pt)."""
+    path = os.fspath(path)
+    if path.endswith(".npy"):
+        c = np.load(path, allow_pickle=False)
+    else:
+        import torch
+        c = torch.load(path, map_location="cpu", weights_only=True)
+        if isinstance(c, dict):
+            if "c_centers" not in c:
+                raise ValueError(f"{path}: a vocabulary dict must hold 'c_centers'")
+            c = c["c_centers"]
+        if not isinstance(c, torch.Tensor):
+            raise ValueError(f"{path}: expected a tensor or a dict with 'c_centers'")
+        c = c.detach().float().cpu().numpy()
+    return check_vocabulary(c, num_clusters)
+
+
+def synthetic_vocabulary(num_clusters=64, seed=0):
+    """Seeded stand-in centres (unit Gaussian directions scaled to the norm k-means centres
+    of unit tokens typically have): exercises the kernels, retrieves nothing meaningful."""
+    rng = np.random.default_rng([seed, num_clusters])
+    c = rng.standard_normal((num_clusters, VLAD_DIM))
+    c *= 0.87 / np.linalg.norm(c, axis=1, keepdims=True)
+    return check_vocabulary(c.astype(np.float32), num_clusters)
+
+
+def resolve_vocabulary(path=None, num_clusters=64, seed=0):
+    path = path or os.environ.get("MLGATE_ANYLOC_VOCAB")
+    if path:
+        return load_vocabulary(path, num_clusters), path
+    return synthetic_vocabulary(num_clusters, seed), f"synthetic(seed={seed})"
