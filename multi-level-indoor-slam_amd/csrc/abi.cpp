@@ -10,13 +10,13 @@
 #include "../../include/mlgate.h"
 #include <cstddef>
 
+#include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
 constexpr int PATCH = 14;
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct VitGeom {
     int B, S, grid, P, T, Tpad;
@@ -35,31 +35,92 @@ struct VitWorkspace {
     size_t q_bytes, vt_bytes, lo_elems;
 };
 
-size_t carve(const VitGeom& g, char* base, VitWorkspace* ws) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off = align_up(off + bytes);
-        return p;
-    };
+// the ViT buffers at the carver's position (AnyLoc carves its own behind them)
+VitWorkspace vit_take(WsCarver& c, const VitGeom& g) {
     const size_t rows = (size_t)g.B * g.T;
     const size_t heads = (size_t)g.B * 12;
     VitWorkspace w{};
-    w.patches = (bf16_t*)take((size_t)g.B * g.P * MLG_VIT_PATCH_K * 2 * 2);
-    w.x = (float*)take(rows * 768 * 4);
-    w.xn = (bf16_t*)take(rows * 768 * 2 * 2);
+    w.patches = c.take<bf16_t>((size_t)g.B * g.P * MLG_VIT_PATCH_K * 2);
+    w.x = c.take<float>(rows * 768);
+    w.xn = c.take<bf16_t>(rows * 768 * 2);
     w.lo_elems = heads * g.Tpad * 64;
-    w.q_bytes = 2 * w.lo_elems * 2;
-    w.q = (bf16_t*)take(w.q_bytes);
-    w.k = (bf16_t*)take(2 * w.lo_elems * 2);
-    w.vt_bytes = 2 * w.lo_elems * 2;
-    w.vt = (bf16_t*)take(w.vt_bytes);
-    w.o = (bf16_t*)take(rows * 768 * 2 * 2);
-    w.h = (bf16_t*)take(rows * 3072 * 2 * 2);
-    w.partial = (float*)take(mlg_gem_partial_bytes(g.B));
-    w.tasks = (int32_t*)take((size_t)g.B * 5 * 4);
+    w.q_bytes = w.vt_bytes = 2 * w.lo_elems * sizeof(bf16_t);
+    w.q = c.take<bf16_t>(2 * w.lo_elems);
+    w.k = c.take<bf16_t>(2 * w.lo_elems);
+    w.vt = c.take<bf16_t>(2 * w.lo_elems);
+    w.o = c.take<bf16_t>(rows * 768 * 2);
+    w.h = c.take<bf16_t>(rows * 3072 * 2);
+    w.partial = c.take<float>(mlg_gem_partial_bytes(g.B) / sizeof(float));
+    w.tasks = c.take<int32_t>((size_t)g.B * 5);
+    return w;
+}
+
+size_t carve(const VitGeom& g, void* base, VitWorkspace* ws) {
+    WsCarver c(base);
+    const VitWorkspace w = vit_take(c, g);
     if (ws) *ws = w;
-    return off;
+    return c.total();
+}
+
+// AnyLoc: the ViT buffers, then the patch tokens, the mean-pooled rows the final norm kernel
+// also writes (unused), then the VLAD head's workspace
+struct AnylocBufs {
+    VitWorkspace vit;
+    float *tokens, *pooled;  // [B, T - 2, 768]; [B, 768]
+    char* head;
+    size_t head_bytes;
+};
+
+// 0 when the VLAD head refuses (B, T - 2, K)
+size_t anyloc_carve(const VitGeom& g, int K, void* base, AnylocBufs* out) {
+    WsCarver c(base);
+    AnylocBufs b;
+    b.vit = vit_take(c, g);
+    b.tokens = c.take<float>((size_t)g.B * (g.T - 2) * 768);
+    b.pooled = c.take<float>((size_t)g.B * 768);
+    b.head_bytes = mlg_vlad_ws_bytes(g.B, g.T - 2, K);
+    b.head = c.take<char>(b.head_bytes);
+    if (out) *out = b;
+    return b.head_bytes ? c.total() : 0;
+}
+
+// k <= 32 and D % 4 == 0 take the fused scan (no [Q, N] matrix): normalised rows plus
+// the per-split partial lists
+bool knn_fused(int D, int k) { return k >= 1 && k <= 32 && D % 4 == 0; }
+
+struct KnnBufs {
+    float *Xn, *Qn, *S;
+    char* part;  // the fused scan's partial lists
+};
+
+// fused layouts: gate = Xn | partial lists; query = Xn | Qn | partial lists; else Xn | Qn | S
+size_t knn_carve(int N, int D, int Q, int k, int query, void* base, KnnBufs* out) {
+    WsCarver c(base);
+    KnnBufs b{};
+    b.Xn = c.take<float>((size_t)N * D);
+    if (knn_fused(D, k)) {
+        if (query) b.Qn = c.take<float>((size_t)Q * D);
+        b.part = c.take<char>(mlg_knn_fused_ws_bytes(Q, N, k));
+    } else {
+        b.Qn = c.take<float>((size_t)Q * D);  // a gap on the gate path (its queries are rows of Xn): the size stays
+        b.S = c.take<float>((size_t)Q * N);
+    }
+    if (out) *out = b;
+    return c.total();
+}
+
+struct XcorrBufs {
+    float *qn, *mn, *C;
+};
+
+size_t xcorr_carve(int n1, int n2, int D, void* base, XcorrBufs* out) {
+    WsCarver c(base);
+    XcorrBufs b;
+    b.qn = c.take<float>((size_t)n1 * D);
+    b.mn = c.take<float>((size_t)n2 * D);
+    b.C = c.take<float>((size_t)n1 * n2);
+    if (out) *out = b;
+    return c.total();
 }
 
 // ------------------------------------------------------------- profiling
@@ -90,12 +151,6 @@ void prof_collect() {
     g_prof.recs.clear();
     g_prof.next = 0;
 }
-
-#define TRY(x)                     \
-    do {                           \
-        int rc_ = (x);             \
-        if (rc_ != MLG_OK) return rc_; \
-    } while (0)
 
 }  // namespace
 
@@ -143,14 +198,15 @@ size_t mlg_vit_workspace_bytes(int batch, int image_size) {
 static int vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, const VitGeom& g, int H, int W, int C,
                      long frame_stride, int swap_rb, const VitWorkspace& ws, hipStream_t s, int split = 0) {
     const int M = g.B * g.T;
-    TRY(mlg_preprocess_patches(frames, g.B, H, W, C, frame_stride, g.S, MLG_VIT_PATCH_K, swap_rb, ws.patches, s,
-                               split));
+    MLG_TRY(mlg_preprocess_patches(frames, g.B, H, W, C, frame_stride, g.S, MLG_VIT_PATCH_K, swap_rb, ws.patches, s,
+                                   split));
     if (split)
-        TRY(mlg_gemm_patch_split(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K,
-                                 s));
+        MLG_TRY(mlg_gemm_patch_split(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P,
+                                     MLG_VIT_PATCH_K, s));
     else
-        TRY(mlg_gemm_patch(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K, s));
-    TRY(mlg_cls_rows(ws.x, w->cls, w->pos, g.B, g.T, s));
+        MLG_TRY(mlg_gemm_patch(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K,
+                               s));
+    MLG_TRY(mlg_cls_rows(ws.x, w->cls, w->pos, g.B, g.T, s));
     // padded key columns of V^T must be finite (masked keys multiply them by p = 0); padded
     // query rows are never stored but are zeroed too, so no lane computes on stale bits
     if (hipMemsetAsync(ws.vt, 0, ws.vt_bytes, s) != hipSuccess) return MLG_EHIP;
@@ -159,52 +215,52 @@ static int vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, const VitG
     const double mul = split ? 3.0 : 1.0;  // MFMA products per algorithmic product
     for (int l = 0; l < MLG_VIT_DEPTH && split; ++l) {
         const mlg_vit_block& bl = w->blocks[l];
-        TRY(mlg_layernorm_split(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
+        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
         {
             MlgProfScope p(2, s, mul * 2.0 * M * 2304 * 768);
-            TRY(mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems, s));
+            MLG_TRY(mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems, s));
         }
         {
             MlgProfScope p(4, s, mul * 4.0 * g.B * 12 * (double)g.T * g.T * 64);
-            TRY(mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s));
+            MLG_TRY(mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s));
         }
         {
             MlgProfScope p(3, s, mul * 2.0 * M * 768 * 768);
-            TRY(mlg_gemm_residual_split(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
+            MLG_TRY(mlg_gemm_residual_split(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
         }
-        TRY(mlg_layernorm_split(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
+        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
         {
             MlgProfScope p(0, s, mul * 2.0 * M * 3072 * 768);
-            TRY(mlg_gemm_bias_gelu_split(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
+            MLG_TRY(mlg_gemm_bias_gelu_split(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
         }
         {
             MlgProfScope p(1, s, mul * 2.0 * M * 768 * 3072);
-            TRY(mlg_gemm_residual_split(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
+            MLG_TRY(mlg_gemm_residual_split(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
         }
     }
     for (int l = 0; l < MLG_VIT_DEPTH && !split; ++l) {
         const mlg_vit_block& bl = w->blocks[l];
-        TRY(mlg_layernorm_bf16(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
+        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
         {
             MlgProfScope p(2, s, 2.0 * M * 2304 * 768);
-            TRY(mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s));
+            MLG_TRY(mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s));
         }
         {
             MlgProfScope p(4, s, 4.0 * g.B * 12 * (double)g.T * g.T * 64);
-            TRY(mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s));
+            MLG_TRY(mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s));
         }
         {
             MlgProfScope p(3, s, 2.0 * M * 768 * 768);
-            TRY(mlg_gemm_residual(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
+            MLG_TRY(mlg_gemm_residual(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
         }
-        TRY(mlg_layernorm_bf16(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
+        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
         {
             MlgProfScope p(0, s, 2.0 * M * 3072 * 768);
-            TRY(mlg_gemm_bias_gelu_bf16(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
+            MLG_TRY(mlg_gemm_bias_gelu_bf16(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
         }
         {
             MlgProfScope p(1, s, 2.0 * M * 768 * 3072);
-            TRY(mlg_gemm_residual(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
+            MLG_TRY(mlg_gemm_residual(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
         }
     }
     return MLG_OK;
@@ -221,12 +277,12 @@ int mlg_vit_forward(const mlg_vit_weights* w, const uint8_t* frames, int batch, 
     if (w->packing != ((flags & MLG_VIT_SPLIT) ? MLG_VIT_SPLIT : 0)) return MLG_EINVAL;
     const VitGeom g(batch, image_size);
     VitWorkspace ws;
-    if (carve(g, (char*)workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
+    if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
     const int swap_rb = (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1;
     const int mean_pool = (flags & MLG_VIT_POOL_MEAN) ? 1 : 0;
-    TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, swap_rb, ws, s, (flags & MLG_VIT_SPLIT) ? 1 : 0));
-    TRY(mlg_final_norm_gem(ws.x, w->norm_w, w->norm_b, local_out, ws.partial, desc_out, g.B, g.T, mean_pool, s));
+    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, swap_rb, ws, s, (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    MLG_TRY(mlg_final_norm_gem(ws.x, w->norm_w, w->norm_b, local_out, ws.partial, desc_out, g.B, g.T, mean_pool, s));
     return MLG_OK;
 }
 
@@ -245,16 +301,16 @@ int mlg_salad_forward(const mlg_vit_weights* w, const mlg_salad_weights* sw, con
     if (w->packing != 0) return MLG_EINVAL;  // SALAD's trunk runs the plain bf16 forward
     const VitGeom g(batch, image_size);
     VitWorkspace ws;
-    if (carve(g, (char*)workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
+    if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
     const int M = g.B * g.T;
     // SALAD._preprocess keeps the stored channel order (place_recognition.py:395-397)
-    TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, /*swap_rb=*/0, ws, s));
-    TRY(mlg_layernorm_bf16(ws.x, w->norm_w, w->norm_b, ws.xn, M, s));  // backbone norm_layer, all tokens
-    TRY(mlg_gemm_bias_relu_bf16(ws.xn, 768, sw->w1, sw->b1, ws.h, 1024, 1024, M, 1024, 768, s));
+    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, /*swap_rb=*/0, ws, s));
+    MLG_TRY(mlg_layernorm_bf16(ws.x, w->norm_w, w->norm_b, ws.xn, M, s));  // backbone norm_layer, all tokens
+    MLG_TRY(mlg_gemm_bias_relu_bf16(ws.xn, 768, sw->w1, sw->b1, ws.h, 1024, 1024, M, 1024, 768, s));
     float* y = ws.x;  // [M, 256]
-    TRY(mlg_gemm_bias_f32_ld(ws.h, 1024, sw->w2, sw->b2, y, 256, M, 256, 1024, s));
-    TRY(mlg_salad_head(ws.xn, y, g.B, g.T, sw->wt1, sw->bt1, sw->wt2, sw->bt2, sw->dust_bin, desc_out, s));
+    MLG_TRY(mlg_gemm_bias_f32_ld(ws.h, 1024, sw->w2, sw->b2, y, 256, M, 256, 1024, s));
+    MLG_TRY(mlg_salad_head(ws.xn, y, g.B, g.T, sw->wt1, sw->bt1, sw->wt2, sw->bt2, sw->dust_bin, desc_out, s));
     return MLG_OK;
 }
 
@@ -267,15 +323,9 @@ int mlg_op_vlad(const mlg_vlad_vocab* vocab, const float* tokens, int B, int P, 
                         labels_or_null, (hipStream_t)stream);
 }
 
-// the ViT buffers, then the patch tokens [B, P, 768] f32, the mean-pooled rows the final
-// norm kernel also writes (unused), then the VLAD head's workspace
 size_t mlg_anyloc_workspace_bytes(int B, int image_size, int K) {
-    const size_t vit = mlg_vit_workspace_bytes(B, image_size);
-    if (!vit || image_size < 2 * PATCH) return 0;
-    const VitGeom g(B, image_size);
-    const size_t head = mlg_vlad_ws_bytes(B, g.T - 2, K);
-    if (!head) return 0;
-    return vit + align_up((size_t)B * (g.T - 2) * 768 * 4) + align_up((size_t)B * 768 * 4) + head;
+    if (!mlg_vit_workspace_bytes(B, image_size) || image_size < 2 * PATCH) return 0;
+    return anyloc_carve(VitGeom(B, image_size), K, nullptr, nullptr);
 }
 
 int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, const uint8_t* frames, int B, int H,
@@ -284,21 +334,17 @@ int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, co
     if (!mlg_head_ok(w, MLG_ABI_VERSION) || !mlg_head_ok(vocab, MLG_ABI_VERSION) || !frames || !workspace || !desc)
         return MLG_EINVAL;
     if (w->packing != ((flags & MLG_VIT_SPLIT) ? MLG_VIT_SPLIT : 0)) return MLG_EINVAL;
-    const size_t need = mlg_anyloc_workspace_bytes(B, image_size, vocab->num_clusters);
-    if (!need || workspace_bytes < need) return MLG_EINVAL;
+    if (!mlg_anyloc_workspace_bytes(B, image_size, vocab->num_clusters)) return MLG_EINVAL;
     const VitGeom g(B, image_size);
-    VitWorkspace ws;
-    char* p = (char*)workspace + carve(g, (char*)workspace, &ws);
-    float* tokens = (float*)p;
-    p += align_up((size_t)B * (g.T - 2) * 768 * 4);
-    float* pooled = (float*)p;
-    p += align_up((size_t)B * 768 * 4);
+    AnylocBufs b;
+    if (anyloc_carve(g, vocab->num_clusters, workspace, &b) > workspace_bytes) return MLG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s,
-                  (flags & MLG_VIT_SPLIT) ? 1 : 0));
-    TRY(mlg_final_norm_gem(ws.x, w->norm_w, w->norm_b, tokens, ws.partial, pooled, g.B, g.T, /*mean_pool=*/1, s));
-    return mlg_vlad_run(vocab->centers, vocab->num_clusters, tokens, B, g.T - 2, p,
-                        workspace_bytes - (size_t)(p - (char*)workspace), desc, nullptr, s);
+    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s,
+                      (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, b.tokens, b.vit.partial, b.pooled, g.B, g.T,
+                               /*mean_pool=*/1, s));
+    return mlg_vlad_run(vocab->centers, vocab->num_clusters, b.tokens, B, g.T - 2, b.head, b.head_bytes, desc, nullptr,
+                        s);
 }
 
 size_t mlg_kmeans_workspace_bytes(long M, int K) { return mlg_kmeans_ws_bytes(M, K); }
@@ -311,19 +357,12 @@ int mlg_kmeans_step(const float* tokens, long M, float* centers, int K, int32_t*
 
 size_t mlg_knn_workspace_bytes(int N, int D, int Q) {
     if (N <= 0 || D <= 0 || Q <= 0) return 0;
-    return align_up((size_t)N * D * 4) + align_up((size_t)Q * D * 4) + align_up((size_t)Q * N * 4);
+    return knn_carve(N, D, Q, /*k=*/0, 0, nullptr, nullptr);  // k = 0: never fused
 }
 
-// k <= 32 and D % 4 == 0 take the fused scan (no [Q, N] matrix): normalised rows plus
-// the per-split partial lists
-static bool knn_fused(int D, int k) { return k >= 1 && k <= 32 && D % 4 == 0; }
-
-// fused layouts: gate = Xn | partial lists; query = Xn | Qn | partial lists
 size_t mlg_knn_workspace_bytes_k(int N, int D, int Q, int k, int query) {
     if (N <= 0 || D <= 0 || Q <= 0) return 0;
-    if (!knn_fused(D, k)) return mlg_knn_workspace_bytes(N, D, Q);
-    return align_up((size_t)N * D * 4) + (query ? align_up((size_t)Q * D * 4) : 0) +
-           align_up(mlg_knn_fused_ws_bytes(Q, N, k));
+    return knn_carve(N, D, Q, k, query, nullptr, nullptr);
 }
 
 int mlg_knn_gate(const float* desc, int N, int D, const double* t, const int64_t* floor, const uint8_t* has_floor,
@@ -333,22 +372,19 @@ int mlg_knn_gate(const float* desc, int N, int D, const double* t, const int64_t
     if (!desc || !t || !workspace || N <= 0 || D <= 0 || Q <= 0 || q0 < 0 || q0 + Q > N) return MLG_EINVAL;
     if (gating && (!floor || !has_floor)) return MLG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* Xn = (float*)workspace;
-    float* S = (float*)((char*)workspace + align_up((size_t)N * D * 4) + align_up((size_t)Q * D * 4));
+    KnnBufs b;
+    if (knn_carve(N, D, Q, k, 0, workspace, &b) > workspace_bytes) return MLG_ENOMEM;
     if (knn_fused(D, k)) {
-        if (mlg_knn_workspace_bytes_k(N, D, Q, k, 0) > workspace_bytes) return MLG_ENOMEM;
-        TRY(mlg_row_normalize_wave(desc, Xn, N, D, nullptr, s));
-        void* part = (char*)workspace + align_up((size_t)N * D * 4);
-        return mlg_knn_fused(Xn + (size_t)q0 * D, Q, Xn, N, D, t + q0, t, gating ? floor + q0 : nullptr,
+        MLG_TRY(mlg_row_normalize_wave(desc, b.Xn, N, D, nullptr, s));
+        return mlg_knn_fused(b.Xn + (size_t)q0 * D, Q, b.Xn, N, D, t + q0, t, gating ? floor + q0 : nullptr,
                              gating ? has_floor + q0 : nullptr, gating ? floor : nullptr, gating ? has_floor : nullptr,
-                             min_gap, thr, k, gating, part, idx, sim, valid, count, totals, s);
+                             min_gap, thr, k, gating, b.part, idx, sim, valid, count, totals, s);
     }
-    if (mlg_knn_workspace_bytes(N, D, Q) > workspace_bytes) return MLG_ENOMEM;
-    TRY(mlg_row_normalize(desc, Xn, N, D, nullptr, s));
-    TRY(mlg_similarity_f32(Xn + (size_t)q0 * D, Q, Xn, N, D, S, N, s));
-    TRY(mlg_topk_gate(S, N, N, Q, t + q0, t, gating ? floor + q0 : nullptr, gating ? has_floor + q0 : nullptr,
-                      gating ? floor : nullptr, gating ? has_floor : nullptr, min_gap, thr, k, gating, idx, sim,
-                      valid, count, totals, s));
+    MLG_TRY(mlg_row_normalize(desc, b.Xn, N, D, nullptr, s));
+    MLG_TRY(mlg_similarity_f32(b.Xn + (size_t)q0 * D, Q, b.Xn, N, D, b.S, N, s));
+    MLG_TRY(mlg_topk_gate(b.S, N, N, Q, t + q0, t, gating ? floor + q0 : nullptr, gating ? has_floor + q0 : nullptr,
+                          gating ? floor : nullptr, gating ? has_floor : nullptr, min_gap, thr, k, gating, idx, sim,
+                          valid, count, totals, s));
     return MLG_OK;
 }
 
@@ -357,22 +393,19 @@ int mlg_knn_query(const float* db, int N, int D, const float* qdesc, int Q, cons
                   int32_t* idx, float* sim, int32_t* count, void* stream) {
     if (!db || !qdesc || !t_db || !t_query || !workspace || N <= 0 || D <= 0 || Q <= 0) return MLG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* Xn = (float*)workspace;
-    float* Qn = (float*)((char*)workspace + align_up((size_t)N * D * 4));
-    float* S = (float*)((char*)Qn + align_up((size_t)Q * D * 4));
+    KnnBufs b;
+    if (knn_carve(N, D, Q, k, 1, workspace, &b) > workspace_bytes) return MLG_ENOMEM;
     if (knn_fused(D, k)) {
-        if (mlg_knn_workspace_bytes_k(N, D, Q, k, 1) > workspace_bytes) return MLG_ENOMEM;
-        TRY(mlg_row_normalize_wave(db, Xn, N, D, nullptr, s));
-        TRY(mlg_row_normalize_wave(qdesc, Qn, Q, D, nullptr, s));
-        return mlg_knn_fused(Qn, Q, Xn, N, D, t_query, t_db, nullptr, nullptr, nullptr, nullptr, min_gap, -INFINITY,
-                             k, 0, S, idx, sim, nullptr, count, nullptr, s);
+        MLG_TRY(mlg_row_normalize_wave(db, b.Xn, N, D, nullptr, s));
+        MLG_TRY(mlg_row_normalize_wave(qdesc, b.Qn, Q, D, nullptr, s));
+        return mlg_knn_fused(b.Qn, Q, b.Xn, N, D, t_query, t_db, nullptr, nullptr, nullptr, nullptr, min_gap,
+                             -INFINITY, k, 0, b.part, idx, sim, nullptr, count, nullptr, s);
     }
-    if (mlg_knn_workspace_bytes(N, D, Q) > workspace_bytes) return MLG_ENOMEM;
-    TRY(mlg_row_normalize(db, Xn, N, D, nullptr, s));
-    TRY(mlg_row_normalize(qdesc, Qn, Q, D, nullptr, s));
-    TRY(mlg_similarity_f32(Qn, Q, Xn, N, D, S, N, s));
-    TRY(mlg_topk_gate(S, N, N, Q, t_query, t_db, nullptr, nullptr, nullptr, nullptr, min_gap, -INFINITY, k, 0, idx,
-                      sim, nullptr, count, nullptr, s));
+    MLG_TRY(mlg_row_normalize(db, b.Xn, N, D, nullptr, s));
+    MLG_TRY(mlg_row_normalize(qdesc, b.Qn, Q, D, nullptr, s));
+    MLG_TRY(mlg_similarity_f32(b.Qn, Q, b.Xn, N, D, b.S, N, s));
+    MLG_TRY(mlg_topk_gate(b.S, N, N, Q, t_query, t_db, nullptr, nullptr, nullptr, nullptr, min_gap, -INFINITY, k, 0,
+                          idx, sim, nullptr, count, nullptr, s));
     return MLG_OK;
 }
 
@@ -474,10 +507,10 @@ int mlg_mixvpr_forward(const mlg_mixvpr_weights* w, const uint8_t* frames, int B
     }
     if (workspace_bytes < mlg_mixvpr_workspace_bytes(B, H, W)) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    TRY(mlg_mixvpr_preprocess(frames, B, H, W, C, frame_stride, mlg_resnet50_l3_image(workspace, B, MLG_MIXVPR_SIZE),
-                              s));
+    MLG_TRY(mlg_mixvpr_preprocess(frames, B, H, W, C, frame_stride,
+                                  mlg_resnet50_l3_image(workspace, B, MLG_MIXVPR_SIZE), s));
     float* feat = nullptr;
-    TRY(mlg_resnet50_l3_run(rn, B, MLG_MIXVPR_SIZE, workspace, workspace_bytes, &feat, s));
+    MLG_TRY(mlg_resnet50_l3_run(rn, B, MLG_MIXVPR_SIZE, workspace, workspace_bytes, &feat, s));
     return mlg_mixvpr_head(*reinterpret_cast<const mlg_mix_weights_i*>(&w->mix_w), feat, B, desc, s);
 }
 
@@ -585,21 +618,19 @@ int mlg_recover_pose(const float* kp1, const float* kp2, const int32_t* offsets,
 
 size_t mlg_xcorr_workspace_bytes(int n1, int n2, int D) {
     if (n1 <= 0 || n2 <= 0 || D <= 0) return 0;
-    return align_up((size_t)n1 * D * 4) + align_up((size_t)n2 * D * 4) + align_up((size_t)n1 * n2 * 4);
+    return xcorr_carve(n1, n2, D, nullptr, nullptr);
 }
 
 int mlg_xcorr_score(const float* q, int n1, const float* m, int n2, int D, void* workspace, size_t workspace_bytes,
                     float* score, void* stream) {
     if (!q || !m || !workspace || !score || n1 <= 0 || n2 <= 0 || D <= 0) return MLG_EINVAL;
-    if (mlg_xcorr_workspace_bytes(n1, n2, D) > workspace_bytes) return MLG_ENOMEM;
+    XcorrBufs b;
+    if (xcorr_carve(n1, n2, D, workspace, &b) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    float* qn = (float*)workspace;
-    float* mn = (float*)((char*)workspace + align_up((size_t)n1 * D * 4));
-    float* C = (float*)((char*)mn + align_up((size_t)n2 * D * 4));
-    TRY(mlg_row_normalize(q, qn, n1, D, nullptr, s));
-    TRY(mlg_row_normalize(m, mn, n2, D, nullptr, s));
-    TRY(mlg_similarity_f32(qn, n1, mn, n2, D, C, n2, s));
-    TRY(mlg_xcorr_reduce(C, n1, n2, score, s));
+    MLG_TRY(mlg_row_normalize(q, b.qn, n1, D, nullptr, s));
+    MLG_TRY(mlg_row_normalize(m, b.mn, n2, D, nullptr, s));
+    MLG_TRY(mlg_similarity_f32(b.qn, n1, b.mn, n2, D, b.C, n2, s));
+    MLG_TRY(mlg_xcorr_reduce(b.C, n1, n2, score, s));
     return MLG_OK;
 }
 

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -847,28 +848,43 @@ __global__ __launch_bounds__(256) void k_xcorr_finish(const float* __restrict__ 
 // (346 MB at L = 528) however many pairs one call scores
 constexpr int XC_SLICE = 16384;
 
+namespace {
+struct XcBufs {
+    float *fn, *rowp, *colp;  // normalised rows; per-tile row / column maxima of one slice
+};
+
+size_t xc_carve(int F, int L, int D, int P, void* base, XcBufs* out) {
+    WsCarver c(base);
+    XcBufs b;
+    const size_t part = (size_t)(P < XC_SLICE ? P : XC_SLICE) * ((L + SBM - 1) / SBM) * L;
+    b.fn = c.take<float>((size_t)F * L * D);
+    // rowp | colp end the workspace without rounding (the size has always been exact)
+    b.rowp = c.take<float>(0);
+    b.colp = b.rowp ? b.rowp + part : nullptr;
+    if (out) *out = b;
+    return c.total() + 2 * part * sizeof(float);
+}
+}  // namespace
+
 size_t mlg_xcorr_batch_ws_bytes(int F, int L, int D, int P) {
     if (F <= 0 || L <= 0 || D <= 0 || P <= 0) return 0;
-    const size_t t = (size_t)((L + SBM - 1) / SBM);
-    const size_t ps = (size_t)(P < XC_SLICE ? P : XC_SLICE);
-    return (((size_t)F * L * D * 4 + 255) & ~(size_t)255) + 2 * ps * t * L * 4;
+    return xc_carve(F, L, D, P, nullptr, nullptr);
 }
 
 int mlg_xcorr_batch_run(const float* feats, int F, int L, int D, const int32_t* qa, const int32_t* qb, int P,
                         void* ws, size_t ws_bytes, float* score, hipStream_t s) {
     if (P <= 0) return MLG_OK;
     if (!feats || !qa || !qb || !ws || !score || F <= 0 || L <= 0 || D <= 0 || (D % 4)) return MLG_EINVAL;
-    if (ws_bytes < mlg_xcorr_batch_ws_bytes(F, L, D, P)) return MLG_ENOMEM;
-    float* fn = (float*)ws;
+    XcBufs b;
+    if (xc_carve(F, L, D, P, ws, &b) > ws_bytes) return MLG_ENOMEM;
     const int t = (L + SBM - 1) / SBM;
-    float* rowp = (float*)((char*)ws + (((size_t)F * L * D * 4 + 255) & ~(size_t)255));
-    float* colp = rowp + (size_t)(P < XC_SLICE ? P : XC_SLICE) * t * L;
     // the reference's q / (||q|| + 1e-8) per row, numpy-exact (one thread per row)
-    hipLaunchKernelGGL(k_row_normalize, dim3((F * L + 63) / 64), dim3(64), 0, s, feats, fn, F * L, D, D, nullptr);
+    hipLaunchKernelGGL(k_row_normalize, dim3((F * L + 63) / 64), dim3(64), 0, s, feats, b.fn, F * L, D, D, nullptr);
     for (int p0 = 0; p0 < P; p0 += XC_SLICE) {  // stream order: a slice reuses rowp / colp after the last
         const int ps = P - p0 < XC_SLICE ? P - p0 : XC_SLICE;
-        hipLaunchKernelGGL(k_xcorr_tiles, dim3(t, t, ps), dim3(256), 0, s, fn, L, D, qa + p0, qb + p0, rowp, colp);
-        hipLaunchKernelGGL(k_xcorr_finish, dim3(ps), dim3(256), 0, s, rowp, colp, L, t, t, score + p0);
+        hipLaunchKernelGGL(k_xcorr_tiles, dim3(t, t, ps), dim3(256), 0, s, b.fn, L, D, qa + p0, qb + p0, b.rowp,
+                           b.colp);
+        hipLaunchKernelGGL(k_xcorr_finish, dim3(ps), dim3(256), 0, s, b.rowp, b.colp, L, t, t, score + p0);
     }
     MLG_LAUNCH_CHECK();
     return MLG_OK;

@@ -21,11 +21,11 @@
 #include "common.h"
 #include "kernels.h"
 #include "pair_plan.h"
+#include "ws_carve.h"
 #include "../../include/mlgate.h"
 
 namespace {
 
-using pair_plan::a256;
 using pair_plan::Seg;
 static_assert(sizeof(pair_plan::Task) == sizeof(int4) && sizeof(pair_plan::Move) == sizeof(int4),
               "the host tables are uploaded by bytes into the kernels' int4 tables");
@@ -763,56 +763,65 @@ void trace(int tag, const void* base, int rpt, int row_bytes, size_t row_stride,
     t->counts.push_back(ntiles);
 }
 
-struct LgLayout {
-    size_t x, cat, efac, ind, x2, cat2, efac2, ind2, Q, K, Vt, ctx, hf, hb, live, rowseg, lz, keep,
-        stats, segs, tasks, outoff, moves, mdesc, rmax, rlog, cmax, clog, arg, val, part, asg, norm, S, total;
-    int asg_cap;
+struct LgBufs {
+    // the token buffers, primary and secondary (layer 0's frame layout; the compaction's target)
+    float *X, *X2;
+    bf16_t *CAT, *CAT2;
+    float4 *EF, *EF2;  // rotary factors, lg_fac4 layout
+    int32_t *IND, *IND2;
+    bf16_t *Q, *K, *VT, *CTX;
+    bf16_t* MDH;  // hi half, then the lo half
+    uint8_t *LIVE, *KEEP;
+    int *ROWSEG, *STATS, *OUTOFF, *ARG;
+    float *LZ, *RMAX, *RLOG, *CMAX, *CLOG, *VAL, *SS;
+    Seg* SEGS;
+    int4 *TASKS, *MOVES;  // TASKS: self tasks, then cross tasks
+    float2* PART;
+    Asg* ASG;
+    float4* NORM;
+    int asg_cap;  // pairs per assignment chunk
 };
 
-LgLayout lg_layout(int P, int kmax) {
+size_t lg_carve(int P, int kmax, void* base, LgBufs* out) {
     const size_t N = (size_t)2 * P * (((size_t)kmax + 63) & ~(size_t)63);
-    LgLayout L;
-    L.asg_cap = std::min(P, 64);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += a256(bytes);
-        return r;
-    };
-    L.x = take(N * LG_D * 4);
-    L.cat = take(N * 512 * 2);
-    L.efac = take(N * 64 * 4);  // rotary factors, lg_fac4 layout
-    L.ind = take(N * 4);
-    L.x2 = take(N * LG_D * 4);
-    L.cat2 = take(N * 512 * 2);
-    L.efac2 = take(N * 64 * 4);
-    L.ind2 = take(N * 4);
-    L.Q = take(N * LG_D * 2);
-    L.K = take(N * LG_D * 2);
-    L.Vt = take(N * LG_D * 2);
-    L.ctx = take(N * LG_D * 2);
-    L.live = take(N);
-    L.rowseg = take(N * 4);
-    L.lz = take(N * 4);
-    L.keep = take(N);
-    L.stats = take((size_t)2 * P * 2 * 4);
-    L.segs = take((size_t)2 * P * sizeof(Seg));
-    L.tasks = take((size_t)4 * P * sizeof(int4));  // self tasks, then cross tasks
-    L.outoff = take((size_t)4 * P * 4);
-    L.moves = take((size_t)2 * P * sizeof(int4));
-    L.mdesc = take(N * LG_D * 4);
-    L.rmax = take(N * 4);
-    L.rlog = take(N * 4);
-    L.cmax = take(N * 4);
-    L.clog = take(N * 4);
-    L.arg = take(N * 4);
-    L.val = take(N * 4);
-    L.part = take((size_t)L.asg_cap * 2 * ((kmax + ARM - 1) / ARM) * kmax * sizeof(float2));
-    L.asg = take((size_t)P * sizeof(Asg));
-    L.norm = take((size_t)2 * P * sizeof(float4));
-    L.S = take((size_t)L.asg_cap * kmax * ((kmax + 3) & ~3) * 4);
-    L.total = o;
-    return L;
+    const size_t ldS = ((size_t)kmax + 3) & ~(size_t)3;
+    WsCarver c(base);
+    LgBufs b;
+    b.asg_cap = std::min(P, 64);
+    b.X = c.take<float>(N * LG_D);
+    b.CAT = c.take<bf16_t>(N * 512);
+    b.EF = c.take<float4>(N * 16);
+    b.IND = c.take<int32_t>(N);
+    b.X2 = c.take<float>(N * LG_D);
+    b.CAT2 = c.take<bf16_t>(N * 512);
+    b.EF2 = c.take<float4>(N * 16);
+    b.IND2 = c.take<int32_t>(N);
+    b.Q = c.take<bf16_t>(N * LG_D);
+    b.K = c.take<bf16_t>(N * LG_D);
+    b.VT = c.take<bf16_t>(N * LG_D);
+    b.CTX = c.take<bf16_t>(N * LG_D);
+    b.LIVE = c.take<uint8_t>(N);
+    b.ROWSEG = c.take<int>(N);
+    b.LZ = c.take<float>(N);
+    b.KEEP = c.take<uint8_t>(N);
+    b.STATS = c.take<int>((size_t)2 * P * 2);
+    b.SEGS = c.take<Seg>((size_t)2 * P);
+    b.TASKS = c.take<int4>((size_t)4 * P);
+    b.OUTOFF = c.take<int>((size_t)4 * P);
+    b.MOVES = c.take<int4>((size_t)2 * P);
+    b.MDH = c.take<bf16_t>(2 * N * LG_D);
+    b.RMAX = c.take<float>(N);
+    b.RLOG = c.take<float>(N);
+    b.CMAX = c.take<float>(N);
+    b.CLOG = c.take<float>(N);
+    b.ARG = c.take<int>(N);
+    b.VAL = c.take<float>(N);
+    b.PART = c.take<float2>((size_t)b.asg_cap * 2 * ((kmax + ARM - 1) / ARM) * kmax);
+    b.ASG = c.take<Asg>((size_t)P);
+    b.NORM = c.take<float4>((size_t)2 * P);
+    b.SS = c.take<float>((size_t)b.asg_cap * kmax * ldS);
+    if (out) *out = b;
+    return c.total();
 }
 
 float conf_threshold(int i) {
@@ -824,7 +833,7 @@ float conf_threshold(int i) {
 
 size_t mlg_lightglue_ws_bytes(int P, int kmax) {
     if (P <= 0 || kmax <= 0 || kmax > 2048) return 0;
-    return lg_layout(P, kmax).total;
+    return lg_carve(P, kmax, nullptr, nullptr);
 }
 
 int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float* desc, const int32_t* counts, int kmax,
@@ -832,46 +841,14 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
                       float filter_thr, int pruning_min, void* ws, size_t ws_bytes, int32_t* matches, float* mscores,
                       int32_t* nmatch, int32_t* stop_layer, hipStream_t s) {
     if (P <= 0 || kmax <= 0 || kmax > 2048) return MLG_EINVAL;
-    const LgLayout L = lg_layout(P, kmax);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* base = (char*)ws;
-    float* X = (float*)(base + L.x);
-    bf16_t* CAT = (bf16_t*)(base + L.cat);
-    float4* EF = (float4*)(base + L.efac);
-    int32_t* IND = (int32_t*)(base + L.ind);
-    float* X2 = (float*)(base + L.x2);
-    bf16_t* CAT2 = (bf16_t*)(base + L.cat2);
-    float4* EF2 = (float4*)(base + L.efac2);
-    int32_t* IND2 = (int32_t*)(base + L.ind2);
-    bf16_t* Q = (bf16_t*)(base + L.Q);
-    bf16_t* K = (bf16_t*)(base + L.K);
-    bf16_t* VT = (bf16_t*)(base + L.Vt);
-    bf16_t* CTX = (bf16_t*)(base + L.ctx);
-    uint8_t* LIVE = (uint8_t*)(base + L.live);
-    int* ROWSEG = (int*)(base + L.rowseg);
-    float* LZ = (float*)(base + L.lz);
-    uint8_t* KEEP = (uint8_t*)(base + L.keep);
-    int* STATS = (int*)(base + L.stats);
-    Seg* SEGS = (Seg*)(base + L.segs);
-    int4* TASKS = (int4*)(base + L.tasks);
-    int* OUTOFF = (int*)(base + L.outoff);
-    int4* MOVES = (int4*)(base + L.moves);
-    bf16_t* MDH = (bf16_t*)(base + L.mdesc);  // hi half, then the lo half
-    float* RMAX = (float*)(base + L.rmax);
-    float* RLOG = (float*)(base + L.rlog);
-    float* CMAX = (float*)(base + L.cmax);
-    float* CLOG = (float*)(base + L.clog);
-    int* ARG = (int*)(base + L.arg);
-    float* VAL = (float*)(base + L.val);
-    float2* PART = (float2*)(base + L.part);
-    Asg* ASG = (Asg*)(base + L.asg);
-    float* SS = (float*)(base + L.S);
+    LgBufs b;  // X / CAT / EF / IND swap with their secondaries at each compaction
+    if (lg_carve(P, kmax, ws, &b) > ws_bytes) return MLG_EINVAL;
     // debug trace (mlg_dbg_lg_trace_begin): per-stage hashes of 64-row tiles
     // live rows only (LIVE is the current layout's mask); byte-per-row buffers as 64-B tiles
     auto tr_rows = [&](int tag, const void* p, size_t row_bytes, int np, size_t stride = 0) {
         if (!t_trace) return;
         if (row_bytes < 4) trace(tag, p, 1, 64, 64, 1, 0, np / 64, s);
-        else trace(tag, p, 64, (int)row_bytes, stride ? stride : row_bytes, 1, 0, np / 64, s, LIVE);
+        else trace(tag, p, 64, (int)row_bytes, stride ? stride : row_bytes, 1, 0, np / 64, s, b.LIVE);
     };
     auto tr_heads = [&](int tag, const void* p, int np) {  // Q / K / V^T: [4 heads][np rows][64] bf16
         if (t_trace) trace(tag, p, 64, 128, 128, 4, (size_t)np * 128, np / 64, s);
@@ -900,15 +877,15 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     auto upload_layout = [&]() -> int {
         // segments, live-row mask / row -> segment map, self and cross attention tasks
         att.build(segs);
-        if (!mlg_upload(SEGS, segs, s) || !mlg_upload(TASKS, att.tasks, s) || !mlg_upload(OUTOFF, att.out_off, s))
+        if (!mlg_upload(b.SEGS, segs, s) || !mlg_upload(b.TASKS, att.tasks, s) || !mlg_upload(b.OUTOFF, att.out_off, s))
             return MLG_EHIP;
-        hipLaunchKernelGGL(k_pair_live<int*>, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, (int)segs.size(), LIVE,
-                           ROWSEG, Npad);
+        hipLaunchKernelGGL(k_pair_live<int*>, dim3((Npad + 255) / 256), dim3(256), 0, s, b.SEGS, (int)segs.size(),
+                           b.LIVE, b.ROWSEG, Npad);
         MLG_LAUNCH_CHECK();
-        tr_tab(tl * 100 + 3, SEGS, segs.size() * sizeof(Seg));
-        tr_tab(tl * 100 + 4, TASKS, att.tasks.size() * sizeof(int4));
-        tr_tab(tl * 100 + 5, OUTOFF, att.out_off.size() * sizeof(int));
-        tr_rows(tl * 100 + 6, LIVE, 1, Npad);
+        tr_tab(tl * 100 + 3, b.SEGS, segs.size() * sizeof(Seg));
+        tr_tab(tl * 100 + 4, b.TASKS, att.tasks.size() * sizeof(int4));
+        tr_tab(tl * 100 + 5, b.OUTOFF, att.out_off.size() * sizeof(int));
+        tr_rows(tl * 100 + 6, b.LIVE, 1, Npad);
         return MLG_OK;
     };
     // One self block on the uploaded layout's first `nt` (self) tasks: q / k / v projection
@@ -919,16 +896,16 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
                           const int* outoff, int nt, int np, int mq, double tok, double work, int tag) -> int {
         {
             MlgProfScope prof(6, s, 2.0 * tok * 768 * 256);
-            MLG_TRY(mlg_lg_proj(true, cat, 512, bw.Wqkv, bw.bqkv, (const float*)ef, LIVE, Q, K, VT, np, s));
+            MLG_TRY(mlg_lg_proj(true, cat, 512, bw.Wqkv, bw.bqkv, (const float*)ef, b.LIVE, b.Q, b.K, b.VT, np, s));
         }
-        tr_heads(tag + 10, Q, np);
-        tr_heads(tag + 11, K, np);
-        tr_heads(tag + 12, VT, np);
+        tr_heads(tag + 10, b.Q, np);
+        tr_heads(tag + 11, b.K, np);
+        tr_heads(tag + 12, b.VT, np);
         {
             MlgProfScope prof(5, s, work);
-            MLG_TRY(mlg_attention_varlen(Q, K, VT, CTX, LG_D, np, LG_H, tasks, outoff, nt, mq, s));
+            MLG_TRY(mlg_attention_varlen(b.Q, b.K, b.VT, b.CTX, LG_D, np, LG_H, tasks, outoff, nt, mq, s));
         }
-        tr_rows(tag + 13, CTX, 512, np);
+        tr_rows(tag + 13, b.CTX, 512, np);
         {
             // algorithmic FLOPs per live token: 2 (256 x 256 + 512 x 512 + 256 x 512) = 917,504.
             // Its HBM bytes per token (ctx + bf16 x in 512 + 512, f32 x read + written 1024 +
@@ -936,7 +913,7 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             // 312): the three GEMM phases, not HBM, bound it, so the slot is
             // priced against the MFMA peak
             MlgProfScope prof(8, s, 917504.0 * tok);
-            MLG_TRY(mlg_lg_ffn(CTX, x, cat, 512, np, bw, s, nullptr));
+            MLG_TRY(mlg_lg_ffn(b.CTX, x, cat, 512, np, bw, s, nullptr));
         }
         tr_rows(tag + 14, x, LG_D * 4, np);
         tr_rows(tag + 15, cat, 512, np, 1024);
@@ -950,30 +927,30 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     const bool self0_done = fp.repeats;
     if (fp.repeats) {
         const int nf = (int)fp.fsegs.size(), NpadF = fp.NpadF;
-        if (!mlg_upload(SEGS, fp.fsegs, s) || !mlg_upload(TASKS, fp.tasks, s) || !mlg_upload(OUTOFF, fp.out_off, s) ||
-            !mlg_upload(MOVES, fp.moves, s))
+        if (!mlg_upload(b.SEGS, fp.fsegs, s) || !mlg_upload(b.TASKS, fp.tasks, s) ||
+            !mlg_upload(b.OUTOFF, fp.out_off, s) || !mlg_upload(b.MOVES, fp.moves, s))
             return MLG_EHIP;
-        hipLaunchKernelGGL(k_pair_live<int*>, dim3((NpadF + 255) / 256), dim3(256), 0, s, SEGS, nf, LIVE, ROWSEG,
+        hipLaunchKernelGGL(k_pair_live<int*>, dim3((NpadF + 255) / 256), dim3(256), 0, s, b.SEGS, nf, b.LIVE, b.ROWSEG,
                            NpadF);
-        hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)nf), dim3(256), 0, s, SEGS, kpts, kmax,
-                           (float4*)(base + L.norm));
-        hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)nf), dim3(256), 0, s, SEGS,
-                           (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X2, CAT2, EF2, IND2);
+        hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)nf), dim3(256), 0, s, b.SEGS, kpts, kmax, b.NORM);
+        hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)nf), dim3(256), 0, s, b.SEGS,
+                           (const float4*)b.NORM, kpts, desc, kmax, w.Wr, b.X2, b.CAT2, b.EF2, b.IND2);
         MLG_LAUNCH_CHECK();
-        tr_tab(9903, SEGS, fp.fsegs.size() * sizeof(Seg));
-        tr_tab(9904, TASKS, fp.tasks.size() * sizeof(int4));
-        tr_rows(9901, X2, LG_D * 4, NpadF);
-        tr_rows(9902, CAT2, 512, NpadF, 1024);
-        MLG_TRY(self_block(w.self[0], X2, CAT2, EF2, TASKS, OUTOFF, nf, NpadF, fp.maxqf, fp.tok, fp.work, 9900));
+        tr_tab(9903, b.SEGS, fp.fsegs.size() * sizeof(Seg));
+        tr_tab(9904, b.TASKS, fp.tasks.size() * sizeof(int4));
+        tr_rows(9901, b.X2, LG_D * 4, NpadF);
+        tr_rows(9902, b.CAT2, 512, NpadF, 1024);
+        MLG_TRY(self_block(w.self[0], b.X2, b.CAT2, b.EF2, b.TASKS, b.OUTOFF, nf, NpadF, fp.maxqf, fp.tok, fp.work,
+                           9900));
     }
     MLG_TRY(upload_layout());
-    hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)segs.size()), dim3(256), 0, s, SEGS, kpts, kmax, (float4*)(base + L.norm));
-    hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)segs.size()), dim3(256), 0, s, SEGS,
-                       (const float4*)(base + L.norm), kpts, desc, kmax, w.Wr, X, CAT, EF, IND,
-                       self0_done ? (const int4*)MOVES : nullptr, X2, CAT2);
+    hipLaunchKernelGGL(k_lg_kpnorm, dim3((unsigned)segs.size()), dim3(256), 0, s, b.SEGS, kpts, kmax, b.NORM);
+    hipLaunchKernelGGL(k_lg_init, dim3((unsigned)((kmax + 63) / 64), (unsigned)segs.size()), dim3(256), 0, s, b.SEGS,
+                       (const float4*)b.NORM, kpts, desc, kmax, w.Wr, b.X, b.CAT, b.EF, b.IND,
+                       self0_done ? (const int4*)b.MOVES : nullptr, b.X2, b.CAT2);
     MLG_LAUNCH_CHECK();
-    tr_rows(1, X, LG_D * 4, Npad);
-    tr_rows(2, CAT, 512, Npad, 1024);
+    tr_rows(1, b.X, LG_D * 4, Npad);
+    tr_rows(2, b.CAT, 512, Npad, 1024);
 
     auto live_tokens = [&]() {
         double t = 0;
@@ -983,17 +960,17 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     auto attn_work = [&](bool cross) {  // 4 * heads * q * kv * 64 per task (QK^T and PV)
         double work = 0;
         for (size_t k = 0; k < segs.size(); k += 2) {
-            const double a = segs[k].len, b = segs[k + 1].len;
-            work += 4.0 * LG_H * 64 * (cross ? 2 * a * b : a * a + b * b);
+            const double la = segs[k].len, lb = segs[k + 1].len;
+            work += 4.0 * LG_H * 64 * (cross ? 2 * la * lb : la * la + lb * lb);
         }
         return work;
     };
     // assignment + filter of the listed segment pairs (k = index of image a's segment)
     auto assign = [&](int i, const std::vector<size_t>& ks) -> int {
         // mdesc = final_proj(x) for every token, as bf16 hi + lo; the 1/4 per side folds into S / 16
-        MLG_TRY(mlg_gemm_bias_split_bf16(CAT, 512, w.Wfinal[i], w.bfinal[i], MDH, MDH + (size_t)Npad * LG_D, Npad, LG_D,
-                                         LG_D, s));
-        if (t_trace) trace(i * 100 + 40, MDH, 64, 32, 32, 32, (size_t)Npad * 32, Npad / 64, s);
+        MLG_TRY(mlg_gemm_bias_split_bf16(b.CAT, 512, w.Wfinal[i], w.bfinal[i], b.MDH, b.MDH + (size_t)Npad * LG_D, Npad,
+                                         LG_D, LG_D, s));
+        if (t_trace) trace(i * 100 + 40, b.MDH, 64, 32, 32, 32, (size_t)Npad * 32, Npad / 64, s);
         // one table upload for all chunks (the per-layer statistics read-back orders its
         // reuse), so chunks follow each other without a host round trip
         h_asg.clear();
@@ -1004,7 +981,7 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             a.n = sb.len;
             a.ra = sa.off;
             a.rb = sb.off;
-            a.soff = (long)(c % L.asg_cap) * kmax * ((kmax + 3) & ~3);
+            a.soff = (long)(c % b.asg_cap) * kmax * ((kmax + 3) & ~3);
             a.pair = pair_of[ks[c] / 2];
             a.ld = (sb.len + 3) & ~3;
             a.lo_first = sa.frame > sb.frame;
@@ -1012,27 +989,28 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             h_asg.push_back(a);
             if (stop_layer) stop_layer[a.pair] = i + 1;
         }
-        if (!mlg_upload(ASG, h_asg, s)) return MLG_EHIP;
-        tr_tab(i * 100 + 41, ASG, h_asg.size() * sizeof(Asg));
-        for (size_t c0 = 0; c0 < ks.size(); c0 += L.asg_cap) {
-            const size_t c1 = std::min(ks.size(), c0 + L.asg_cap);
+        if (!mlg_upload(b.ASG, h_asg, s)) return MLG_EHIP;
+        tr_tab(i * 100 + 41, b.ASG, h_asg.size() * sizeof(Asg));
+        for (size_t c0 = 0; c0 < ks.size(); c0 += b.asg_cap) {
+            const size_t c1 = std::min(ks.size(), c0 + b.asg_cap);
             int maxm = 0, maxn = 0;
             for (size_t c = c0; c < c1; ++c) {
                 maxm = std::max(maxm, h_asg[c].m);
                 maxn = std::max(maxn, h_asg[c].n);
             }
             const unsigned na = (unsigned)(c1 - c0);
-            const Asg* tab = ASG + c0;
+            const Asg* tab = b.ASG + c0;
             const dim3 stiles((maxn + SBM - 1) / SBM, (maxm + SBM - 1) / SBM, na),
                 atiles((maxn + ARN - 1) / ARN, (maxm + ARM - 1) / ARM, na),
                 lines((std::max(maxm, maxn) + 255) / 256, na, 2);
-            hipLaunchKernelGGL(k_asg_sim, stiles, dim3(256), 0, s, tab, MDH, MDH + (size_t)Npad * LG_D, Npad, SS, PART,
-                               kmax);
-            hipLaunchKernelGGL(k_asg_stats, lines, dim3(256), 0, s, tab, PART, kmax, RMAX, RLOG, CMAX, CLOG);
-            hipLaunchKernelGGL(k_asg_arg, atiles, dim3(256), 0, s, tab, SS, RMAX, RLOG, CMAX, CLOG, LZ, PART, kmax);
-            hipLaunchKernelGGL(k_asg_argfinal, lines, dim3(256), 0, s, tab, PART, kmax, ARG, VAL);
-            hipLaunchKernelGGL(k_lg_filter, dim3(na), dim3(256), 0, s, tab, ARG, VAL, IND, filter_thr, kmax, matches,
-                               mscores, nmatch);
+            hipLaunchKernelGGL(k_asg_sim, stiles, dim3(256), 0, s, tab, b.MDH, b.MDH + (size_t)Npad * LG_D, Npad, b.SS,
+                               b.PART, kmax);
+            hipLaunchKernelGGL(k_asg_stats, lines, dim3(256), 0, s, tab, b.PART, kmax, b.RMAX, b.RLOG, b.CMAX, b.CLOG);
+            hipLaunchKernelGGL(k_asg_arg, atiles, dim3(256), 0, s, tab, b.SS, b.RMAX, b.RLOG, b.CMAX, b.CLOG, b.LZ,
+                               b.PART, kmax);
+            hipLaunchKernelGGL(k_asg_argfinal, lines, dim3(256), 0, s, tab, b.PART, kmax, b.ARG, b.VAL);
+            hipLaunchKernelGGL(k_lg_filter, dim3(na), dim3(256), 0, s, tab, b.ARG, b.VAL, b.IND, filter_thr, kmax,
+                               matches, mscores, nmatch);
             MLG_LAUNCH_CHECK();
         }
         return MLG_OK;
@@ -1043,38 +1021,39 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         const int nt = (int)segs.size();
         // self block (layer 0's already ran per frame above when frames repeat)
         if (!(i == 0 && self0_done))
-            MLG_TRY(self_block(w.self[i], X, CAT, EF, TASKS, OUTOFF, nt, Npad, att.maxq, live_tokens(), attn_work(false),
-                               i * 100));
+            MLG_TRY(self_block(w.self[i], b.X, b.CAT, b.EF, b.TASKS, b.OUTOFF, nt, Npad, att.maxq, live_tokens(),
+                               attn_work(false), i * 100));
         // cross block
         {
             MlgProfScope prof(6, s, 2.0 * live_tokens() * 512 * 256);
-            MLG_TRY(mlg_lg_proj(false, CAT, 512, w.cross[i].Wqkv, w.cross[i].bqkv, nullptr, LIVE, Q, nullptr, VT,
-                                Npad, s));
+            MLG_TRY(mlg_lg_proj(false, b.CAT, 512, w.cross[i].Wqkv, w.cross[i].bqkv, nullptr, b.LIVE, b.Q, nullptr,
+                                b.VT, Npad, s));
         }
-        tr_heads(i * 100 + 20, Q, Npad);
-        tr_heads(i * 100 + 21, VT, Npad);
+        tr_heads(i * 100 + 20, b.Q, Npad);
+        tr_heads(i * 100 + 21, b.VT, Npad);
         {
             MlgProfScope prof(5, s, attn_work(true));
-            MLG_TRY(mlg_attention_varlen(Q, Q, VT, CTX, LG_D, Npad, LG_H, TASKS + nt, OUTOFF + nt, nt, att.maxq, s));
+            MLG_TRY(mlg_attention_varlen(b.Q, b.Q, b.VT, b.CTX, LG_D, Npad, LG_H, b.TASKS + nt, b.OUTOFF + nt, nt,
+                                         att.maxq, s));
         }
-        tr_rows(i * 100 + 22, CTX, 512, Npad);
+        tr_rows(i * 100 + 22, b.CTX, 512, Npad);
         // layer i's heads on the updated tokens: matchability log-sigmoid (the assignment's
         // certainty term) and, before the last layer, confidences + early-stop / prune flags
         const bool last = i == LG_L - 1;
-        const mlg_lg_conf_i heads{ROWSEG, last ? nullptr : w.wconf[i], last ? nullptr : w.bconf[i], w.wmatch[i],
+        const mlg_lg_conf_i heads{b.ROWSEG, last ? nullptr : w.wconf[i], last ? nullptr : w.bconf[i], w.wmatch[i],
                                   w.bmatch[i], last ? 0.f : (depth_conf > 0.f ? conf_threshold(i) : -INFINITY),
-                                  width_conf, LZ, KEEP};
+                                  width_conf, b.LZ, b.KEEP};
         // (depth_confidence <= 0: upstream computes no token confidences, so its pruning
         // mask is matchability alone -- a threshold of -inf drops the "low confidence is
         // never pruned" term; the stop bit is unused then)
         {
             MlgProfScope prof(8, s, 917504.0 * live_tokens());  // priced as the self block's tail
-            MLG_TRY(mlg_lg_ffn(CTX, X, CAT, 512, Npad, w.cross[i], s, &heads));  // + the heads, fused into the tail
+            MLG_TRY(mlg_lg_ffn(b.CTX, b.X, b.CAT, 512, Npad, w.cross[i], s, &heads));  // + the heads, fused in the tail
         }
-        tr_rows(i * 100 + 23, X, LG_D * 4, Npad);
-        tr_rows(i * 100 + 24, CAT, 512, Npad, 1024);
-        tr_rows(i * 100 + 25, LZ, 4, Npad);
-        if (!last) tr_rows(i * 100 + 26, KEEP, 1, Npad);
+        tr_rows(i * 100 + 23, b.X, LG_D * 4, Npad);
+        tr_rows(i * 100 + 24, b.CAT, 512, Npad, 1024);
+        tr_rows(i * 100 + 25, b.LZ, 4, Npad);
+        if (!last) tr_rows(i * 100 + 26, b.KEEP, 1, Npad);
 
         if (last) {
             std::vector<size_t> ks;
@@ -1082,10 +1061,10 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
             MLG_TRY(assign(i, ks));
             break;
         }
-        hipLaunchKernelGGL(k_lg_segstats, dim3((unsigned)segs.size()), dim3(256), 0, s, SEGS, KEEP, STATS);
+        hipLaunchKernelGGL(k_lg_segstats, dim3((unsigned)segs.size()), dim3(256), 0, s, b.SEGS, b.KEEP, b.STATS);
         MLG_LAUNCH_CHECK();
-        tr_tab(i * 100 + 27, STATS, segs.size() * 2 * sizeof(int));
-        if (hipMemcpyAsync(stats.data(), STATS, segs.size() * 2 * sizeof(int), hipMemcpyDeviceToHost, s) !=
+        tr_tab(i * 100 + 27, b.STATS, segs.size() * 2 * sizeof(int));
+        if (hipMemcpyAsync(stats.data(), b.STATS, segs.size() * 2 * sizeof(int), hipMemcpyDeviceToHost, s) !=
                 hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return MLG_EHIP;
@@ -1096,14 +1075,14 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         // compact: drop stopped pairs, prune segments above the threshold
         if (!dec.moves.empty()) {
             if (!dec.stopped.empty() && hipStreamSynchronize(s) != hipSuccess) return MLG_EHIP;  // h_asg in flight
-            if (!mlg_upload(MOVES, dec.moves, s)) return MLG_EHIP;
-            hipLaunchKernelGGL(k_lg_compact, dim3((unsigned)dec.moves.size()), dim3(256), 0, s, MOVES, KEEP, X, EF,
-                               IND, X2, CAT2, EF2, IND2);
+            if (!mlg_upload(b.MOVES, dec.moves, s)) return MLG_EHIP;
+            hipLaunchKernelGGL(k_lg_compact, dim3((unsigned)dec.moves.size()), dim3(256), 0, s, b.MOVES, b.KEEP, b.X,
+                               b.EF, b.IND, b.X2, b.CAT2, b.EF2, b.IND2);
             MLG_LAUNCH_CHECK();
-            std::swap(X, X2);
-            std::swap(CAT, CAT2);
-            std::swap(EF, EF2);
-            std::swap(IND, IND2);
+            std::swap(b.X, b.X2);
+            std::swap(b.CAT, b.CAT2);
+            std::swap(b.EF, b.EF2);
+            std::swap(b.IND, b.IND2);
         }
         // the old layout's upload completed before the read-back above: its vectors may go
         segs.swap(dec.segs);
@@ -1112,9 +1091,9 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
         if (stop_layer)
             for (const auto& pl : dec.stop_layer) stop_layer[pl.first] = pl.second;
         tl = i + 1;
-        if (!dec.moves.empty()) tr_tab(tl * 100 + 31, MOVES, dec.moves.size() * sizeof(int4));
+        if (!dec.moves.empty()) tr_tab(tl * 100 + 31, b.MOVES, dec.moves.size() * sizeof(int4));
         if (!segs.empty()) MLG_TRY(upload_layout());
-        if (!dec.moves.empty() && !segs.empty()) tr_rows(tl * 100 + 30, X, LG_D * 4, Npad);
+        if (!dec.moves.empty() && !segs.empty()) tr_rows(tl * 100 + 30, b.X, LG_D * 4, Npad);
         stats.assign(segs.size() * 2, 0);
     }
     if (t_trace) {

@@ -43,6 +43,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "pair_plan.h"
+#include "ws_carve.h"
 #include "../../include/mlgate.h"
 
 namespace {
@@ -913,8 +914,6 @@ __global__ __launch_bounds__(64) void k_lf_fine_match(const float* __restrict__ 
     }
 }
 
-using pair_plan::a256;
-
 struct ConvSpec {
     int cin, cout, k, s;
 };
@@ -926,30 +925,32 @@ constexpr ConvSpec CONVS[MLG_LOFTR_NCONV] = {
     {256, 256, 1, 1}, {256, 256, 1, 1}, {256, 256, 3, 1}, {256, 256, 3, 1},                    // FPN 1/4
     {128, 256, 1, 1}, {256, 256, 3, 1}, {256, 128, 3, 1}};                                     // FPN 1/2
 
-struct FeatLayout {
-    size_t xf, xb, yb, rf, tf, zero, c3, c2, gray, total;
+struct FeatBufs {
+    float* xf;     // residual stream f32 (up to 256 channels)
+    bf16_t* xb;    // its bf16 copy
+    bf16_t* yb;    // block-internal bf16 activation
+    float* rf;     // shortcut / lateral f32
+    float* tf;     // FPN f32 temporaries
+    bf16_t* zero;  // zero bytes: the convs' padding taps
+    float* c2;     // layer2 output f32 (1/4) kept for the FPN
+    uint8_t* gray; // resized gray frames (H, W not multiples of 8)
 };
 
-FeatLayout feat_layout(int B, int H, int W) {
+size_t feat_carve(int B, int H, int W, void* base, FeatBufs* out) {
     const size_t P2 = (size_t)B * (H / 2) * (W / 2);  // 1/2-resolution pixels
-    FeatLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += a256(bytes);
-        return r;
-    };
-    L.xf = take(P2 * 256 * 4);   // residual stream f32 (up to 256 channels)
-    L.xb = take(P2 * 256 * 2);   // its bf16 copy
-    L.yb = take(P2 * 256 * 2);   // block-internal bf16 activation
-    L.rf = take(P2 * 256 * 4);   // shortcut / lateral f32
-    L.tf = take(P2 * 256 * 4);   // FPN f32 temporaries
-    L.zero = take(256);               // 16 zero bytes: the convs' padding taps
-    L.c3 = take(P2 / 16 * 256 * 4 + 256);  // layer3 output f32 (1/8)
-    L.c2 = take(P2 / 4 * 256 * 4 + 256);   // layer2 output f32 (1/4) kept for the FPN
-    L.gray = take(P2 * 4);                  // resized gray frames (H, W not multiples of 8)
-    L.total = o;
-    return L;
+    WsCarver c(base);
+    FeatBufs b;
+    b.xf = c.take<float>(P2 * 256);
+    b.xb = c.take<bf16_t>(P2 * 256);
+    b.yb = c.take<bf16_t>(P2 * 256);
+    b.rf = c.take<float>(P2 * 256);
+    b.tf = c.take<float>(P2 * 256);
+    b.zero = c.take<bf16_t>(128);
+    c.take<float>(P2 / 16 * 256 + 64);  // layer3 output f32 (1/8): no longer used, the size stays
+    b.c2 = c.take<float>(P2 / 4 * 256 + 64);
+    b.gray = c.take<uint8_t>(P2 * 4);
+    if (out) *out = b;
+    return c.total();
 }
 
 int conv(const mlg_loftr_weights& w, int idx, const bf16_t* in, int B, int H, int W, const bf16_t* zero,
@@ -1005,7 +1006,7 @@ int fpn_merge(const mlg_loftr_weights& w, int idx, const bf16_t* in, int B, int 
 
 size_t mlg_loftr_features_ws_bytes(int B, int H, int W) {
     if (B <= 0 || H < 32 || W < 32) return 0;
-    return feat_layout(B, H / 8 * 8, W / 8 * 8).total;
+    return feat_carve(B, H / 8 * 8, W / 8 * 8, nullptr, nullptr);
 }
 
 int mlg_loftr_features(const mlg_loftr_weights* wp, const uint8_t* frames_in, int B, int H_in, int W_in, int C,
@@ -1014,14 +1015,14 @@ int mlg_loftr_features(const mlg_loftr_weights* wp, const uint8_t* frames_in, in
         (C != 1 && C != 3 && C != 4))
         return MLG_EINVAL;
     const int H = H_in / 8 * 8, W = W_in / 8 * 8;
-    const FeatLayout L = feat_layout(B, H, W);
-    if (ws_bytes < L.total) return MLG_ENOMEM;
+    FeatBufs b;
+    if (feat_carve(B, H, W, ws, &b) > ws_bytes) return MLG_ENOMEM;
     const uint8_t* frames = frames_in;
     if (H != H_in || W != W_in) {  // cv2 gray + INTER_LINEAR resize to multiples of 8
         int vend = 0;  // first byte of a row in the vertical pass's scalar tail
         for (; vend <= W - 16; vend += 16) {}
         for (; vend < W - 8; vend += 8) {}
-        uint8_t* g = (uint8_t*)ws + L.gray;
+        uint8_t* g = b.gray;
         const long n = (long)B * H * W;
         hipLaunchKernelGGL(k_lf_gray_resize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            frames_in, frame_stride, H_in, W_in, C, H, W, vend, g, B);
@@ -1032,48 +1033,38 @@ int mlg_loftr_features(const mlg_loftr_weights* wp, const uint8_t* frames_in, in
     }
     const mlg_loftr_weights& w = *wp;
     hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    float* xf = (float*)(base + L.xf);
-    bf16_t* xb = (bf16_t*)(base + L.xb);
-    bf16_t* yb = (bf16_t*)(base + L.yb);
-    float* rf = (float*)(base + L.rf);
-    float* tf = (float*)(base + L.tf);
-    const bf16_t* zero = (const bf16_t*)(base + L.zero);
-    if (hipMemsetAsync(base + L.zero, 0, 256, (hipStream_t)stream) != hipSuccess) return MLG_EHIP;
-    float* c3 = (float*)(base + L.c3);
-    float* c2 = (float*)(base + L.c2);
+    if (hipMemsetAsync(b.zero, 0, 256, (hipStream_t)stream) != hipSuccess) return MLG_EHIP;
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
     hipLaunchKernelGGL(k_lf_stem, dim3((W2 + 15) / 16, (H2 + 7) / 8, B), dim3(256), 0, s, frames, frame_stride, H, W,
-                       C, w.stem_w, w.stem_b, xf, xb);
+                       C, w.stem_w, w.stem_b, b.xf, b.xb);
     MLG_LAUNCH_CHECK();
     // layer1 (1/2, 128)
-    MLG_TRY(basic_block(w, 0, 1, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
-    MLG_TRY(basic_block(w, 2, 3, -1, B, H2, W2, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 0, 1, -1, B, H2, W2, b.xf, b.xb, b.yb, b.rf, b.zero, s));
+    MLG_TRY(basic_block(w, 2, 3, -1, B, H2, W2, b.xf, b.xb, b.yb, b.rf, b.zero, s));
     // x1 (bf16) is needed by the FPN: kept in `fine` (scratch until the end: fine is
     // written last)
     bf16_t* x1b = (bf16_t*)fine;
-    if (hipMemcpyAsync(x1b, xb, (size_t)B * H2 * W2 * 128 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    if (hipMemcpyAsync(x1b, b.xb, (size_t)B * H2 * W2 * 128 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return MLG_EHIP;
     // layer2 (1/4, 256p)
-    MLG_TRY(basic_block(w, 4, 5, 6, B, H2, W2, xf, xb, yb, rf, zero, s));
-    MLG_TRY(basic_block(w, 7, 8, -1, B, H4, W4, xf, xb, yb, rf, zero, s));
-    bf16_t* x2b = (bf16_t*)c2;  // bf16 copy of x2 (c2 is free until the FPN needs its f32 slot)
-    if (hipMemcpyAsync(x2b, xb, (size_t)B * H4 * W4 * 256 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    MLG_TRY(basic_block(w, 4, 5, 6, B, H2, W2, b.xf, b.xb, b.yb, b.rf, b.zero, s));
+    MLG_TRY(basic_block(w, 7, 8, -1, B, H4, W4, b.xf, b.xb, b.yb, b.rf, b.zero, s));
+    bf16_t* x2b = (bf16_t*)b.c2;  // bf16 copy of x2 (b.c2 is free until the FPN needs its f32 slot)
+    if (hipMemcpyAsync(x2b, b.xb, (size_t)B * H4 * W4 * 256 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return MLG_EHIP;
     // layer3 (1/8, 256)
-    MLG_TRY(basic_block(w, 9, 10, 11, B, H4, W4, xf, xb, yb, rf, zero, s));
-    MLG_TRY(basic_block(w, 12, 13, -1, B, H8, W8, xf, xb, yb, rf, zero, s));
+    MLG_TRY(basic_block(w, 9, 10, 11, B, H4, W4, b.xf, b.xb, b.yb, b.rf, b.zero, s));
+    MLG_TRY(basic_block(w, 12, 13, -1, B, H8, W8, b.xf, b.xb, b.yb, b.rf, b.zero, s));
     // FPN: x3_out = outconv3(x3) -> coarse output (f32)
-    MLG_TRY(conv(w, 14, xb, B, H8, W8, zero, nullptr, coarse, nullptr, 0, s));
+    MLG_TRY(conv(w, 14, b.xb, B, H8, W8, b.zero, nullptr, coarse, nullptr, 0, s));
     // x2_out = outconv2(x2) + up(x3_out) -> bf16 -> conv + BN + leaky -> conv
-    MLG_TRY(fpn_merge(w, 15, x2b, B, H4, W4, coarse, tf, yb, s));
-    MLG_TRY(conv(w, 16, yb, B, H4, W4, zero, nullptr, nullptr, xb, 2, s));
-    MLG_TRY(conv(w, 17, xb, B, H4, W4, zero, nullptr, c2, nullptr, 0, s));  // x2_out f32 (1/4, 256p)
+    MLG_TRY(fpn_merge(w, 15, x2b, B, H4, W4, coarse, b.tf, b.yb, s));
+    MLG_TRY(conv(w, 16, b.yb, B, H4, W4, b.zero, nullptr, nullptr, b.xb, 2, s));
+    MLG_TRY(conv(w, 17, b.xb, B, H4, W4, b.zero, nullptr, b.c2, nullptr, 0, s));  // x2_out f32 (1/4, 256p)
     // x1_out = outconv1(x1) + up(x2_out) -> conv + BN + leaky -> conv -> fine
-    MLG_TRY(fpn_merge(w, 18, x1b, B, H2, W2, c2, tf, yb, s));
-    MLG_TRY(conv(w, 19, yb, B, H2, W2, zero, nullptr, nullptr, xb, 2, s));
-    MLG_TRY(conv(w, 20, xb, B, H2, W2, zero, nullptr, fine, nullptr, 0, s));
-    (void)c3;
+    MLG_TRY(fpn_merge(w, 18, x1b, B, H2, W2, b.c2, b.tf, b.yb, s));
+    MLG_TRY(conv(w, 19, b.yb, B, H2, W2, b.zero, nullptr, nullptr, b.xb, 2, s));
+    MLG_TRY(conv(w, 20, b.xb, B, H2, W2, b.zero, nullptr, fine, nullptr, 0, s));
     return MLG_OK;
 }
 
@@ -1268,85 +1259,91 @@ int pack_tails(const mlg_loftr_weights& w, char* base, TailW (&tw)[8], hipStream
     return MLG_OK;
 }
 
-struct MatchLayout {
-    size_t cx, ccat, cqkv, cmsg, ct, ch, ckv, cks, ckvp;  // coarse transformer (rows 2 P L, d 256)
-    size_t fx, fcat, fqkv, fmsg, ft, fh, fkv, fks;  // fine transformer (rows 2 C 25, d 128)
-    size_t win, crow, cd, cm, S, csplit, rmax, rsum, rkey, cmax, csum, ckey, pm, pz, prm, bval, bidx, cbest, mi, mj, mconf, cnt,
-        frm, ufr, umap, mp, ms, tails, total;
-};
+// a transformer's scratch behind its token buffers x / cat (rows tokens of width d, nseg
+// segments of L tokens each; kvp: with the chunked K^T V partial sums)
+void layer_carve(WsCarver& c, size_t rows, size_t nseg, int L, int d, bool kvp, LayerBufs* b) {
+    const size_t dh = (size_t)d / 8;
+    b->qkv = c.take<float>(rows * 3 * d);
+    b->msg = c.take<bf16_t>(rows * d);
+    b->t = c.take<float>(rows * d);
+    b->h = c.take<bf16_t>(rows * 2 * d);
+    b->kv = c.take<float>(nseg * 8 * dh * dh);
+    b->ks = c.take<float>(nseg * 8 * dh);
+    b->kvp = kvp ? c.take<float>(nseg * 8 * ((L + LF_KV_CHUNK - 1) / LF_KV_CHUNK) * (dh * dh + dh)) : nullptr;
+}
 
 constexpr int FINE_CHUNK = 4096;  // matches per fine-stage pass
 
-MatchLayout match_layout(int P, int L) {
-    MatchLayout M{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += a256(bytes);
-        return r;
-    };
+struct MatchBufs {
+    LayerBufs bc;  // coarse transformer (rows 2 P L, d 256)
+    LayerBufs bf;  // fine transformer (rows 2 C 25, d 128)
+    bf16_t *win, *crow, *cd;
+    float *cm, *S;
+    bf16_t* csplit;
+    float *rmax, *rsum, *rkey, *cmax, *csum, *ckey, *pm, *pz, *prm, *bval;
+    int32_t* bidx;
+    float* cbest;
+    int32_t *mi, *mj;
+    float* mconf;
+    int32_t *cnt, *frm, *ufr, *umap, *mp, *ms;
+    char* tails;
+};
+
+size_t match_carve(int P, int L, void* base, MatchBufs* out) {
+    WsCarver c(base);
+    MatchBufs M;
     const size_t rc = (size_t)2 * P * L, rf = (size_t)2 * FINE_CHUNK * 25;
-    M.cx = take(rc * 256 * 4);
-    M.ccat = take(rc * 512 * 2);
-    M.cqkv = take(rc * 768 * 4);
-    M.cmsg = take(rc * 256 * 2);
-    M.ct = take(rc * 256 * 4);
-    M.ch = take(rc * 512 * 2);
-    M.ckv = take((size_t)2 * P * 8 * 32 * 32 * 4);
-    M.cks = take((size_t)2 * P * 8 * 32 * 4);
-    M.ckvp = take((size_t)2 * P * 8 * ((L + LF_KV_CHUNK - 1) / LF_KV_CHUNK) * (32 * 32 + 32) * 4);
-    M.fx = take(rf * 128 * 4);
-    M.fcat = take(rf * 256 * 2);
-    M.fqkv = take(rf * 384 * 4);
-    M.fmsg = take(rf * 128 * 2);
-    M.ft = take(rf * 128 * 4);
-    M.fh = take(rf * 256 * 2);
-    M.fkv = take((size_t)2 * FINE_CHUNK * 8 * 16 * 16 * 4);
-    M.fks = take((size_t)2 * FINE_CHUNK * 8 * 16 * 4);
-    M.win = take(rf * 128 * 2);
-    M.crow = take((size_t)2 * FINE_CHUNK * 256 * 2);
-    M.cd = take((size_t)2 * FINE_CHUNK * 128 * 2);
-    M.cm = take((size_t)2 * FINE_CHUNK * 128 * 4);
+    M.bc.x = c.take<float>(rc * 256);
+    M.bc.cat = c.take<bf16_t>(rc * 512);
+    layer_carve(c, rc, (size_t)2 * P, L, 256, true, &M.bc);
+    M.bf.x = c.take<float>(rf * 128);
+    M.bf.cat = c.take<bf16_t>(rf * 256);
+    layer_carve(c, rf, (size_t)2 * FINE_CHUNK, 25, 128, false, &M.bf);
+    M.win = c.take<bf16_t>(rf * 128);
+    M.crow = c.take<bf16_t>((size_t)2 * FINE_CHUNK * 256);
+    M.cd = c.take<bf16_t>((size_t)2 * FINE_CHUNK * 128);
+    M.cm = c.take<float>((size_t)2 * FINE_CHUNK * 128);
     const size_t G = (size_t)std::min(P, MLG_LF_PGRP);  // pairs per dual-softmax group
     const size_t Lp = (size_t)(L + 3) / 4 * 4;          // S / ckey row stride (split path)
-    M.S = take(G * L * Lp * 4);
+    M.S = c.take<float>(G * L * Lp);
     // the coarse features as split-bf16 rows [hi | lo] (+ 256 zero rows: the similarity
     // GEMM reads B rows up to its 256-column tile), in the q / k / v buffer, which the
     // coarse transformer no longer needs when the similarity runs (3x larger: 2 P L x 768 f32)
-    const size_t csplit_bytes = ((size_t)2 * P * L + 256) * 512 * 2;
-    M.csplit = csplit_bytes <= rc * 768 * 4 ? M.cqkv : take(csplit_bytes);
-    M.rmax = take(G * L * 4);
-    M.rsum = take(G * L * 4);
-    M.rkey = take(G * L * 4);
-    M.cmax = take(G * L * 4);
-    M.csum = take(G * L * 4);
-    M.ckey = take(G * Lp * 4);
+    const size_t csplit_elems = (rc + 256) * 512;
+    M.csplit = csplit_elems * sizeof(bf16_t) <= rc * 768 * sizeof(float) ? (bf16_t*)M.bc.qkv
+                                                                         : c.take<bf16_t>(csplit_elems);
+    M.rmax = c.take<float>(G * L);
+    M.rsum = c.take<float>(G * L);
+    M.rkey = c.take<float>(G * L);
+    M.cmax = c.take<float>(G * L);
+    M.csum = c.take<float>(G * L);
+    M.ckey = c.take<float>(G * Lp);
     const size_t nrch = (size_t)(L + LF_RCH - 1) / LF_RCH;
-    M.pm = take(G * nrch * L * 4);
-    M.pz = take(G * nrch * L * 4);
-    M.prm = take(G * ((L + 255) / 256) * L * 4);
-    M.bval = take(G * L * 4);
-    M.bidx = take(G * L * 4);
-    M.cbest = take(G * L * 4);
-    M.mi = take((size_t)P * L * 4);
-    M.mj = take((size_t)P * L * 4);
-    M.mconf = take((size_t)P * L * 4);
-    M.cnt = take((size_t)P * 4);
-    M.frm = take((size_t)2 * P * 4);
-    M.ufr = take((size_t)2 * P * 4);
-    M.umap = take((size_t)2 * P * 4);
-    M.mp = take((size_t)FINE_CHUNK * 4);
-    M.ms = take((size_t)FINE_CHUNK * 4);
-    M.tails = take(TAILS_BYTES);
-    M.total = o;
-    return M;
+    M.pm = c.take<float>(G * nrch * L);
+    M.pz = c.take<float>(G * nrch * L);
+    M.prm = c.take<float>(G * ((L + 255) / 256) * L);
+    M.bval = c.take<float>(G * L);
+    M.bidx = c.take<int32_t>(G * L);
+    M.cbest = c.take<float>(G * L);
+    M.mi = c.take<int32_t>((size_t)P * L);
+    M.mj = c.take<int32_t>((size_t)P * L);
+    M.mconf = c.take<float>((size_t)P * L);
+    M.cnt = c.take<int32_t>((size_t)P);
+    M.frm = c.take<int32_t>((size_t)2 * P);
+    M.ufr = c.take<int32_t>((size_t)2 * P);
+    M.umap = c.take<int32_t>((size_t)2 * P);
+    M.mp = c.take<int32_t>((size_t)FINE_CHUNK);
+    M.ms = c.take<int32_t>((size_t)FINE_CHUNK);
+    M.tails = c.take<char>(TAILS_BYTES);
+    if (out) *out = M;
+    return c.total();
 }
 
 }  // namespace
 
 size_t mlg_loftr_match_ws_bytes(int P, int H, int W) {
     if (P <= 0 || H < 32 || W < 32 || (H % 8) || (W % 8)) return 0;
-    return match_layout(P, (H / 8) * (W / 8)).total;
+    return match_carve(P, (H / 8) * (W / 8), nullptr, nullptr);
 }
 
 int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const float* fine, int H, int W,
@@ -1356,41 +1353,12 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         H < 32 || W < 32 || (H % 8) || (W % 8))
         return MLG_EINVAL;
     const int hc = H / 8, wc = W / 8, L = hc * wc, Hf = H / 2, Wf = W / 2;
-    const MatchLayout ML = match_layout(P, L);
-    if (ws_bytes < ML.total) return MLG_ENOMEM;
+    MatchBufs b;
+    if (match_carve(P, L, ws, &b) > ws_bytes) return MLG_ENOMEM;
     const mlg_loftr_weights& w = *wp;
     hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)ws;
-    auto at = [&](size_t off) { return (void*)(base + off); };
-    const LayerBufs bc{(float*)at(ML.cx), (bf16_t*)at(ML.ccat), (float*)at(ML.cqkv), (bf16_t*)at(ML.cmsg),
-                       (float*)at(ML.ct), (bf16_t*)at(ML.ch), (float*)at(ML.ckv), (float*)at(ML.cks), (float*)at(ML.ckvp)};
-    const LayerBufs bf{(float*)at(ML.fx), (bf16_t*)at(ML.fcat), (float*)at(ML.fqkv), (bf16_t*)at(ML.fmsg),
-                       (float*)at(ML.ft), (bf16_t*)at(ML.fh), (float*)at(ML.fkv), (float*)at(ML.fks), nullptr};
-    bf16_t* win = (bf16_t*)at(ML.win);
-    bf16_t* crow = (bf16_t*)at(ML.crow);
-    bf16_t* cd = (bf16_t*)at(ML.cd);
-    float* cm = (float*)at(ML.cm);
-    float* S = (float*)at(ML.S);
-    float* rmax = (float*)at(ML.rmax);
-    float* rsum = (float*)at(ML.rsum);
-    float* cmax = (float*)at(ML.cmax);
-    float* csum = (float*)at(ML.csum);
-    float* rkey = (float*)at(ML.rkey);
-    float* ckey = (float*)at(ML.ckey);
-    float* pm = (float*)at(ML.pm);
-    float* pz = (float*)at(ML.pz);
-    float* prm = (float*)at(ML.prm);
+    const LayerBufs &bc = b.bc, &bf = b.bf;
     const int nrch = (L + LF_RCH - 1) / LF_RCH, ncb = (L + 255) / 256;
-    float* bval = (float*)at(ML.bval);
-    int32_t* bidx = (int32_t*)at(ML.bidx);
-    float* cbest = (float*)at(ML.cbest);
-    int32_t* mi = (int32_t*)at(ML.mi);
-    int32_t* mj = (int32_t*)at(ML.mj);
-    float* mconf = (float*)at(ML.mconf);
-    int32_t* cnt = (int32_t*)at(ML.cnt);
-    int32_t* frm = (int32_t*)at(ML.frm);
-    int32_t* dmp = (int32_t*)at(ML.mp);
-    int32_t* dms = (int32_t*)at(ML.ms);
 
     // coarse tokens, side-major: side 0 = frames pa, side 1 = frames pb
     std::vector<int32_t> h_frames(2 * P);
@@ -1398,14 +1366,14 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
         h_frames[p] = pa[p];
         h_frames[P + p] = pb[p];
     }
-    if (hipMemcpyAsync(frm, h_frames.data(), h_frames.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    if (hipMemcpyAsync(b.frm, h_frames.data(), h_frames.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
         return MLG_EHIP;
     const long crows = (long)2 * P * L;
     TailW tails[8];
     if (w.coarse_tails)
         tails_at((char*)w.coarse_tails, tails);  // packed once (mlg_loftr_pack_tails)
     else
-        MLG_TRY(pack_tails(w, (char*)at(ML.tails), tails, s));
+        MLG_TRY(pack_tails(w, b.tails, tails, s));
     const TailW* tw = tails;
     // the distinct frames of the call (first-appearance order) and each pair side's index
     const pair_plan::Distinct uf = pair_plan::distinct_frames(h_frames.data(), h_frames.size());
@@ -1413,13 +1381,11 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     const std::vector<int32_t>& h_umap = uf.index;
     const int NU = (int)h_ufr.size();
     if (NU < 2 * P) {
-        int32_t* ufr = (int32_t*)at(ML.ufr);
-        int32_t* umap = (int32_t*)at(ML.umap);
-        if (hipMemcpyAsync(ufr, h_ufr.data(), (size_t)NU * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(umap, h_umap.data(), (size_t)2 * P * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        if (hipMemcpyAsync(b.ufr, h_ufr.data(), (size_t)NU * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(b.umap, h_umap.data(), (size_t)2 * P * 4, hipMemcpyHostToDevice, s) != hipSuccess)
             return MLG_EHIP;
         const long urows = (long)NU * L;
-        hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((urows * 64 + 255) / 256)), dim3(256), 0, s, coarse, ufr, L,
+        hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((urows * 64 + 255) / 256)), dim3(256), 0, s, coarse, b.ufr, L,
                            pe, bc.x, bc.cat, (int)urows);
         MLG_LAUNCH_CHECK();
         MLG_TRY(encoder_layer(w.coarse[0], bc, 256, 0, 0, NU, L, s, tw));
@@ -1431,11 +1397,11 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
                            urows, tx, tc);
         MLG_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_lf_gather_rows, dim3((unsigned)((crows * 96 + 255) / 256)), dim3(256), 0, s, tx, tc,
-                           umap, L, crows, bc.x, bc.cat);
+                           b.umap, L, crows, bc.x, bc.cat);
         MLG_LAUNCH_CHECK();
         MLG_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw, 1));
     } else {
-        hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((crows * 64 + 255) / 256)), dim3(256), 0, s, coarse, frm, L,
+        hipLaunchKernelGGL(k_lf_tokens, dim3((unsigned)((crows * 64 + 255) / 256)), dim3(256), 0, s, coarse, b.frm, L,
                            pe, bc.x, bc.cat, (int)crows);
         MLG_LAUNCH_CHECK();
         MLG_TRY(transformer(w.coarse, 8, bc, 256, P, L, s, tw));
@@ -1445,7 +1411,7 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     // writes 16-B row pieces, so its S rows are lds = L rounded up to 4 floats, the pad
     // columns -inf (EpiSimLoFTR): frames of L % 4 != 0 cells -- the ISEC 720 x 536, L =
     // 6030 -- take the split path too (round 6; before, the exact-f32 one)
-    bf16_t* CS = (bf16_t*)at(ML.csplit);
+    bf16_t* const CS = b.csplit;
     const int Lpad = (L + 255) / 256 * 256;
     const bool split = g_lf_sim_split != 0;
     const int lds = split ? (L + 3) / 4 * 4 : L;
@@ -1460,31 +1426,31 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     for (int p0 = 0; p0 < P; p0 += G) {
         const unsigned g = (unsigned)std::min(G, P - p0);
         if (split) {  // the group's g similarities as one tile queue
-            MLG_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p0 * L * 512, CS + ((size_t)P + p0) * L * 512, L, Lpad, 256, S,
-                                            lds, L, s, (int)g, (long)L * 512));
+            MLG_TRY(mlg_gemm_sim_split_loftr(CS + (size_t)p0 * L * 512, CS + ((size_t)P + p0) * L * 512, L, Lpad, 256,
+                                            b.S, lds, L, s, (int)g, (long)L * 512));
         } else {
             for (int q = 0; q < (int)g; ++q) {
                 const int p = p0 + q;
                 MLG_TRY(mlg_similarity_f32_loftr(bc.x + (size_t)p * L * 256, L, bc.x + ((size_t)P + p) * L * 256, L, 256,
-                                                S + (size_t)q * L * lds, L, s));
+                                                b.S + (size_t)q * L * lds, L, s));
             }
         }
         // three reads of S: stats, rowbest, colmaxpart
-        hipLaunchKernelGGL(k_lf_stats, dim3(ncb, nrch, g), dim3(256), 0, s, S, L, lds, pm, pz, prm);
-        hipLaunchKernelGGL(k_lf_colfin, dim3((L + 63) / 64, 1, g), dim3(256), 0, s, pm, pz, L, lds, nrch, cmax, csum,
-                           ckey);
-        hipLaunchKernelGGL(k_lf_rowbest, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, S, L, lds, rmax, rsum, rkey, prm,
-                           ncb, cmax, csum, ckey, bval, bidx);
-        hipLaunchKernelGGL(k_lf_colmaxpart, dim3((L + 255) / 256, nrch, g), dim3(256), 0, s, S, L, lds, rmax, rsum,
-                           rkey, cmax, csum, pm);
-        hipLaunchKernelGGL(k_lf_colmaxfin, dim3((L + 255) / 256, 1, g), dim3(256), 0, s, pm, L, nrch, cbest);
-        hipLaunchKernelGGL(k_lf_select, dim3(1, 1, g), dim3(1024), 0, s, bval, bidx, cbest, L, hc, wc, 0.2f, 2,
-                           mi + (size_t)p0 * L, mj + (size_t)p0 * L, mconf + (size_t)p0 * L, cnt + p0);
+        hipLaunchKernelGGL(k_lf_stats, dim3(ncb, nrch, g), dim3(256), 0, s, b.S, L, lds, b.pm, b.pz, b.prm);
+        hipLaunchKernelGGL(k_lf_colfin, dim3((L + 63) / 64, 1, g), dim3(256), 0, s, b.pm, b.pz, L, lds, nrch, b.cmax,
+                           b.csum, b.ckey);
+        hipLaunchKernelGGL(k_lf_rowbest, dim3((L + 3) / 4, 1, g), dim3(256), 0, s, b.S, L, lds, b.rmax, b.rsum, b.rkey,
+                           b.prm, ncb, b.cmax, b.csum, b.ckey, b.bval, b.bidx);
+        hipLaunchKernelGGL(k_lf_colmaxpart, dim3((L + 255) / 256, nrch, g), dim3(256), 0, s, b.S, L, lds, b.rmax,
+                           b.rsum, b.rkey, b.cmax, b.csum, b.pm);
+        hipLaunchKernelGGL(k_lf_colmaxfin, dim3((L + 255) / 256, 1, g), dim3(256), 0, s, b.pm, L, nrch, b.cbest);
+        hipLaunchKernelGGL(k_lf_select, dim3(1, 1, g), dim3(1024), 0, s, b.bval, b.bidx, b.cbest, L, hc, wc, 0.2f, 2,
+                           b.mi + (size_t)p0 * L, b.mj + (size_t)p0 * L, b.mconf + (size_t)p0 * L, b.cnt + p0);
         MLG_LAUNCH_CHECK();
     }
     std::vector<int32_t> h_cnt(P);
-    if (hipMemcpyAsync(h_cnt.data(), cnt, (size_t)P * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(counts, cnt, (size_t)P * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+    if (hipMemcpyAsync(h_cnt.data(), b.cnt, (size_t)P * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(counts, b.cnt, (size_t)P * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return MLG_EHIP;
     std::vector<int32_t> mp, ms;
@@ -1496,27 +1462,27 @@ int mlg_loftr_match(const mlg_loftr_weights* wp, const float* coarse, const floa
     const long Mtot = (long)mp.size();
     for (long m0 = 0; m0 < Mtot; m0 += FINE_CHUNK) {
         const int M = (int)std::min<long>(FINE_CHUNK, Mtot - m0);
-        if (hipMemcpyAsync(dmp, mp.data() + m0, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(dms, ms.data() + m0, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        if (hipMemcpyAsync(b.mp, mp.data() + m0, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(b.ms, ms.data() + m0, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess)
             return MLG_EHIP;
         const long items = (long)2 * M * 25 * 32 + (long)2 * M * 64;
         hipLaunchKernelGGL(k_lf_windows, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, fine, Hf, Wf, wc,
-                           Hf / hc, frm, P, mi, mj, L, dmp, dms, M, bc.x, win, crow);
+                           Hf / hc, b.frm, P, b.mi, b.mj, L, b.mp, b.ms, M, bc.x, b.win, b.crow);
         MLG_LAUNCH_CHECK();
         const long frows = (long)2 * M * 25;
         // merge_feat on [window | down_proj(coarse)]: the window half per token, the
         // coarse half once per (side, match)
-        MLG_TRY(mlg_gemm_conv(win, 128, (const bf16_t*)w.merge_wf, nullptr, nullptr, 0, bf.t, 128, nullptr, 0, 0, 0,
+        MLG_TRY(mlg_gemm_conv(b.win, 128, (const bf16_t*)w.merge_wf, nullptr, nullptr, 0, bf.t, 128, nullptr, 0, 0, 0,
                              (int)frows, 128, 128, s));
-        MLG_TRY(mlg_gemm_conv(crow, 256, (const bf16_t*)w.down_w, w.down_b, nullptr, 0, nullptr, 0, cd, 128, 0, 0,
+        MLG_TRY(mlg_gemm_conv(b.crow, 256, (const bf16_t*)w.down_w, w.down_b, nullptr, 0, nullptr, 0, b.cd, 128, 0, 0,
                              2 * M, 128, 256, s));
-        MLG_TRY(mlg_gemm_conv(cd, 128, (const bf16_t*)w.merge_wc, w.merge_b, nullptr, 0, cm, 128, nullptr, 0, 0, 0,
+        MLG_TRY(mlg_gemm_conv(b.cd, 128, (const bf16_t*)w.merge_wc, w.merge_b, nullptr, 0, b.cm, 128, nullptr, 0, 0, 0,
                              2 * M, 128, 128, s));
-        hipLaunchKernelGGL(k_lf_fine_tokens, dim3((unsigned)((frows * 32 + 255) / 256)), dim3(256), 0, s, bf.t, cm,
+        hipLaunchKernelGGL(k_lf_fine_tokens, dim3((unsigned)((frows * 32 + 255) / 256)), dim3(256), 0, s, bf.t, b.cm,
                            frows, bf.x, bf.cat);
         MLG_LAUNCH_CHECK();
         MLG_TRY(transformer(w.fine, 2, bf, 128, M, 25, s));
-        hipLaunchKernelGGL(k_lf_fine_match, dim3(M), dim3(64), 0, s, bf.x, M, dmp, dms, mi, mj, mconf, L, wc,
+        hipLaunchKernelGGL(k_lf_fine_match, dim3(M), dim3(64), 0, s, bf.x, M, b.mp, b.ms, b.mi, b.mj, b.mconf, L, wc,
                            (float)H / (float)hc, (float)H / (float)Hf, kpts0, kpts1, conf);
         MLG_LAUNCH_CHECK();
         if (m0 + M < Mtot && hipStreamSynchronize(s) != hipSuccess) return MLG_EHIP;  // mp / ms reused
@@ -1541,29 +1507,22 @@ extern "C" int mlg_loftr_pack_tails(const mlg_loftr_weights* w, void* out, void*
 
 // ------------------------------------------------ op-level check of one coarse layer
 namespace {
-struct CoarseLayerLayout {
-    size_t qkv, msg, t, h, kv, ks, kvp, tails, total;
+struct CoarseLayerBufs {
+    LayerBufs l;  // x and cat are the caller's
+    char* tails;  // room for the packed tails
 };
-CoarseLayerLayout coarse_layer_layout(int nseg, int L) {
-    CoarseLayerLayout M;
-    size_t o = 0;
-    auto take = [&](size_t b) { const size_t at = o; o += (b + 255) & ~(size_t)255; return at; };
-    const size_t rows = (size_t)2 * nseg * L;
-    M.qkv = take(rows * 768 * 4);
-    M.msg = take(rows * 256 * 2);
-    M.t = take(rows * 256 * 4);
-    M.h = take(rows * 512 * 2);
-    M.kv = take((size_t)2 * nseg * 8 * 32 * 32 * 4);
-    M.ks = take((size_t)2 * nseg * 8 * 32 * 4);
-    M.kvp = take((size_t)2 * nseg * 8 * ((L + LF_KV_CHUNK - 1) / LF_KV_CHUNK) * (32 * 32 + 32) * 4);
-    M.tails = take(TAILS_BYTES);
-    M.total = o;
-    return M;
+size_t coarse_layer_carve(int nseg, int L, void* base, CoarseLayerBufs* out) {
+    WsCarver c(base);
+    CoarseLayerBufs b{};
+    layer_carve(c, (size_t)2 * nseg * L, (size_t)2 * nseg, L, 256, true, &b.l);
+    b.tails = c.take<char>(TAILS_BYTES);
+    if (out) *out = b;
+    return c.total();
 }
 }  // namespace
 
 extern "C" size_t mlg_op_loftr_coarse_layer_ws_bytes(int nseg, int L) {
-    return (nseg > 0 && L > 0) ? coarse_layer_layout(nseg, L).total : 0;
+    return (nseg > 0 && L > 0) ? coarse_layer_carve(nseg, L, nullptr, nullptr) : 0;
 }
 
 // One coarse LoFTREncoderLayer `layer` (even: self on both sides; odd: cross, side 0 then
@@ -1573,18 +1532,18 @@ extern "C" size_t mlg_op_loftr_coarse_layer_ws_bytes(int nseg, int L) {
 extern "C" int mlg_op_loftr_coarse_layer(const mlg_loftr_weights* w, int layer, int fused, float* x, uint16_t* cat,
                                          int nseg, int L, void* ws, size_t ws_bytes, void* stream) {
     if (!mlg_head_ok(w, MLG_ABI_VERSION) || !x || !cat || !ws || layer < 0 || layer >= 8 || nseg <= 0 || L <= 0) return MLG_EINVAL;
-    const CoarseLayerLayout M = coarse_layer_layout(nseg, L);
-    if (ws_bytes < M.total) return MLG_ENOMEM;
-    char* base = (char*)ws;
+    CoarseLayerBufs cb;
+    if (coarse_layer_carve(nseg, L, ws, &cb) > ws_bytes) return MLG_ENOMEM;
+    LayerBufs& b = cb.l;
+    b.x = x;
+    b.cat = (bf16_t*)cat;
     hipStream_t s = (hipStream_t)stream;
-    const LayerBufs b{x, (bf16_t*)cat, (float*)(base + M.qkv), (bf16_t*)(base + M.msg), (float*)(base + M.t),
-                      (bf16_t*)(base + M.h), (float*)(base + M.kv), (float*)(base + M.ks), (float*)(base + M.kvp)};
     TailW tails[8];
     if (fused) {
         if (w->coarse_tails)
             tails_at((char*)w->coarse_tails, tails);
         else
-            MLG_TRY(pack_tails(*w, base + M.tails, tails, s));
+            MLG_TRY(pack_tails(*w, cb.tails, tails, s));
     }
     const TailW* tw = fused ? tails + layer : nullptr;
     const long half = (long)nseg * L;

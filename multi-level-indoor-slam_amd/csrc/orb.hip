@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 #include "../../include/mlgate.h"
 
 namespace {
@@ -472,26 +473,42 @@ __global__ __launch_bounds__(256) void k_orb_cross(const int32_t* __restrict__ c
     }
 }
 
-long a256(long x) { return (x + 255) & ~255L; }
-
-struct OrbLayout {
-    long pyr, blur, score, cand, sel, ccount, hist, scount, kstart, total;
+struct OrbBufs {
+    uint8_t *pyr, *blur, *score;
+    uint32_t* cand;
+    int4* sel;
+    int *ccount, *hist, *scount, *kstart;
 };
 
-OrbLayout orb_layout(const OrbGeom& g) {
-    OrbLayout L{};
-    long o = 0;
-    L.pyr = o;    o += a256(g.pyr_bytes * g.F);
-    L.blur = o;   o += a256(g.pyr_bytes * g.F);
-    L.score = o;  o += a256(g.pyr_bytes * g.F);
-    L.cand = o;   o += a256(g.cand_per_frame * g.F * 4);
-    L.sel = o;    o += a256(g.cand_per_frame * g.F * 16);
-    L.ccount = o; o += a256((long)g.F * NL * 4);
-    L.hist = o;   o += a256((long)g.F * NL * 256 * 4);
-    L.scount = o; o += a256((long)g.F * NL * 4);
-    L.kstart = o; o += a256((long)g.F * NL * 4);
-    L.total = o;
-    return L;
+size_t orb_carve(const OrbGeom& g, void* base, OrbBufs* out) {
+    WsCarver c(base);
+    OrbBufs b;
+    const size_t F = (size_t)g.F;
+    b.pyr = c.take<uint8_t>(g.pyr_bytes * F);
+    b.blur = c.take<uint8_t>(g.pyr_bytes * F);
+    b.score = c.take<uint8_t>(g.pyr_bytes * F);
+    b.cand = c.take<uint32_t>(g.cand_per_frame * F);
+    b.sel = c.take<int4>(g.cand_per_frame * F);
+    b.ccount = c.take<int>(F * NL);
+    b.hist = c.take<int>(F * NL * 256);
+    b.scount = c.take<int>(F * NL);
+    b.kstart = c.take<int>(F * NL);
+    if (out) *out = b;
+    return c.total();
+}
+
+struct OrbMatchBufs {
+    int *best, *bdist;  // [2 directions][P][max_kp] each, one region
+};
+
+size_t orb_match_carve(int P, int max_kp, void* base, OrbMatchBufs* out) {
+    WsCarver c(base);
+    OrbMatchBufs b;
+    const size_t n = (size_t)2 * P * max_kp;
+    b.best = c.take<int>(2 * n);
+    b.bdist = b.best ? b.best + n : nullptr;
+    if (out) *out = b;
+    return c.total();
 }
 
 bool make_geom(const mlg_orb_params* p, int F, int H, int W, int max_kp, OrbGeom& g) {
@@ -515,7 +532,7 @@ bool make_geom(const mlg_orb_params* p, int F, int H, int W, int max_kp, OrbGeom
         coff += (g.lcap[l] + 3) & ~3L;
     }
     if (g.lw[0] != W || g.lh[0] != H || (long)W * H >= (1L << 24)) return false;
-    g.pyr_bytes = (off + 255) & ~255L;
+    g.pyr_bytes = (long)a256((size_t)off);
     g.cand_per_frame = coff;
     for (int i = 0; i < 16; ++i) g.umax[i] = p->umax[i];
     for (int i = 0; i < 7; ++i) g.gk[i] = p->gauss[i];
@@ -531,7 +548,7 @@ extern "C" {
 size_t mlg_orb_workspace_bytes(const mlg_orb_params* p, int F, int H, int W, int max_kp) {
     OrbGeom g;
     if (!make_geom(p, F, H, W, max_kp, g)) return 0;
-    return (size_t)orb_layout(g).total;
+    return orb_carve(g, nullptr, nullptr);
 }
 
 int mlg_orb_detect(const mlg_orb_params* p, const int16_t* pattern, const uint8_t* frames, long frame_stride, int F,
@@ -541,53 +558,45 @@ int mlg_orb_detect(const mlg_orb_params* p, const int16_t* pattern, const uint8_
     if (!make_geom(p, F, H, W, max_kp, g) || !pattern || !frames || (C != 1 && C != 3 && C != 4) ||
         frame_stride < (long)H * W * C)
         return MLG_EINVAL;
-    const OrbLayout L = orb_layout(g);
-    if (!ws || ws_bytes < (size_t)L.total) return MLG_ENOMEM;
+    OrbBufs b;
+    if (orb_carve(g, ws, &b) > ws_bytes || !ws) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    char* b = (char*)ws;
-    uint8_t* pyr = (uint8_t*)(b + L.pyr);
-    uint8_t* blur = (uint8_t*)(b + L.blur);
-    uint8_t* score = (uint8_t*)(b + L.score);
-    uint32_t* cand = (uint32_t*)(b + L.cand);
-    int4* sel = (int4*)(b + L.sel);
-    int* ccount = (int*)(b + L.ccount);
-    int* hist = (int*)(b + L.hist);
-    int* scount = (int*)(b + L.scount);
-    int* kstart = (int*)(b + L.kstart);
-    if (hipMemsetAsync(ccount, 0, sizeof(int) * F * NL, s) != hipSuccess ||
-        hipMemsetAsync(hist, 0, sizeof(int) * F * NL * 256, s) != hipSuccess)
+    if (hipMemsetAsync(b.ccount, 0, sizeof(int) * F * NL, s) != hipSuccess ||
+        hipMemsetAsync(b.hist, 0, sizeof(int) * F * NL * 256, s) != hipSuccess)
         return MLG_EHIP;
-    hipLaunchKernelGGL(k_orb_gray, dim3(blocks((long)F * H * W)), dim3(256), 0, s, frames, frame_stride, C, g, pyr);
+    hipLaunchKernelGGL(k_orb_gray, dim3(blocks((long)F * H * W)), dim3(256), 0, s, frames, frame_stride, C, g, b.pyr);
     MLG_LAUNCH_CHECK();
     for (int l = 1; l < NL; ++l) {
-        hipLaunchKernelGGL(k_orb_resize, dim3(blocks((long)F * g.lw[l] * g.lh[l])), dim3(256), 0, s, g, l, pyr);
+        hipLaunchKernelGGL(k_orb_resize, dim3(blocks((long)F * g.lw[l] * g.lh[l])), dim3(256), 0, s, g, l, b.pyr);
         MLG_LAUNCH_CHECK();
     }
     for (int l = 0; l < NL; ++l) {
         const long px = (long)F * g.lw[l] * g.lh[l];
-        hipLaunchKernelGGL(k_orb_fast, dim3(blocks(px)), dim3(256), 0, s, g, l, pyr, score);
+        hipLaunchKernelGGL(k_orb_fast, dim3(blocks(px)), dim3(256), 0, s, g, l, b.pyr, b.score);
         MLG_LAUNCH_CHECK();
         const long inner = (long)F * std::max(0, g.lw[l] - 2 * g.edge) * std::max(0, g.lh[l] - 2 * g.edge);
         if (inner > 0) {
-            hipLaunchKernelGGL(k_orb_nms, dim3(blocks(inner)), dim3(256), 0, s, g, l, score, cand, ccount, hist);
+            hipLaunchKernelGGL(k_orb_nms, dim3(blocks(inner)), dim3(256), 0, s, g, l, b.score, b.cand, b.ccount,
+                               b.hist);
             MLG_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_orb_blur, dim3(blocks(px)), dim3(256), 0, s, g, l, pyr, blur);
+        hipLaunchKernelGGL(k_orb_blur, dim3(blocks(px)), dim3(256), 0, s, g, l, b.pyr, b.blur);
         MLG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_orb_select, dim3(F * NL), dim3(256), 0, s, g, pyr, cand, ccount, hist, sel, scount);
+    hipLaunchKernelGGL(k_orb_select, dim3(F * NL), dim3(256), 0, s, g, b.pyr, b.cand, b.ccount, b.hist, b.sel,
+                       b.scount);
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_orb_gather, dim3(blocks(F)), dim3(256), 0, s, g, scount, kstart, counts);
+    hipLaunchKernelGGL(k_orb_gather, dim3(blocks(F)), dim3(256), 0, s, g, b.scount, b.kstart, counts);
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_orb_describe, dim3(blocks((long)F * max_kp)), dim3(256), 0, s, g, pyr, blur, sel, scount,
-                       kstart, counts, pattern, keypoints, responses, angles, levels, descriptors);
+    hipLaunchKernelGGL(k_orb_describe, dim3(blocks((long)F * max_kp)), dim3(256), 0, s, g, b.pyr, b.blur, b.sel,
+                       b.scount, b.kstart, counts, pattern, keypoints, responses, angles, levels, descriptors);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
 
 size_t mlg_orb_match_workspace_bytes(int P, int max_kp) {
     if (P <= 0 || max_kp <= 0) return 0;
-    return (size_t)a256((long)4 * P * max_kp * 4);
+    return orb_match_carve(P, max_kp, nullptr, nullptr);
 }
 
 int mlg_orb_match(const uint8_t* descriptors, const int32_t* counts, int max_kp, const int32_t* pair_a,
@@ -595,17 +604,16 @@ int mlg_orb_match(const uint8_t* descriptors, const int32_t* counts, int max_kp,
                   int32_t* distance, int32_t* nmatch, void* stream) {
     if (P <= 0) return MLG_OK;
     if (max_kp <= 0 || !descriptors || !counts || !pair_a || !pair_b || P > 65535) return MLG_EINVAL;
-    if (!ws || ws_bytes < mlg_orb_match_workspace_bytes(P, max_kp)) return MLG_ENOMEM;
+    OrbMatchBufs b;
+    if (orb_match_carve(P, max_kp, ws, &b) > ws_bytes || !ws) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    int* best = (int*)ws;
-    int* bdist = best + (long)2 * P * max_kp;
     const dim3 grid((unsigned)((max_kp + 255) / 256), (unsigned)P);
     for (int dir = 0; dir < 2; ++dir) {
-        hipLaunchKernelGGL(k_orb_nn, grid, dim3(256), 0, s, descriptors, counts, max_kp, pair_a, pair_b, dir, best,
-                           bdist);
+        hipLaunchKernelGGL(k_orb_nn, grid, dim3(256), 0, s, descriptors, counts, max_kp, pair_a, pair_b, dir, b.best,
+                           b.bdist);
         MLG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_orb_cross, dim3((unsigned)P), dim3(256), 0, s, counts, max_kp, pair_a, P, best, bdist,
+    hipLaunchKernelGGL(k_orb_cross, dim3((unsigned)P), dim3(256), 0, s, counts, max_kp, pair_a, P, b.best, b.bdist,
                        query_idx, train_idx, distance, nmatch);
     MLG_LAUNCH_CHECK();
     return MLG_OK;

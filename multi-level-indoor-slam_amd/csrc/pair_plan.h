@@ -24,6 +24,8 @@
 #include <utility>
 #include <vector>
 
+#include "ws_carve.h"
+
 namespace pair_plan {
 
 struct Seg {
@@ -49,7 +51,6 @@ static_assert(offsetof(Move, src_off) == 0 && offsetof(Move, src_len) == 4 && of
               "Move is the kernels' int4");
 
 inline int pad64(int n) { return (n + 63) & ~63; }
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }  // workspace carving granule
 
 // The distinct ids of a list in first-appearance order, and each entry's index into them.
 struct Distinct {

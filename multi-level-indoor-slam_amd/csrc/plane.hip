@@ -11,6 +11,7 @@
 // stream through LDS in chunks and are read by all hypotheses (broadcast).
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -120,22 +121,36 @@ __global__ void k_plane_select(const int32_t* __restrict__ offs, int H, const do
     }
 }
 
+struct PlaneBufs {
+    double* planes;   // [S][H][4]
+    int32_t* counts;  // [S][H]
+};
+
+size_t plane_carve(int S, int H, void* base, PlaneBufs* out) {
+    WsCarver c(base);
+    PlaneBufs b;
+    b.planes = c.take<double>((size_t)S * H * 4);
+    b.counts = c.take<int32_t>(0);  // ends the workspace without rounding (the size has always been exact)
+    if (out) *out = b;
+    return c.total() + (size_t)S * H * sizeof(int32_t);
+}
+
 }  // namespace
 
 size_t mlg_plane_ws_bytes(int S, int H) {
     if (S <= 0 || H <= 0) return 0;
-    return (((size_t)S * H * 4 * 8 + 255) & ~(size_t)255) + (size_t)S * H * 4;
+    return plane_carve(S, H, nullptr, nullptr);
 }
 
 int mlg_plane_ransac_run(const float* pts, const int32_t* offs, int S, int H, uint64_t seed, double thr, void* ws,
                          size_t ws_bytes, double* plane, double* ratio, int32_t* inliers, hipStream_t s) {
     if (S <= 0 || H <= 0 || !(thr > 0.0)) return MLG_EINVAL;
-    if (ws_bytes < mlg_plane_ws_bytes(S, H)) return MLG_EINVAL;
-    double* planes = (double*)ws;
-    int32_t* counts = (int32_t*)((char*)ws + (((size_t)S * H * 4 * 8 + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(k_plane_score, dim3((H + 63) / 64, S), dim3(64), 0, s, pts, offs, H, seed, thr, planes, counts);
+    PlaneBufs b;
+    if (plane_carve(S, H, ws, &b) > ws_bytes) return MLG_EINVAL;
+    hipLaunchKernelGGL(k_plane_score, dim3((H + 63) / 64, S), dim3(64), 0, s, pts, offs, H, seed, thr, b.planes,
+                       b.counts);
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_plane_select, dim3(S), dim3(256), 0, s, offs, H, planes, counts, plane, ratio, inliers);
+    hipLaunchKernelGGL(k_plane_select, dim3(S), dim3(256), 0, s, offs, H, b.planes, b.counts, plane, ratio, inliers);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -104,25 +105,26 @@ __global__ void k_proximity_totals(const uint64_t* counts, const uint64_t* offse
     }
 }
 
-struct ProxLayout {
+struct ProxBufs {
     int nchunk;
-    size_t M, counts, offsets, scan_tmp, scan_bytes, total;
+    size_t M, scan_bytes;  // (row, chunk) counters; rocprim's temporary storage
+    uint64_t *counts, *offsets;
+    char* scan_tmp;
 };
 
-ProxLayout prox_layout(int N, int nrows) {
-    ProxLayout L;
-    L.nchunk = (N + PX_JC - 1) / PX_JC;
-    L.M = (size_t)nrows * L.nchunk;
-    size_t scan_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, L.M,
-                            rocprim::plus<uint64_t>(), (hipStream_t)0);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    L.counts = 0;
-    L.offsets = up(L.M * 8);
-    L.scan_tmp = L.offsets + up(L.M * 8);
-    L.scan_bytes = scan_bytes;
-    L.total = L.scan_tmp + up(scan_bytes > 0 ? scan_bytes : 1);
-    return L;
+size_t prox_carve(int N, int nrows, void* base, ProxBufs* out) {
+    WsCarver c(base);
+    ProxBufs b;
+    b.nchunk = (N + PX_JC - 1) / PX_JC;
+    b.M = (size_t)nrows * b.nchunk;
+    b.scan_bytes = 0;
+    (void)rocprim::exclusive_scan(nullptr, b.scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0,
+                                  b.M, rocprim::plus<uint64_t>(), (hipStream_t)0);
+    b.counts = c.take<uint64_t>(b.M);
+    b.offsets = c.take<uint64_t>(b.M);
+    b.scan_tmp = c.take<char>(b.scan_bytes > 0 ? b.scan_bytes : 1);
+    if (out) *out = b;
+    return c.total();
 }
 
 }  // namespace
@@ -134,28 +136,25 @@ bool mlg_proximity_shape_ok(int N, int row0, int nrows) {
 
 size_t mlg_proximity_ws_bytes(int N, int nrows) {
     if (!mlg_proximity_shape_ok(N, 0, nrows)) return 0;
-    return prox_layout(N, nrows).total;
+    return prox_carve(N, nrows, nullptr, nullptr);
 }
 
 int mlg_proximity_count_run(const double* pos, const int64_t* floor, int N, int row0, int nrows, double radius,
                             int min_gap, int strict, void* ws, size_t ws_bytes, long long* totals, hipStream_t s) {
     if (!mlg_proximity_shape_ok(N, row0, nrows) || min_gap < 1 || !(radius >= 0.0)) return MLG_EINVAL;
-    const ProxLayout L = prox_layout(N, nrows);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* w = (char*)ws;
-    uint64_t* counts = (uint64_t*)(w + L.counts);
-    uint64_t* offsets = (uint64_t*)(w + L.offsets);
-    if (L.M > 0) {
-        dim3 grid((nrows + PX_ROWS - 1) / PX_ROWS, L.nchunk);
+    ProxBufs b;
+    if (prox_carve(N, nrows, ws, &b) > ws_bytes) return MLG_EINVAL;
+    if (b.M > 0) {
+        dim3 grid((nrows + PX_ROWS - 1) / PX_ROWS, b.nchunk);
         hipLaunchKernelGGL(k_proximity<false>, grid, dim3(PX_ROWS), 0, s, pos, floor, N, row0, nrows, radius * radius,
-                           min_gap, strict ? 0 : 1, L.nchunk, counts, nullptr, nullptr, nullptr, nullptr);
+                           min_gap, strict ? 0 : 1, b.nchunk, b.counts, nullptr, nullptr, nullptr, nullptr);
         MLG_LAUNCH_CHECK();
-        size_t sb = L.scan_bytes;
-        if (rocprim::exclusive_scan(w + L.scan_tmp, sb, counts, offsets, (uint64_t)0, L.M, rocprim::plus<uint64_t>(),
+        size_t sb = b.scan_bytes;
+        if (rocprim::exclusive_scan(b.scan_tmp, sb, b.counts, b.offsets, (uint64_t)0, b.M, rocprim::plus<uint64_t>(),
                                     s) != hipSuccess)
             return MLG_EHIP;
     }
-    hipLaunchKernelGGL(k_proximity_totals, dim3(1), dim3(64), 0, s, counts, offsets, L.M, totals);
+    hipLaunchKernelGGL(k_proximity_totals, dim3(1), dim3(64), 0, s, b.counts, b.offsets, b.M, totals);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
@@ -164,14 +163,12 @@ int mlg_proximity_emit_run(const double* pos, const int64_t* floor, int N, int r
                            int min_gap, int strict, const void* ws, size_t ws_bytes, int32_t* pairs, double* dist,
                            uint8_t* valid, hipStream_t s) {
     if (!mlg_proximity_shape_ok(N, row0, nrows) || min_gap < 1 || !(radius >= 0.0)) return MLG_EINVAL;
-    const ProxLayout L = prox_layout(N, nrows);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    if (L.M == 0) return MLG_OK;
-    const char* w = (const char*)ws;
-    dim3 grid((nrows + PX_ROWS - 1) / PX_ROWS, L.nchunk);
+    ProxBufs b;  // read only here: the offsets mlg_proximity_count_run left
+    if (prox_carve(N, nrows, const_cast<void*>(ws), &b) > ws_bytes) return MLG_EINVAL;
+    if (b.M == 0) return MLG_OK;
+    dim3 grid((nrows + PX_ROWS - 1) / PX_ROWS, b.nchunk);
     hipLaunchKernelGGL(k_proximity<true>, grid, dim3(PX_ROWS), 0, s, pos, floor, N, row0, nrows, radius * radius,
-                       min_gap, strict ? 0 : 1, L.nchunk, nullptr, (const uint64_t*)(w + L.offsets), pairs, dist,
-                       valid);
+                       min_gap, strict ? 0 : 1, b.nchunk, nullptr, (const uint64_t*)b.offsets, pairs, dist, valid);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }

@@ -43,6 +43,7 @@
 //   k_recover_pose   : one workgroup per pair: E -> [R|t] by cheirality on the inliers
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 // Values that feed a branch, a root or a count come from rs_math.h, the one header the C
 // twin (oracle/csrc/ransac_cv.c) includes too; this file builds with -ffp-contract=off
@@ -1534,8 +1535,6 @@ __global__ __launch_bounds__(256) void k_recover_pose(const float* __restrict__ 
     }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // mlg_dbg_ransac_poison_nsol: overwrite the counts of the slots no scan uses
 bool g_poison_nsol = false;
 int g_poison_value = 0;
@@ -1551,87 +1550,87 @@ __global__ __launch_bounds__(64) void k_ransac_poison_nsol(const PairInfo* __res
     if (unused) nsol[(size_t)p * H + h] = (int8_t)value;
 }
 
-struct RsLayout {
-    size_t info, ptsn, ptsr, models, nsol, score, subsets, nsub, done, total;
+struct RsBufs {
+    PairInfo* info;
+    double4 *ptsn, *ptsr;
+    double* models;
+    int8_t* nsol;
+    float* score;
+    int32_t *subsets, *nsub;
+    uint8_t* done;
 };
 
-RsLayout rs_layout(int P, long S_total, int H) {
-    RsLayout L;
-    L.info = 0;
-    L.ptsn = align256(sizeof(PairInfo) * (size_t)P);
-    L.ptsr = L.ptsn + align256(sizeof(double4) * (size_t)S_total);
-    L.models = L.ptsr + align256(sizeof(double4) * (size_t)S_total);
-    L.nsol = L.models + align256(sizeof(double) * 9 * MAXSOL * (size_t)P * H);
-    L.score = L.nsol + align256((size_t)P * H);
-    L.subsets = L.score + align256(sizeof(float) * MAXSOL * (size_t)P * H);
-    L.nsub = L.subsets + align256(sizeof(int32_t) * 7 * (size_t)P * H);
-    L.done = L.nsub + align256(sizeof(int32_t) * (size_t)P);
-    L.total = L.done + align256((size_t)P);
-    return L;
+size_t rs_carve(int P, long S_total, int H, void* base, RsBufs* out) {
+    WsCarver c(base);
+    RsBufs b;
+    const size_t PH = (size_t)P * H;
+    b.info = c.take<PairInfo>((size_t)P);
+    b.ptsn = c.take<double4>((size_t)S_total);
+    b.ptsr = c.take<double4>((size_t)S_total);
+    b.models = c.take<double>(9 * MAXSOL * PH);
+    b.nsol = c.take<int8_t>(PH);
+    b.score = c.take<float>(MAXSOL * PH);
+    b.subsets = c.take<int32_t>(7 * PH);
+    b.nsub = c.take<int32_t>((size_t)P);
+    b.done = c.take<uint8_t>((size_t)P);
+    if (out) *out = b;
+    return c.total();
 }
 
 }  // namespace
 
 size_t mlg_ransac_ws_bytes(int P, long S_total, int H) {
     if (P <= 0 || S_total < 0 || H <= 0) return 0;
-    return rs_layout(P, S_total, H).total;
+    return rs_carve(P, S_total, H, nullptr, nullptr);
 }
 
 int mlg_ransac_run(const float* kp1, const float* kp2, const int32_t* offs, int P, long S_total, const double* K,
                    int k_stride, double thr, int H, uint64_t seed, void* ws, size_t ws_bytes, double* model_out,
                    uint8_t* mask, int32_t* inliers, double* pose, int32_t* status, hipStream_t s) {
     if (P <= 0 || H <= 0 || H > (1 << 20) || !(thr > 0.0) || S_total < 0) return MLG_EINVAL;
-    const RsLayout L = rs_layout(P, S_total, H);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* w = (char*)ws;
-    PairInfo* info = (PairInfo*)(w + L.info);
-    double4* ptsn = (double4*)(w + L.ptsn);
-    double4* ptsr = (double4*)(w + L.ptsr);
-    double* models = (double*)(w + L.models);
-    int8_t* nsol = (int8_t*)(w + L.nsol);
-    float* score = (float*)(w + L.score);
-    int32_t* subsets = (int32_t*)(w + L.subsets);
-    int32_t* nsub = (int32_t*)(w + L.nsub);
-    hipLaunchKernelGGL(k_ransac_prep, dim3(P), dim3(256), 0, s, kp1, kp2, offs, K, k_stride, thr, info, ptsn, ptsr);
+    RsBufs b;
+    if (rs_carve(P, S_total, H, ws, &b) > ws_bytes) return MLG_EINVAL;
+    hipLaunchKernelGGL(k_ransac_prep, dim3(P), dim3(256), 0, s, kp1, kp2, offs, K, k_stride, thr, b.info, b.ptsn,
+                       b.ptsr);
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ransac_subsets, dim3((P + 63) / 64), dim3(64), 0, s, info, P, H, kp1, kp2, subsets, nsub);
+    hipLaunchKernelGGL(k_ransac_subsets, dim3((P + 63) / 64), dim3(64), 0, s, b.info, P, H, kp1, kp2, b.subsets,
+                       b.nsub);
     MLG_LAUNCH_CHECK();
-    uint8_t* done = (uint8_t*)(w + L.done);
     // round one: hypotheses [0, H1) of every pair; round two: [H1, H) of the pairs whose
     // sequential scan has not stopped inside round one (k_ransac_probe)
     const int H1 = std::min(H, RS_ROUND1);
     for (int round = 0; round < 2; ++round) {
         const int h0 = round ? H1 : 0, hn = round ? H - H1 : H1;
-        const uint8_t* skip = round ? done : nullptr;
+        const uint8_t* skip = round ? b.done : nullptr;
         if (hn <= 0) break;
-        hipLaunchKernelGGL(k_ransac_hyp, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, ptsn, H, seed, subsets, nsub,
-                           models, nsol, h0, skip);
+        hipLaunchKernelGGL(k_ransac_hyp, dim3((hn + 63) / 64, P), dim3(64), 0, s, b.info, b.ptsn, H, seed, b.subsets,
+                           b.nsub, b.models, b.nsol, h0, skip);
         MLG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ransac_null5, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, ptsn, H, subsets, nsub, models,
-                           h0, hn, skip);
+        hipLaunchKernelGGL(k_ransac_null5, dim3((hn + 63) / 64, P), dim3(64), 0, s, b.info, b.ptsn, H, b.subsets,
+                           b.nsub, b.models, h0, hn, skip);
         MLG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ransac_hyp5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, info, ptsn, H,
-                           subsets, nsub, models, nsol, h0, skip);
+        hipLaunchKernelGGL(k_ransac_hyp5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, b.info, b.ptsn, H,
+                           b.subsets, b.nsub, b.models, b.nsol, h0, skip);
         MLG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ransac_roots5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, info, H, nsub,
-                           models, nsol, h0, skip);
+        hipLaunchKernelGGL(k_ransac_roots5, dim3((hn + HYP5_GPB - 1) / HYP5_GPB, P), dim3(256), 0, s, b.info, H, b.nsub,
+                           b.models, b.nsol, h0, skip);
         MLG_LAUNCH_CHECK();
         if (g_poison_nsol) {
-            hipLaunchKernelGGL(k_ransac_poison_nsol, dim3((hn + 63) / 64, P), dim3(64), 0, s, info, H, nsub, nsol, h0,
-                               hn, skip, g_poison_value);
+            hipLaunchKernelGGL(k_ransac_poison_nsol, dim3((hn + 63) / 64, P), dim3(64), 0, s, b.info, H, b.nsub, b.nsol,
+                               h0, hn, skip, g_poison_value);
             MLG_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_ransac_score, dim3((hn + 255) / 256, P), dim3(256), 0, s, info, ptsn, ptsr, H, models,
-                           nsol, score, h0, skip);
+        hipLaunchKernelGGL(k_ransac_score, dim3((hn + 255) / 256, P), dim3(256), 0, s, b.info, b.ptsn, b.ptsr, H,
+                           b.models, b.nsol, b.score, h0, skip);
         MLG_LAUNCH_CHECK();
         if (round == 0 && H1 < H) {
-            hipLaunchKernelGGL(k_ransac_probe, dim3((P + 255) / 256), dim3(256), 0, s, info, P, H, H1, score, nsol,
-                               nsub, done);
+            hipLaunchKernelGGL(k_ransac_probe, dim3((P + 255) / 256), dim3(256), 0, s, b.info, P, H, H1, b.score,
+                               b.nsol, b.nsub, b.done);
             MLG_LAUNCH_CHECK();
         }
     }
-    hipLaunchKernelGGL(k_ransac_select, dim3(P), dim3(256), 0, s, info, ptsn, ptsr, H, models, score, nsol, nsub, model_out,
-                       mask, inliers, status);
+    hipLaunchKernelGGL(k_ransac_select, dim3(P), dim3(256), 0, s, b.info, b.ptsn, b.ptsr, H, b.models, b.score, b.nsol,
+                       b.nsub, model_out, mask, inliers, status);
     MLG_LAUNCH_CHECK();
     if (pose && K) {
         hipLaunchKernelGGL(k_recover_pose, dim3(P), dim3(256), 0, s, kp1, kp2, offs, K, k_stride, model_out, mask, pose,

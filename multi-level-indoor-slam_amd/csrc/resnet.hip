@@ -18,12 +18,14 @@
 // after layer3 and takes the f32 residual stream [B, (S/16)^2, 1024] instead of the pool.
 #include <math.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
 
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -226,37 +228,36 @@ Coeffs pillow_coeffs(int in_size, int out_size) {
     return c;
 }
 
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct RnLayout {
-    size_t tables, tmp, img, stem, xf0, xf1, xb0, xb1, t1, t2, col, sub, total;
+struct RnBufs {
+    int* tables;   // the Pillow resize's two (xmin, xcnt, kk) sets
+    uint8_t* tmp;  // horizontally resized frames
+    float* img;    // the normalised image, f32 NHWC [B, S, S, 3]
+    bf16_t* stem;
+    float* xf[2];  // the f32 residual stream, ping-pong
+    bf16_t* xb[2]; // its bf16 copy
+    bf16_t *t1, *t2, *col, *sub;
 };
 
 // S: the trunk's input side (a multiple of 32); H: the source height of the Pillow resize
 // (0: the caller supplies the normalised image, no tables / intermediate)
-RnLayout rn_layout(int B, int H, int S) {
-    RnLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += a256(bytes);
-        return r;
-    };
+size_t rn_carve(int B, int H, int S, void* base, RnBufs* out) {
+    WsCarver c(base);
+    RnBufs b;
     const size_t m4 = (size_t)B * (S / 4) * (S / 4), m8 = (size_t)B * (S / 8) * (S / 8);
-    L.tables = take(H ? (size_t)4 * (2 * RN_S + RN_S * 64) * 2 + 4096 : 0);  // generous: two (xmin, xcnt, kk) sets
-    L.tmp = take((size_t)B * H * RN_S * 3);
-    L.img = take((size_t)B * S * S * 3 * 4);
-    L.stem = take((size_t)B * (S / 2) * (S / 2) * 64 * 2);
-    L.xf0 = take(m4 * 256 * 4);  // largest residual tensor: stage 1, S/4 x S/4 x 256
-    L.xf1 = take(m4 * 256 * 4);
-    L.xb0 = take(m4 * 256 * 2);
-    L.xb1 = take(m4 * 256 * 2);
-    L.t1 = take(m4 * 128 * 2);   // bottleneck conv1 out (<= S/4 x S/4 x 64 padded to 128, S/8 x S/8 x 128 ...)
-    L.t2 = take(m4 * 128 * 2);   // conv2 out
-    L.col = take(m4 * 9 * 64 * 2 > m8 * 9 * 128 * 2 ? m4 * 9 * 64 * 2 : m8 * 9 * 128 * 2);
-    L.sub = take(m8 * 256 * 2);
-    L.total = o;
-    return L;
+    b.tables = c.take<int>(H ? (size_t)(2 * RN_S + RN_S * 64) * 2 + 1024 : 0);  // generous
+    b.tmp = c.take<uint8_t>((size_t)B * H * RN_S * 3);
+    b.img = c.take<float>((size_t)B * S * S * 3);
+    b.stem = c.take<bf16_t>((size_t)B * (S / 2) * (S / 2) * 64);
+    b.xf[0] = c.take<float>(m4 * 256);  // largest residual tensor: stage 1, S/4 x S/4 x 256
+    b.xf[1] = c.take<float>(m4 * 256);
+    b.xb[0] = c.take<bf16_t>(m4 * 256);
+    b.xb[1] = c.take<bf16_t>(m4 * 256);
+    b.t1 = c.take<bf16_t>(m4 * 128);  // bottleneck conv1 out (<= S/4 x S/4 x 64 padded to 128, S/8 x S/8 x 128 ...)
+    b.t2 = c.take<bf16_t>(m4 * 128);  // conv2 out
+    b.col = c.take<bf16_t>(std::max(m4 * 9 * 64, m8 * 9 * 128));
+    b.sub = c.take<bf16_t>(m8 * 256);
+    if (out) *out = b;
+    return c.total();
 }
 
 // Tables per input size, never freed: pending async uploads keep reading them.
@@ -273,26 +274,18 @@ struct CoeffCache {
 
 }  // namespace
 
-// Stem, max-pool and the first `nstages` bottleneck stages over the normalised image at
-// base + L.img (f32 NHWC [B, S, S, 3]); *xout: the f32 residual stream
-// [B, side, side, C] it ends with (inside the workspace).
+// Stem, max-pool and the first `nstages` bottleneck stages over the normalised image
+// b.img (f32 NHWC [B, S, S, 3]); *xout: the f32 residual stream [B, side, side, C] it ends
+// with (inside the workspace).  b: a copy, its xb pair is swapped along the way.
 template <int S>
-static int rn_trunk(const mlg_rn_weights_i& w, int B, int nstages, char* base, const RnLayout& L, hipStream_t s,
-             float** xout, int* side) {
-    float* img = (float*)(base + L.img);
-    bf16_t* stem = (bf16_t*)(base + L.stem);
-    float* xf[2] = {(float*)(base + L.xf0), (float*)(base + L.xf1)};
-    bf16_t* xb[2] = {(bf16_t*)(base + L.xb0), (bf16_t*)(base + L.xb1)};
-    bf16_t* t1 = (bf16_t*)(base + L.t1);
-    bf16_t* t2 = (bf16_t*)(base + L.t2);
-    bf16_t* col = (bf16_t*)(base + L.col);
-    bf16_t* sub = (bf16_t*)(base + L.sub);
-
+static int rn_trunk(const mlg_rn_weights_i& w, int B, int nstages, RnBufs b, hipStream_t s, float** xout,
+                    int* side) {
     const long ns = (long)B * (S / 2) * (S / 2);
-    hipLaunchKernelGGL(k_rn_stem<S>, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, img, w.stem_w, w.stem_b,
-                       stem, B);
+    hipLaunchKernelGGL(k_rn_stem<S>, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, b.img, w.stem_w, w.stem_b,
+                       b.stem, B);
     const long np = (long)B * (S / 4) * (S / 4) * 64;
-    hipLaunchKernelGGL(k_rn_maxpool<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, stem, xf[0], xb[0], B);
+    hipLaunchKernelGGL(k_rn_maxpool<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, b.stem, b.xf[0], b.xb[0],
+                       B);
     MLG_LAUNCH_CHECK();
 
     int cur = 0, Hc = S / 4, Cc = 64, blk = 0;
@@ -306,72 +299,71 @@ static int rn_trunk(const mlg_rn_weights_i& w, int B, int nstages, char* base, c
             const int M_in = B * Hc * Hc, M_out = B * Ho * Ho;
             const int nxt = cur ^ 1;
             // conv1 1x1 (+BN, ReLU) at the input resolution
-            int rc = mlg_gemm_bias_relu_bf16(xb[cur], Cc, bw.w1, bw.b1, t1, width, width, M_in, wpad, Cc, s);
+            int rc = mlg_gemm_bias_relu_bf16(b.xb[cur], Cc, bw.w1, bw.b1, b.t1, width, width, M_in, wpad, Cc, s);
             if (rc != MLG_OK) return rc;
             // conv2 3x3 / stride (+BN, ReLU) via im2col
             const long ni = (long)M_out * 9 * (width / 8);
-            hipLaunchKernelGGL(k_rn_im2col, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, t1, B, Hc, Hc, width,
-                               stride, col);
+            hipLaunchKernelGGL(k_rn_im2col, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, b.t1, B, Hc, Hc, width,
+                               stride, b.col);
             MLG_LAUNCH_CHECK();
-            rc = mlg_gemm_bias_relu_bf16(col, 9 * width, bw.w2, bw.b2, t2, width, width, M_out, wpad, 9 * width, s);
+            rc = mlg_gemm_bias_relu_bf16(b.col, 9 * width, bw.w2, bw.b2, b.t2, width, width, M_out, wpad, 9 * width, s);
             if (rc != MLG_OK) return rc;
             // shortcut: downsample conv (+BN) into the next f32 stream, or identity in place
-            float* res = xf[cur];
+            float* res = b.xf[cur];
             if (bw.wd) {
-                const bf16_t* src = xb[cur];
+                const bf16_t* src = b.xb[cur];
                 if (stride == 2) {
                     const long nsb = (long)M_out * (Cc / 8);
-                    hipLaunchKernelGGL(k_rn_subsample, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, s, xb[cur],
-                                       B, Hc, Hc, Cc, sub);
+                    hipLaunchKernelGGL(k_rn_subsample, dim3((unsigned)((nsb + 255) / 256)), dim3(256), 0, s, b.xb[cur],
+                                       B, Hc, Hc, Cc, b.sub);
                     MLG_LAUNCH_CHECK();
-                    src = sub;
+                    src = b.sub;
                 }
-                rc = mlg_gemm_bias_f32_ld(src, Cc, bw.wd, bw.bd, xf[nxt], 4 * width, M_out, 4 * width, Cc, s);
+                rc = mlg_gemm_bias_f32_ld(src, Cc, bw.wd, bw.bd, b.xf[nxt], 4 * width, M_out, 4 * width, Cc, s);
                 if (rc != MLG_OK) return rc;
-                res = xf[nxt];
+                res = b.xf[nxt];
             }
             // conv3 1x1 (+BN) + shortcut + ReLU -> f32 stream and its bf16 copy
-            float* outf = bw.wd ? xf[nxt] : xf[cur];
-            bf16_t* outb = xb[nxt];
-            rc = mlg_gemm_bias_add_relu(t2, width, bw.w3, bw.b3, res, outf, 4 * width, outb, M_out, 4 * width, width,
+            float* outf = bw.wd ? b.xf[nxt] : b.xf[cur];
+            bf16_t* outb = b.xb[nxt];
+            rc = mlg_gemm_bias_add_relu(b.t2, width, bw.w3, bw.b3, res, outf, 4 * width, outb, M_out, 4 * width, width,
                                         s);
             if (rc != MLG_OK) return rc;
             if (bw.wd) {
                 cur = nxt;
             } else {
                 // f32 stream updated in place (xf[cur]); bf16 copy went to xb[nxt]
-                std::swap(xb[cur], xb[nxt]);
+                std::swap(b.xb[cur], b.xb[nxt]);
             }
             Hc = Ho;
             Cc = 4 * width;
         }
     }
-    *xout = xf[cur];
+    *xout = b.xf[cur];
     *side = Hc;
     return MLG_OK;
 }
 
 size_t mlg_resnet50_ws_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return rn_layout(B, H, RN_S).total;
+    return rn_carve(B, H, RN_S, nullptr, nullptr);
 }
 
 int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                      int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s) {
     if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || D <= 0) return MLG_EINVAL;
-    const RnLayout L = rn_layout(B, H, RN_S);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* base = (char*)ws;
+    RnBufs b;
+    if (rn_carve(B, H, RN_S, ws, &b) > ws_bytes) return MLG_EINVAL;
     const Coeffs& ch = g_coeffs.get(W);
     const Coeffs& cv = g_coeffs.get(H);
-    int* tb = (int*)(base + L.tables);
-    int* hx0 = tb;
+    int* hx0 = b.tables;
     int* hxc = hx0 + RN_S;
     int* hkk = hxc + RN_S;
     int* vy0 = hkk + (size_t)RN_S * ch.ksize;
     int* vyc = vy0 + RN_S;
     int* vkk = vyc + RN_S;
-    if ((size_t)((char*)(vkk + (size_t)RN_S * cv.ksize) - (char*)tb) > L.tmp - L.tables) return MLG_EINVAL;
+    // the table region ends where the next one (tmp) begins
+    if ((char*)(vkk + (size_t)RN_S * cv.ksize) > (char*)b.tmp) return MLG_EINVAL;
     if (hipMemcpyAsync(hx0, ch.xmin.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(hxc, ch.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(hkk, ch.kk.data(), ch.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -379,22 +371,20 @@ int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, in
         hipMemcpyAsync(vyc, cv.xcnt.data(), RN_S * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(vkk, cv.kk.data(), cv.kk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
         return MLG_EHIP;
-    uint8_t* tmp = (uint8_t*)(base + L.tmp);
-    float* img = (float*)(base + L.img);
 
     const long nh = (long)B * H * RN_S;
     hipLaunchKernelGGL(k_rn_resize_h, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, frames, frame_stride, H, W,
-                       C, hx0, hxc, hkk, ch.ksize, tmp, B);
+                       C, hx0, hxc, hkk, ch.ksize, b.tmp, B);
     const long nv = (long)B * RN_S * RN_S;
-    hipLaunchKernelGGL(k_rn_resize_v, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, tmp, H, vy0, vyc, vkk,
-                       cv.ksize, img, resized_u8, B);
+    hipLaunchKernelGGL(k_rn_resize_v, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, b.tmp, H, vy0, vyc, vkk,
+                       cv.ksize, b.img, resized_u8, B);
     if (resized_u8) {  // parity entry: stop after the resize
         MLG_LAUNCH_CHECK();
         return MLG_OK;
     }
     float* x = nullptr;
     int Hc = 0;
-    MLG_TRY(rn_trunk<RN_S>(w, B, 4, base, L, s, &x, &Hc));
+    MLG_TRY(rn_trunk<RN_S>(w, B, 4, b, s, &x, &Hc));
     const long nd = (long)B * D;
     hipLaunchKernelGGL(k_rn_avgpool, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, x, B, Hc * Hc, D, desc);
     MLG_LAUNCH_CHECK();
@@ -403,16 +393,20 @@ int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, in
 
 size_t mlg_resnet50_l3_ws_bytes(int B, int S) {
     if (B <= 0 || S != 320) return 0;
-    return rn_layout(B, 0, S).total;
+    return rn_carve(B, 0, S, nullptr, nullptr);
 }
 
-float* mlg_resnet50_l3_image(void* ws, int B, int S) { return (float*)((char*)ws + rn_layout(B, 0, S).img); }
+float* mlg_resnet50_l3_image(void* ws, int B, int S) {
+    RnBufs b;
+    rn_carve(B, 0, S, ws, &b);
+    return b.img;
+}
 
 int mlg_resnet50_l3_run(const mlg_rn_weights_i& w, int B, int S, void* ws, size_t ws_bytes, float** feat,
                         hipStream_t s) {
     if (B <= 0 || S != 320 || !feat) return MLG_EINVAL;  // one instantiation per supported side
-    const RnLayout L = rn_layout(B, 0, S);
-    if (ws_bytes < L.total) return MLG_ENOMEM;
+    RnBufs b;
+    if (rn_carve(B, 0, S, ws, &b) > ws_bytes) return MLG_ENOMEM;
     int side = 0;
-    return rn_trunk<320>(w, B, 3, (char*)ws, L, s, feat, &side);
+    return rn_trunk<320>(w, B, 3, b, s, feat, &side);
 }

@@ -34,10 +34,10 @@
 #include "common.h"
 #include "kernels.h"
 #include "pair_plan.h"
+#include "ws_carve.h"
 
 namespace {
 
-using pair_plan::a256;
 using pair_plan::Seg;
 static_assert(sizeof(pair_plan::Task) == sizeof(int4),
               "the host tables are uploaded by bytes into the kernels' int4 tables");
@@ -288,53 +288,55 @@ inline int sg_chunk(int kmax) {
     return (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)SG_CHUNK_MB << 20) / per));
 }
 
-struct SgLayout {
-    size_t x, cat, Q, K, Vt, ctx, h3, h4, live, ef, md, segs, tasks, outoff, S, T, u, v, pairs, rmax, ridx, cidx,
-        total;
+struct SgBufs {
+    float *X, *MD, *S, *T, *U, *V, *RMAX;
+    float* EF;  // identity rotary factors (lg_fac4 layout)
+    bf16_t *CAT, *Q, *K, *VT, *CTX, *H3, *H4;
+    uint8_t* LIVE;
+    Seg* SEGS;
+    int4* TASKS;
+    int* OUTOFF;
+    SgPair* PAIRS;
+    int32_t *RIDX, *CIDX;
 };
 
-SgLayout sg_layout(int P, int kmax) {
+size_t sg_carve(int P, int kmax, void* base, SgBufs* out) {
     const size_t N = (size_t)2 * P * (((size_t)kmax + 63) & ~(size_t)63);
     const size_t ldS = ((size_t)kmax + 3) & ~(size_t)3;
     const size_t ch = (size_t)sg_chunk(kmax);
-    SgLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += a256(bytes);
-        return r;
-    };
-    L.x = take(N * 256 * 4);
-    L.cat = take(N * 512 * 2);
-    L.Q = take(N * 256 * 2);
-    L.K = take(N * 256 * 2);
-    L.Vt = take(N * 256 * 2);
-    L.ctx = take(N * 256 * 2);
-    L.h3 = take(N * 128 * 2);
-    L.h4 = take(N * 256 * 2);
-    L.live = take(N);
-    L.ef = take(N * 64 * 4);
-    L.md = take(N * 256 * 4);
-    L.segs = take((size_t)2 * P * sizeof(Seg));
-    L.tasks = take((size_t)4 * P * sizeof(int4));
-    L.outoff = take((size_t)4 * P * 4);
-    L.S = take(ch * kmax * ldS * 4);
-    L.T = take(ch * kmax * ldS * 4);
-    L.u = take((size_t)P * (kmax + 4) * 4);
-    L.v = take((size_t)P * (kmax + 4) * 4);
-    L.pairs = take((size_t)P * sizeof(SgPair));
-    L.rmax = take(ch * kmax * 4);
-    L.ridx = take(ch * kmax * 4);
-    L.cidx = take(ch * kmax * 4);
-    L.total = o;
-    return L;
+    WsCarver c(base);
+    SgBufs b;
+    b.X = c.take<float>(N * 256);
+    b.CAT = c.take<bf16_t>(N * 512);
+    b.Q = c.take<bf16_t>(N * 256);
+    b.K = c.take<bf16_t>(N * 256);
+    b.VT = c.take<bf16_t>(N * 256);
+    b.CTX = c.take<bf16_t>(N * 256);
+    b.H3 = c.take<bf16_t>(N * 128);
+    b.H4 = c.take<bf16_t>(N * 256);
+    b.LIVE = c.take<uint8_t>(N);
+    b.EF = c.take<float>(N * 64);
+    b.MD = c.take<float>(N * 256);
+    b.SEGS = c.take<Seg>((size_t)2 * P);
+    b.TASKS = c.take<int4>((size_t)4 * P);
+    b.OUTOFF = c.take<int>((size_t)4 * P);
+    b.S = c.take<float>(ch * kmax * ldS);
+    b.T = c.take<float>(ch * kmax * ldS);
+    b.U = c.take<float>((size_t)P * (kmax + 4));
+    b.V = c.take<float>((size_t)P * (kmax + 4));
+    b.PAIRS = c.take<SgPair>((size_t)P);
+    b.RMAX = c.take<float>(ch * kmax);
+    b.RIDX = c.take<int32_t>(ch * kmax);
+    b.CIDX = c.take<int32_t>(ch * kmax);
+    if (out) *out = b;
+    return c.total();
 }
 
 }  // namespace
 
 size_t mlg_superglue_ws_bytes(int P, int kmax) {
     if (P <= 0 || kmax <= 0) return 0;
-    return sg_layout(P, kmax).total;
+    return sg_carve(P, kmax, nullptr, nullptr);
 }
 
 int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float* kscores, const float* desc,
@@ -344,32 +346,8 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     if (P <= 0 || kmax <= 0 || !kpts || !kscores || !desc || !counts || !pa || !pb || !matches || !mscores ||
         !nmatch || iters < 0)
         return MLG_EINVAL;
-    const SgLayout L = sg_layout(P, kmax);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* base = (char*)ws;
-    auto at = [&](size_t off) { return (void*)(base + off); };
-    float* X = (float*)at(L.x);
-    bf16_t* CAT = (bf16_t*)at(L.cat);
-    bf16_t* Q = (bf16_t*)at(L.Q);
-    bf16_t* K = (bf16_t*)at(L.K);
-    bf16_t* VT = (bf16_t*)at(L.Vt);
-    bf16_t* CTX = (bf16_t*)at(L.ctx);
-    bf16_t* H3 = (bf16_t*)at(L.h3);
-    bf16_t* H4 = (bf16_t*)at(L.h4);
-    uint8_t* LIVE = (uint8_t*)at(L.live);
-    float* EF = (float*)at(L.ef);  // identity rotary factors (lg_fac4 layout)
-    float* MD = (float*)at(L.md);
-    Seg* SEGS = (Seg*)at(L.segs);
-    int4* TASKS = (int4*)at(L.tasks);
-    int* OUTOFF = (int*)at(L.outoff);
-    float* S = (float*)at(L.S);
-    float* T = (float*)at(L.T);
-    float* U = (float*)at(L.u);
-    float* V = (float*)at(L.v);
-    SgPair* PAIRS = (SgPair*)at(L.pairs);
-    float* RMAX = (float*)at(L.rmax);
-    int32_t* RIDX = (int32_t*)at(L.ridx);
-    int32_t* CIDX = (int32_t*)at(L.cidx);
+    SgBufs b;
+    if (sg_carve(P, kmax, ws, &b) > ws_bytes) return MLG_EINVAL;
 
     if (hipMemsetAsync(nmatch, 0, sizeof(int32_t) * P, s) != hipSuccess) return MLG_EHIP;
     // segments (pair p -> [a | b], empty sides skipped) and the attention tables: pageable
@@ -383,28 +361,31 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     const int Npad = lay.Npad, nseg = (int)segs.size(), np = nseg / 2;
     att.build(segs);
     const int maxq = att.maxq;
-    if (!mlg_upload(SEGS, segs, s) || !mlg_upload(TASKS, att.tasks, s) || !mlg_upload(OUTOFF, att.out_off, s))
+    if (!mlg_upload(b.SEGS, segs, s) || !mlg_upload(b.TASKS, att.tasks, s) || !mlg_upload(b.OUTOFF, att.out_off, s))
         return MLG_EHIP;
-    hipLaunchKernelGGL(k_pair_live<>, dim3((Npad + 255) / 256), dim3(256), 0, s, SEGS, nseg, LIVE, Npad);
+    hipLaunchKernelGGL(k_pair_live<>, dim3((Npad + 255) / 256), dim3(256), 0, s, b.SEGS, nseg, b.LIVE, Npad);
     hipLaunchKernelGGL(k_sg_fill_rot, dim3((unsigned)(((long)Npad * 16 + 255) / 256)), dim3(256), 0, s,
-                       (float4*)EF, (long)Npad * 16);
+                       (float4*)b.EF, (long)Npad * 16);
     // keypoint encoder: layers 1-3 on the VALU, 4-5 as GEMMs; x = desc + kenc
-    hipLaunchKernelGGL(k_sg_gather, dim3(Npad), dim3(128), 0, s, SEGS, nseg, Npad, kpts, kscores, desc, kmax,
+    hipLaunchKernelGGL(k_sg_gather, dim3(Npad), dim3(128), 0, s, b.SEGS, nseg, Npad, kpts, kscores, desc, kmax,
                        (float)W, (float)H, w.kenc_w[0], w.kenc_b[0], w.kenc_w[1], w.kenc_b[1], w.kenc_w[2],
-                       w.kenc_b[2], X, H3);
+                       w.kenc_b[2], b.X, b.H3);
     MLG_LAUNCH_CHECK();
-    MLG_TRY(mlg_gemm_conv(H3, 128, w.kenc_w4, w.kenc_b4, nullptr, 0, nullptr, 0, H4, 256, 1, 256, Npad, 256, 128, s));
-    MLG_TRY(mlg_gemm_conv(H4, 256, w.kenc_w5, w.kenc_b5, X, 256, X, 256, CAT, 512, 0, 0, Npad, 256, 256, s));
+    MLG_TRY(mlg_gemm_conv(b.H3, 128, w.kenc_w4, w.kenc_b4, nullptr, 0, nullptr, 0, b.H4, 256, 1, 256, Npad, 256, 128,
+                          s));
+    MLG_TRY(mlg_gemm_conv(b.H4, 256, w.kenc_w5, w.kenc_b5, b.X, 256, b.X, 256, b.CAT, 512, 0, 0, Npad, 256, 256, s));
     // the GNN: 18 layers, self / cross alternating, every projection from the pre-layer states
     for (int l = 0; l < 18; ++l) {
         const bool cross = (l & 1) != 0;
-        MLG_TRY(mlg_lg_proj(true, CAT, 512, w.layer[l].Wqkv, w.layer[l].bqkv, EF, LIVE, Q, K, VT, Npad, s));
-        MLG_TRY(mlg_attention_varlen(Q, K, VT, CTX, 256, Npad, 4, TASKS + (cross ? nseg : 0),
-                                    OUTOFF + (cross ? nseg : 0), nseg, maxq, s));
-        MLG_TRY(mlg_lg_ffn(CTX, X, CAT, 512, Npad, w.layer[l], s, nullptr, 1));
+        MLG_TRY(mlg_lg_proj(true, b.CAT, 512, w.layer[l].Wqkv, w.layer[l].bqkv, b.EF, b.LIVE, b.Q, b.K, b.VT, Npad,
+                            s));
+        MLG_TRY(mlg_attention_varlen(b.Q, b.K, b.VT, b.CTX, 256, Npad, 4, b.TASKS + (cross ? nseg : 0),
+                                    b.OUTOFF + (cross ? nseg : 0), nseg, maxq, s));
+        MLG_TRY(mlg_lg_ffn(b.CTX, b.X, b.CAT, 512, Npad, w.layer[l], s, nullptr, 1));
     }
     // matching descriptors
-    MLG_TRY(mlg_gemm_conv(CAT, 512, w.Wfinal, w.bfinal, nullptr, 0, MD, 256, nullptr, 0, 0, 0, Npad, 256, 256, s));
+    MLG_TRY(
+        mlg_gemm_conv(b.CAT, 512, w.Wfinal, w.bfinal, nullptr, 0, b.MD, 256, nullptr, 0, 0, 0, Npad, 256, 256, s));
     // per chunk of pairs: scores and their transpose, Sinkhorn, mutual matches
     const int ldS = (kmax + 3) & ~3;
     const long sstride = (long)kmax * ldS;
@@ -412,36 +393,37 @@ int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float*
     std::vector<SgPair> hp(np);
     int uo = 0, vo = 0;
     for (int c = 0; c < np; ++c) {
-        const Seg a = segs[2 * c], b = segs[2 * c + 1];
-        hp[c] = SgPair{a.len, b.len, uo, vo, pair_of[c], 0, 0, 0};
-        uo += (a.len + 4) & ~3;  // 16-B aligned vectors
-        vo += (b.len + 4) & ~3;
+        const Seg sa = segs[2 * c], sb = segs[2 * c + 1];
+        hp[c] = SgPair{sa.len, sb.len, uo, vo, pair_of[c], 0, 0, 0};
+        uo += (sa.len + 4) & ~3;  // 16-B aligned vectors
+        vo += (sb.len + 4) & ~3;
     }
-    if (hipMemcpyAsync(PAIRS, hp.data(), np * sizeof(SgPair), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(U, 0, (size_t)uo * 4, s) != hipSuccess || hipMemsetAsync(V, 0, (size_t)vo * 4, s) != hipSuccess)
+    if (hipMemcpyAsync(b.PAIRS, hp.data(), np * sizeof(SgPair), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(b.U, 0, (size_t)uo * 4, s) != hipSuccess ||
+        hipMemsetAsync(b.V, 0, (size_t)vo * 4, s) != hipSuccess)
         return MLG_EHIP;
     for (int c0 = 0; c0 < np; c0 += chunk) {
         const int nc = std::min(chunk, np - c0);
         int mm = 0, nn = 0;
         for (int c = 0; c < nc; ++c) {
-            const Seg a = segs[2 * (c0 + c)], b = segs[2 * (c0 + c) + 1];
-            mm = std::max(mm, a.len);
-            nn = std::max(nn, b.len);
-            MLG_TRY(mlg_similarity_f32_t(MD + (size_t)a.off * 256, a.len, MD + (size_t)b.off * 256, b.len, 256,
-                                        S + (size_t)c * sstride, ldS, T + (size_t)c * sstride, ldS, s));
+            const Seg sa = segs[2 * (c0 + c)], sb = segs[2 * (c0 + c) + 1];
+            mm = std::max(mm, sa.len);
+            nn = std::max(nn, sb.len);
+            MLG_TRY(mlg_similarity_f32_t(b.MD + (size_t)sa.off * 256, sa.len, b.MD + (size_t)sb.off * 256, sb.len, 256,
+                                        b.S + (size_t)c * sstride, ldS, b.T + (size_t)c * sstride, ldS, s));
         }
-        const SgPair* pc = PAIRS + c0;
+        const SgPair* pc = b.PAIRS + c0;
         const dim3 rows((mm + 1 + 3) / 4, nc), cols((nn + 1 + 3) / 4, nc);
         for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(k_sg_lse<false>, rows, dim3(256), 0, s, S, sstride, ldS, pc, w.bin_score, U, V);
-            hipLaunchKernelGGL(k_sg_lse<true>, cols, dim3(256), 0, s, T, sstride, ldS, pc, w.bin_score, V, U);
+            hipLaunchKernelGGL(k_sg_lse<false>, rows, dim3(256), 0, s, b.S, sstride, ldS, pc, w.bin_score, b.U, b.V);
+            hipLaunchKernelGGL(k_sg_lse<true>, cols, dim3(256), 0, s, b.T, sstride, ldS, pc, w.bin_score, b.V, b.U);
         }
-        hipLaunchKernelGGL(k_sg_argmax<false>, dim3((mm + 3) / 4, nc), dim3(256), 0, s, S, sstride, ldS, pc, U, V,
-                           RMAX, RIDX, kmax);
-        hipLaunchKernelGGL(k_sg_argmax<true>, dim3((nn + 3) / 4, nc), dim3(256), 0, s, T, sstride, ldS, pc, U, V,
-                           (float*)nullptr, CIDX, kmax);
-        hipLaunchKernelGGL(k_sg_select, dim3(nc), dim3(1024), 0, s, pc, RMAX, RIDX, CIDX, kmax, thr, matches, mscores,
-                           nmatch);
+        hipLaunchKernelGGL(k_sg_argmax<false>, dim3((mm + 3) / 4, nc), dim3(256), 0, s, b.S, sstride, ldS, pc, b.U,
+                           b.V, b.RMAX, b.RIDX, kmax);
+        hipLaunchKernelGGL(k_sg_argmax<true>, dim3((nn + 3) / 4, nc), dim3(256), 0, s, b.T, sstride, ldS, pc, b.U,
+                           b.V, (float*)nullptr, b.CIDX, kmax);
+        hipLaunchKernelGGL(k_sg_select, dim3(nc), dim3(1024), 0, s, pc, b.RMAX, b.RIDX, b.CIDX, kmax, thr, matches,
+                           mscores, nmatch);
         MLG_LAUNCH_CHECK();
     }
     // the segment / task / pair tables are pageable host vectors still being copied

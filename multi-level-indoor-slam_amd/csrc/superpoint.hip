@@ -20,6 +20,7 @@
 // descriptor sampling are small memory-bound kernels.
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -712,41 +713,41 @@ int conv(const bf16_t* in, const bf16_t* w, const float* b, bf16_t* out, int B, 
     return MLG_OK;
 }
 
-#define SP_TRY(x)                   \
-    do {                            \
-        int rc_ = (x);              \
-        if (rc_ != MLG_OK) return rc_; \
-    } while (0)
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct SpLayout {
-    size_t a, b, logits, dmap, scores, tmp, mask, supp, ckey, cidx, total;
+struct SpBufs {
+    bf16_t *A, *Bf;  // ping-pong activations, each the size of conv1a's output (the largest)
+    float *logits, *dmap, *sc;
+    float *t0, *t1;  // two f32 temporaries, one region
+    uint8_t* mask;
+    uint8_t *u0, *u1;  // two u8 temporaries, one region
+    uint32_t* ckey;
+    int32_t* cidx;
 };
 
-SpLayout sp_layout(int B, int H, int W) {
-    SpLayout L;
-    const size_t HW = (size_t)H * W, cells = HW / 64;
-    const size_t big = a256((size_t)B * HW * 64 * 2);  // conv1a output (largest activation)
-    L.a = 0;
-    L.b = L.a + big;
-    L.logits = L.b + big;
-    L.dmap = L.logits + a256((size_t)B * cells * 128 * 4);
-    L.scores = L.dmap + a256((size_t)B * cells * 256 * 4);
-    L.tmp = L.scores + a256((size_t)B * HW * 4);
-    L.mask = L.tmp + a256((size_t)B * HW * 4 * 2);  // two f32 temporaries
-    L.supp = L.mask + a256((size_t)B * HW);
-    L.ckey = L.supp + a256((size_t)B * HW * 2);      // two u8 temporaries
-    L.cidx = L.ckey + a256((size_t)B * HW * 4);
-    L.total = L.cidx + a256((size_t)B * HW * 4);
-    return L;
+size_t sp_carve(int B, int H, int W, void* base, SpBufs* out) {
+    WsCarver c(base);
+    SpBufs b;
+    const size_t n = (size_t)B * H * W, cells = (size_t)H * W / 64;
+    b.A = c.take<bf16_t>(n * 64);
+    b.Bf = c.take<bf16_t>(n * 64);
+    b.logits = c.take<float>(B * cells * 128);
+    b.dmap = c.take<float>(B * cells * 256);
+    b.sc = c.take<float>(n);
+    b.t0 = c.take<float>(2 * n);
+    b.t1 = b.t0 ? b.t0 + n : nullptr;
+    b.mask = c.take<uint8_t>(n);
+    b.u0 = c.take<uint8_t>(2 * n);
+    b.u1 = b.u0 ? b.u0 + n : nullptr;
+    b.ckey = c.take<uint32_t>(n);
+    b.cidx = c.take<int32_t>(n);
+    if (out) *out = b;
+    return c.total();
 }
 
 }  // namespace
 
 size_t mlg_superpoint_ws_bytes(int B, int H, int W) {
     if (B <= 0 || H < 16 || W < 16) return 0;
-    return sp_layout(B, H, W).total;
+    return sp_carve(B, H, W, nullptr, nullptr);
 }
 
 int mlg_superpoint_run(const mlg_sp_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
@@ -755,82 +756,69 @@ int mlg_superpoint_run(const mlg_sp_weights_i& w, const uint8_t* frames, int B, 
     if (B <= 0 || H < 16 || W < 16 || (C != 1 && C != 3 && C != 4) || max_kp <= 0 ||
         max_kp > SEL_KMAX || nms_radius < 0 || border < 0)
         return MLG_EINVAL;
-    const SpLayout L = sp_layout(B, H, W);
-    if (ws_bytes < L.total) return MLG_EINVAL;
-    char* base = (char*)ws;
-    bf16_t* A = (bf16_t*)(base + L.a);
-    bf16_t* Bf = (bf16_t*)(base + L.b);
-    float* logits = (float*)(base + L.logits);
-    float* dmap = (float*)(base + L.dmap);
-    float* sc = (float*)(base + L.scores);
-    float* t0 = (float*)(base + L.tmp);
-    float* t1 = t0 + (size_t)B * H * W;
-    uint8_t* mask = (uint8_t*)(base + L.mask);
-    uint8_t* u0 = (uint8_t*)(base + L.supp);
-    uint8_t* u1 = u0 + (size_t)B * H * W;
-    uint32_t* ckey = (uint32_t*)(base + L.ckey);
-    int32_t* cidx = (int32_t*)(base + L.cidx);
+    SpBufs b;
+    if (sp_carve(B, H, W, ws, &b) > ws_bytes) return MLG_EINVAL;
 
     hipLaunchKernelGGL(k_sp_conv1a, dim3((W + TS - 1) / TS, (H + TS - 1) / TS, B), dim3(256), 0, s, frames,
-                       frame_stride, H, W, C, w.conv1a_w, w.conv1a_b, A);
+                       frame_stride, H, W, C, w.conv1a_w, w.conv1a_b, b.A);
     MLG_LAUNCH_CHECK();
     int h = H, wd = W;
-    SP_TRY((conv<64, 64, true>(A, w.w[0], w.b[0], Bf, B, h, wd, 64, s)));   // conv1b + pool
+    MLG_TRY((conv<64, 64, true>(b.A, w.w[0], w.b[0], b.Bf, B, h, wd, 64, s)));   // conv1b + pool
     h /= 2; wd /= 2;
-    SP_TRY((conv<64, 64, false>(Bf, w.w[1], w.b[1], A, B, h, wd, 64, s)));  // conv2a
-    SP_TRY((conv<64, 64, true>(A, w.w[2], w.b[2], Bf, B, h, wd, 64, s)));   // conv2b + pool
+    MLG_TRY((conv<64, 64, false>(b.Bf, w.w[1], w.b[1], b.A, B, h, wd, 64, s)));  // conv2a
+    MLG_TRY((conv<64, 64, true>(b.A, w.w[2], w.b[2], b.Bf, B, h, wd, 64, s)));   // conv2b + pool
     h /= 2; wd /= 2;
-    SP_TRY((conv<64, 128, false>(Bf, w.w[3], w.b[3], A, B, h, wd, 128, s)));   // conv3a
-    SP_TRY((conv<128, 128, true>(A, w.w[4], w.b[4], Bf, B, h, wd, 128, s)));   // conv3b + pool
+    MLG_TRY((conv<64, 128, false>(b.Bf, w.w[3], w.b[3], b.A, B, h, wd, 128, s)));   // conv3a
+    MLG_TRY((conv<128, 128, true>(b.A, w.w[4], w.b[4], b.Bf, B, h, wd, 128, s)));   // conv3b + pool
     h /= 2; wd /= 2;
-    SP_TRY((conv<128, 128, false>(Bf, w.w[5], w.b[5], A, B, h, wd, 128, s)));  // conv4a
-    SP_TRY((conv<128, 128, false>(A, w.w[6], w.b[6], Bf, B, h, wd, 128, s)));  // conv4b -> x (Bf)
+    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[5], w.b[5], b.A, B, h, wd, 128, s)));  // conv4a
+    MLG_TRY((conv<128, 128, false>(b.A, w.w[6], w.b[6], b.Bf, B, h, wd, 128, s)));  // conv4b -> x (b.Bf)
     const int M = B * h * wd;
-    bf16_t* cPa = A;
-    bf16_t* cDa = A + (size_t)M * 256;
-    SP_TRY((conv<128, 128, false>(Bf, w.w[7], w.b[7], cPa, B, h, wd, 256, s)));  // convPa
-    SP_TRY((conv<128, 128, false>(Bf, w.w[9], w.b[9], cDa, B, h, wd, 256, s)));  // convDa
-    SP_TRY(mlg_gemm_f32out(cPa, w.w[8], logits, M, 128, 256, s));                // convPb (65 of 128 rows)
-    SP_TRY(mlg_gemm_f32out(cDa, w.w[10], dmap, M, 256, 256, s));                 // convDb
-    hipLaunchKernelGGL(k_sp_scores, dim3((M + 255) / 256), dim3(256), 0, s, logits, 128, w.b[8], B, h, wd, sc);
+    bf16_t* cPa = b.A;
+    bf16_t* cDa = b.A + (size_t)M * 256;
+    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[7], w.b[7], cPa, B, h, wd, 256, s)));  // convPa
+    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[9], w.b[9], cDa, B, h, wd, 256, s)));  // convDa
+    MLG_TRY(mlg_gemm_f32out(cPa, w.w[8], b.logits, M, 128, 256, s));                // convPb (65 of 128 rows)
+    MLG_TRY(mlg_gemm_f32out(cDa, w.w[10], b.dmap, M, 256, 256, s));                 // convDb
+    hipLaunchKernelGGL(k_sp_scores, dim3((M + 255) / 256), dim3(256), 0, s, b.logits, 128, w.b[8], B, h, wd, b.sc);
     MLG_LAUNCH_CHECK();
     // the score map is 8 * floor(H / 8) x 8 * floor(W / 8): the encoder convolved the
     // full frame, its pools rounded down, and depth-to-space covers whole cells only
     H = 8 * h;
     W = 8 * wd;
     // simple_nms
-    const float* nms_out = sc;
+    const float* nms_out = b.sc;
     if (nms_radius == 4) {  // fused (SuperPoint's default radius)
         hipLaunchKernelGGL(k_sp_nms, dim3((unsigned)((W + NMS_TW - 1) / NMS_TW), (unsigned)((H + NMS_TH - 1) / NMS_TH),
                                           (unsigned)B),
-                           dim3(512), 0, s, sc, t0, B, H, W, border);
+                           dim3(512), 0, s, b.sc, b.t0, B, H, W, border);
         MLG_LAUNCH_CHECK();
-        nms_out = t0;
+        nms_out = b.t0;
     } else {  // multi-pass at full resolution
         const long n = (long)B * H * W;
         const dim3 g((unsigned)((n + 255) / 256)), t(256);
         auto maxpool_f = [&](const float* in, float* out) {
-            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, in, t1, B, H, W, nms_radius, 0);
-            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)t1, out, B, H, W, nms_radius, 1);
+            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, in, b.t1, B, H, W, nms_radius, 0);
+            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)b.t1, out, B, H, W, nms_radius, 1);
         };
-        maxpool_f(sc, t0);
-        hipLaunchKernelGGL(k_nms_init, g, t, 0, s, sc, t0, mask, n);
+        maxpool_f(b.sc, b.t0);
+        hipLaunchKernelGGL(k_nms_init, g, t, 0, s, b.sc, b.t0, b.mask, n);
         for (int it = 0; it < 2; ++it) {
-            hipLaunchKernelGGL(k_maxfilt<uint8_t>, g, t, 0, s, mask, u1, B, H, W, nms_radius, 0);
-            hipLaunchKernelGGL(k_maxfilt<uint8_t>, g, t, 0, s, (const uint8_t*)u1, u0, B, H, W, nms_radius, 1);
-            hipLaunchKernelGGL(k_nms_supp, g, t, 0, s, sc, u0, t0, n);   // t0 = supp_scores
-            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)t0, t1, B, H, W, nms_radius, 0);
-            float* mp = (float*)ckey;  // scratch (candidates are written later)
-            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)t1, mp, B, H, W, nms_radius, 1);
-            hipLaunchKernelGGL(k_nms_update, g, t, 0, s, t0, mp, u0, mask, n);
+            hipLaunchKernelGGL(k_maxfilt<uint8_t>, g, t, 0, s, b.mask, b.u1, B, H, W, nms_radius, 0);
+            hipLaunchKernelGGL(k_maxfilt<uint8_t>, g, t, 0, s, (const uint8_t*)b.u1, b.u0, B, H, W, nms_radius, 1);
+            hipLaunchKernelGGL(k_nms_supp, g, t, 0, s, b.sc, b.u0, b.t0, n);   // b.t0 = supp_scores
+            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)b.t0, b.t1, B, H, W, nms_radius, 0);
+            float* mp = (float*)b.ckey;  // scratch (candidates are written later)
+            hipLaunchKernelGGL(k_maxfilt<float>, g, t, 0, s, (const float*)b.t1, mp, B, H, W, nms_radius, 1);
+            hipLaunchKernelGGL(k_nms_update, g, t, 0, s, b.t0, mp, b.u0, b.mask, n);
         }
-        hipLaunchKernelGGL(k_nms_final, g, t, 0, s, sc, mask, B, H, W, border);
+        hipLaunchKernelGGL(k_nms_final, g, t, 0, s, b.sc, b.mask, B, H, W, border);
         MLG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_sp_select, dim3(B), dim3(SEL_T), 0, s, nms_out, H, W, det_thr, max_kp, ckey, cidx, kpts, kscores,
-                       count);
+    hipLaunchKernelGGL(k_sp_select, dim3(B), dim3(SEL_T), 0, s, nms_out, H, W, det_thr, max_kp, b.ckey, b.cidx, kpts,
+                       kscores, count);
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sp_desc, dim3((unsigned)(((long)B * max_kp + 3) / 4)), dim3(256), 0, s, dmap, w.b[10], B, h,
+    hipLaunchKernelGGL(k_sp_desc, dim3((unsigned)(((long)B * max_kp + 3) / 4)), dim3(256), 0, s, b.dmap, w.b[10], B, h,
                        wd, kpts, count, max_kp, desc, desc_bf16);
     MLG_LAUNCH_CHECK();
     return MLG_OK;

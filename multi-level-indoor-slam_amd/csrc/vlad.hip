@@ -18,6 +18,7 @@
 // No floating-point atomics anywhere: a frame's descriptor does not depend on the batch.
 #include "common.h"
 #include "kernels.h"
+#include "ws_carve.h"
 
 namespace {
 
@@ -27,8 +28,6 @@ constexpr int VCH = 64;          // channels per staged chunk
 constexpr int VLD = VCH + 4;     // LDS row stride: 16 rows x float4 cover the 64 banks once
 // k-means partial sums: at least 1536 tokens each (two gather passes), at most 256 per cluster
 constexpr int KM_SPLIT_MIN = 1536, KM_SPLITS_MAX = 256;
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 __global__ __launch_bounds__(64) void k_vlad_cnorm(const float* __restrict__ C, int K, float* __restrict__ Chat) {
     const int k = blockIdx.x, lane = threadIdx.x;
@@ -313,20 +312,20 @@ struct VladWs {
     int32_t* labels;
 };
 
-size_t vlad_carve(size_t rows, int B, int K, char* base, VladWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off = align_up(off + bytes);
-        return p;
-    };
+VladWs vlad_take(WsCarver& c, size_t rows, int B, int K) {
     VladWs o;
-    o.chat = (float*)take((size_t)VKMAX * VD * 4);
-    o.nrm = (float*)take(rows * 4);
-    o.labels = (int32_t*)take(rows * 4);
-    o.part = (float*)take((size_t)B * K * 4);
+    o.chat = c.take<float>((size_t)VKMAX * VD);
+    o.nrm = c.take<float>(rows);
+    o.labels = c.take<int32_t>(rows);
+    o.part = c.take<float>((size_t)B * K);
+    return o;
+}
+
+size_t vlad_carve(size_t rows, int B, int K, void* base, VladWs* w) {
+    WsCarver c(base);
+    const VladWs o = vlad_take(c, rows, B, K);
     if (w) *w = o;
-    return off;
+    return c.total();
 }
 
 int km_split_len(long M) {
@@ -340,16 +339,16 @@ struct KmWs {
     int32_t* pcnt;
 };
 
-size_t km_carve(long M, int K, char* base, KmWs* w) {
+// the VLAD head's buffers for one "frame" of M tokens, then the per-split partial sums
+size_t km_carve(long M, int K, void* base, KmWs* w) {
+    WsCarver c(base);
     KmWs o;
-    size_t off = vlad_carve((size_t)M, 1, K, base, &o.v);
+    o.v = vlad_take(c, (size_t)M, 1, K);
     const size_t S = (size_t)ceil_div(M, km_split_len(M));
-    o.psum = (float*)(base ? base + off : nullptr);
-    off = align_up(off + S * K * VD * 4);
-    o.pcnt = (int32_t*)(base ? base + off : nullptr);
-    off = align_up(off + S * K * 4);
+    o.psum = c.take<float>(S * K * VD);
+    o.pcnt = c.take<int32_t>(S * K);
     if (w) *w = o;
-    return off;
+    return c.total();
 }
 
 bool vlad_k_ok(int K) { return K >= 16 && K <= VKMAX && K % 16 == 0; }
@@ -383,12 +382,10 @@ size_t mlg_vlad_ws_bytes(int B, int P, int K) {
 
 int mlg_vlad_run(const float* centers, int K, const float* tokens, int B, int P, void* ws, size_t ws_bytes,
                  float* desc, int32_t* labels, hipStream_t s) {
-    const size_t need = mlg_vlad_ws_bytes(B, P, K);
-    if (!need || !centers || !tokens || !ws || !desc) return MLG_EINVAL;
+    if (!mlg_vlad_ws_bytes(B, P, K) || !centers || !tokens || !ws || !desc) return MLG_EINVAL;
     if (((uintptr_t)tokens | (uintptr_t)centers | (uintptr_t)desc) & 15) return MLG_EINVAL;  // float4 access
-    if (ws_bytes < need) return MLG_EINVAL;
     VladWs w;
-    vlad_carve((size_t)B * P, B, K, (char*)ws, &w);
+    if (vlad_carve((size_t)B * P, B, K, ws, &w) > ws_bytes) return MLG_EINVAL;
     if (!labels) labels = w.labels;
     MLG_TRY(vlad_assign(centers, K, tokens, B * P, w, labels, s));
     hipLaunchKernelGGL(k_vlad_agg, dim3(K, B), dim3(192), 0, s, tokens, P, centers, K, labels, w.nrm, desc, w.part);
@@ -405,12 +402,10 @@ size_t mlg_kmeans_ws_bytes(long M, int K) {
 
 int mlg_kmeans_step_run(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
                         int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s) {
-    const size_t need = mlg_kmeans_ws_bytes(M, K);
-    if (!need || !tokens || !centers || !labels || !changed || !counts || !ws) return MLG_EINVAL;
+    if (!mlg_kmeans_ws_bytes(M, K) || !tokens || !centers || !labels || !changed || !counts || !ws) return MLG_EINVAL;
     if (((uintptr_t)tokens | (uintptr_t)centers) & 15) return MLG_EINVAL;
-    if (ws_bytes < need) return MLG_EINVAL;
     KmWs w;
-    km_carve(M, K, (char*)ws, &w);
+    if (km_carve(M, K, ws, &w) > ws_bytes) return MLG_EINVAL;
     MLG_TRY(vlad_assign(centers, K, tokens, (int)M, w.v, w.v.labels, s));
     if (hipMemsetAsync(changed, 0, sizeof(int64_t), s) != hipSuccess) return MLG_EHIP;
     hipLaunchKernelGGL(k_km_changed, dim3(std::min(1024, ceil_div(M, 256))), dim3(256), 0, s, w.v.labels, labels,
