@@ -309,6 +309,64 @@ int mlg_op_lg_proj(int self_block, const uint16_t* xcopy, int ldx, const uint16_
  * [B, Ho, Wo, N], Ho = ceil(H / s); zero16 = 16 zero bytes on the device. */
 int mlg_op_conv2d_nhwc(const uint16_t* in, const uint16_t* zero16, int B, int H, int W, int C, int k, int s,
                        const uint16_t* Wt, const float* bias, float* out, int N, void* stream);
+/* The same convolution with every argument of its epilogue (as mlg_op_gemm_conv below,
+ * without vdiv): R f32 rows of ldr, out f32 rows of ldx and / or out16 bf16 rows of ldc. */
+int mlg_op_conv2d_nhwc_epi(const uint16_t* in, const uint16_t* zero16, int B, int H, int W, int C, int k, int s,
+                           const uint16_t* Wt, const float* bias, const float* R, int ldr, float* out, int ldx,
+                           uint16_t* out16, int ldc, int act, int act_cols, int N, void* stream);
+/* The bf16 GEMM's other epilogues, one entry per launcher (test access; the matcher and
+ * descriptor branches call the launchers themselves).  y = A W^T, A bf16 [M][lda] (lda >= K,
+ * lda % 8 == 0), W bf16 [N][K], K % 64 == 0, N % 128 == 0; device pointers.
+ *   gemm_conv: y (+ bias) (+ R[m][n], rows of ldr; R may be X), then on columns < act_cols
+ *     act 1 = ReLU, 2 = LeakyReLU(0.01), 3 = elu + 1, and with vdiv != 0 the columns >=
+ *     act_cols divided by it; stored f32 (X, ldx) and / or bf16 (C, ldc).  act_cols % 4 == 0.
+ *   gemm_conv_upadd: C bf16 [M][N] = (y + bias) + the bilinear x2 (align_corners) upsampling
+ *     of src f32 [B][h][w][N] at output pixel m of [B][2h][2w]; M % (4 h w) == 0.
+ *   gemm_bias_relu: C bf16 (rows of ldc) = relu(y + bias) on columns < nvalid (nvalid % 4 ==
+ *     0); the others are not written.
+ *   gemm_bias_add_relu: X f32 = relu((y + bias) + R) (rows of ldx, R may be X) and its bf16
+ *     copy C, rows of ldx too.
+ *   gemm_bias_f32_ld: C f32 (rows of ldc) = y + bias.
+ *   gemm_bias_split: y + bias as the pair hi = bf16(y), lo = bf16(y - hi), each k-step-major
+ *     [N / 16][M][16]; N % 16 == 0.
+ *   gemm_qkv (N = 2304, K = 768, M = B T): Q, K bf16 [12][B Tpad][64] at row b Tpad + t, V^T
+ *     bf16 [12][B Tpad / 64][64 d][64 keys]; Tpad % 64 == 0, Tpad >= T; rows t >= T not written.
+ *   gemm_patch (N = 768, K = Kpad, M = B P): X f32 [B (P + 1)][768], row b (P + 1) + 1 + p =
+ *     y + bias + pos[1 + p]; the cls rows b (P + 1) are not written.
+ *   gemm_sim_split_loftr: the split-bf16 product (as mlg_op_gemm_residual_split, A [M][2 K0],
+ *     B [Npad][2 K0]) / 256 / 0.1 into S f32 rows of lds: columns < ncols, -inf in [ncols,
+ *     lds); ncols <= lds <= Npad, lds % 4 == 0, Npad % 256 == 0.  nb > 1: problem z reads A and
+ *     B at + z pstride elements and writes rows z M + m. */
+int mlg_op_gemm_conv(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* R, int ldr,
+                     float* X, int ldx, uint16_t* C, int ldc, int act, int act_cols, int M, int N, int K, float vdiv,
+                     void* stream);
+int mlg_op_gemm_conv_upadd(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* src, int h,
+                           int w, uint16_t* C, int M, int N, int K, void* stream);
+int mlg_op_gemm_bias_relu(const uint16_t* A, int lda, const uint16_t* W, const float* bias, uint16_t* C, int ldc,
+                          int nvalid, int M, int N, int K, void* stream);
+int mlg_op_gemm_bias_add_relu(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* R,
+                              float* X, int ldx, uint16_t* C, int M, int N, int K, void* stream);
+int mlg_op_gemm_bias_f32_ld(const uint16_t* A, int lda, const uint16_t* W, const float* bias, float* C, int ldc, int M,
+                            int N, int K, void* stream);
+int mlg_op_gemm_bias_split(const uint16_t* A, int lda, const uint16_t* W, const float* bias, uint16_t* H, uint16_t* L,
+                           int M, int N, int K, void* stream);
+int mlg_op_gemm_qkv(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* Q, uint16_t* K, uint16_t* Vt,
+                    int M, int T, int Tpad, void* stream);
+int mlg_op_gemm_patch(const uint16_t* A, const uint16_t* W, const float* bias, const float* pos, float* X, int M,
+                      int P, int Kpad, void* stream);
+int mlg_op_gemm_sim_split_loftr(const uint16_t* A, const uint16_t* B, int M, int Npad, int K0, float* S, int lds,
+                                int ncols, int nb, long pstride, void* stream);
+/* mlg_op_lg_ffn with the block tail's mode and its fused heads.  relu 1: ReLU in place of
+ * LayerNorm + GELU; relu 2: LoFTR's encoder tail, msg = LN256(Wout ctx), X += LN256(Wf2
+ * relu(Wf1 [x | msg])), no biases, ln_g / ln_b = [norm1 | norm2].  wm != NULL: z = x . wm +
+ * bm[0] of the updated row, lz[m] = logsigmoid(z); with wc too: c = sigmoid(x . wc + bc[0]),
+ * flags[m] = (c < thr) | (sigmoid(z) > 1 - width || c <= thr) << 1.  Rows with rowseg[m] < 0
+ * get no lz and (with wc) flags 0.  wm == NULL: no heads, the other head arguments unused. */
+int mlg_op_lg_ffn_ex(const uint16_t* ctx, float* X, uint16_t* xcopy, int ldc, int M, const uint16_t* Wout,
+                     const float* bout, const uint16_t* Wf1, const float* bf1, const float* ln_g, const float* ln_b,
+                     const uint16_t* Wf2, const float* bf2, int relu, const int32_t* rowseg, const float* wc,
+                     const float* bc, const float* wm, const float* bm, float thr, float width, float* lz,
+                     uint8_t* flags, void* stream);
 int mlg_op_preprocess_patches(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, int S,
                               uint16_t* patches, void* stream);
 

@@ -697,6 +697,59 @@ int mlg_op_conv2d_nhwc(const uint16_t* in, const uint16_t* zero16, int B, int H,
     return mlg_conv_implicit(in, zero16, B, H, W, C, k, s, Wt, bias, nullptr, 0, out, N, nullptr, 0, 0, N, N,
                              (hipStream_t)stream);
 }
+int mlg_op_conv2d_nhwc_epi(const uint16_t* in, const uint16_t* zero16, int B, int H, int W, int C, int k, int s,
+                           const uint16_t* Wt, const float* bias, const float* R, int ldr, float* out, int ldx,
+                           uint16_t* out16, int ldc, int act, int act_cols, int N, void* stream) {
+    return mlg_conv_implicit(in, zero16, B, H, W, C, k, s, Wt, bias, R, ldr, out, ldx, out16, ldc, act, act_cols, N,
+                             (hipStream_t)stream);
+}
+int mlg_op_gemm_conv(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* R, int ldr,
+                     float* X, int ldx, uint16_t* C, int ldc, int act, int act_cols, int M, int N, int K, float vdiv,
+                     void* stream) {
+    return mlg_gemm_conv(A, lda, W, bias, R, ldr, X, ldx, C, ldc, act, act_cols, M, N, K, (hipStream_t)stream, vdiv);
+}
+int mlg_op_gemm_conv_upadd(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* src, int h,
+                           int w, uint16_t* C, int M, int N, int K, void* stream) {
+    return mlg_gemm_conv_upadd(A, lda, W, bias, src, h, w, C, M, N, K, (hipStream_t)stream);
+}
+int mlg_op_gemm_bias_relu(const uint16_t* A, int lda, const uint16_t* W, const float* bias, uint16_t* C, int ldc,
+                          int nvalid, int M, int N, int K, void* stream) {
+    return mlg_gemm_bias_relu_bf16(A, lda, W, bias, C, ldc, nvalid, M, N, K, (hipStream_t)stream);
+}
+int mlg_op_gemm_bias_add_relu(const uint16_t* A, int lda, const uint16_t* W, const float* bias, const float* R,
+                              float* X, int ldx, uint16_t* C, int M, int N, int K, void* stream) {
+    return mlg_gemm_bias_add_relu(A, lda, W, bias, R, X, ldx, C, M, N, K, (hipStream_t)stream);
+}
+int mlg_op_gemm_bias_f32_ld(const uint16_t* A, int lda, const uint16_t* W, const float* bias, float* C, int ldc, int M,
+                            int N, int K, void* stream) {
+    return mlg_gemm_bias_f32_ld(A, lda, W, bias, C, ldc, M, N, K, (hipStream_t)stream);
+}
+int mlg_op_gemm_bias_split(const uint16_t* A, int lda, const uint16_t* W, const float* bias, uint16_t* H, uint16_t* L,
+                           int M, int N, int K, void* stream) {
+    return mlg_gemm_bias_split_bf16(A, lda, W, bias, H, L, M, N, K, (hipStream_t)stream);
+}
+int mlg_op_gemm_qkv(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* Q, uint16_t* K, uint16_t* Vt,
+                    int M, int T, int Tpad, void* stream) {
+    return mlg_gemm_qkv(A, W, bias, Q, K, Vt, M, T, Tpad, (hipStream_t)stream);
+}
+int mlg_op_gemm_patch(const uint16_t* A, const uint16_t* W, const float* bias, const float* pos, float* X, int M,
+                      int P, int Kpad, void* stream) {
+    return mlg_gemm_patch(A, W, bias, pos, X, M, P, Kpad, (hipStream_t)stream);
+}
+int mlg_op_gemm_sim_split_loftr(const uint16_t* A, const uint16_t* B, int M, int Npad, int K0, float* S, int lds,
+                                int ncols, int nb, long pstride, void* stream) {
+    return mlg_gemm_sim_split_loftr(A, B, M, Npad, K0, S, lds, ncols, (hipStream_t)stream, nb, pstride);
+}
+int mlg_op_lg_ffn_ex(const uint16_t* ctx, float* X, uint16_t* xcopy, int ldc, int M, const uint16_t* Wout,
+                     const float* bout, const uint16_t* Wf1, const float* bf1, const float* ln_g, const float* ln_b,
+                     const uint16_t* Wf2, const float* bf2, int relu, const int32_t* rowseg, const float* wc,
+                     const float* bc, const float* wm, const float* bm, float thr, float width, float* lz,
+                     uint8_t* flags, void* stream) {
+    mlg_lg_block_i w{};
+    w.Wout = Wout; w.bout = bout; w.Wf1 = Wf1; w.bf1 = bf1; w.ln_g = ln_g; w.ln_b = ln_b; w.Wf2 = Wf2; w.bf2 = bf2;
+    const mlg_lg_conf_i cf{rowseg, wc, bc, wm, bm, thr, width, lz, flags};
+    return mlg_lg_ffn(ctx, X, xcopy, ldc, M, w, (hipStream_t)stream, &cf, relu);
+}
 int mlg_op_preprocess_patches(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, int S,
                               uint16_t* patches, void* stream) {
     return mlg_preprocess_patches(frames, B, H, W, C, frame_stride, S, MLG_VIT_PATCH_K, 1, patches,

@@ -236,7 +236,6 @@ struct EpiQKV {
     }
 };
 
-// relu(acc + b) -> bf16, columns >= nvalid dropped (N padded to the tile width)
 // EpiQKV for the split forward: hi planes as EpiQKV, lo planes lo_off elements further
 struct EpiQKVSplit {
     bf16_t* Q; bf16_t* K; bf16_t* Vt; const float* bias; int T, Tpad, Np; size_t lo_off;
@@ -283,6 +282,9 @@ struct EpiQKVSplit {
     }
 };
 
+// relu(acc + b) -> bf16, columns >= nvalid dropped (N padded to the tile width).
+// Contract: nvalid % 4 == 0 -- the test is on the first column of a lane's 4-column group,
+// and the group is stored whole.
 struct EpiBiasReluBF16 {
     bf16_t* C; int ldc; const float* bias; int nvalid;
     __device__ void operator()(int m, int n, const f32x4& v) const {
@@ -317,6 +319,8 @@ struct EpiBiasAddRelu {
 // Generic conv / linear epilogue (LoFTR, loftr.hip): y = acc (+ bias) (+ R[m, n]), then
 // act 1 = ReLU, 2 = LeakyReLU(0.01), 3 = elu + 1 on columns < act_cols; stored as f32
 // (X, ldx) and / or bf16 (C, ldc), either may be null.
+// Contract: act_cols % 4 == 0 -- the activation (and vdiv) boundary is tested on the first
+// column of a lane's 4-column group and applies to the whole group.
 struct EpiConv {
     // row-major outputs / residual: k_gemm256 runs it from an LDS row image (whole-row
     // accesses) -- see row_staged below

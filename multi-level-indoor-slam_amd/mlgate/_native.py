@@ -103,6 +103,26 @@ EXPORTS = {
     "mlg_op_lg_ffn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_void_p]),
     "mlg_op_lg_proj": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_void_p]),
     "mlg_op_conv2d_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int, c_void_p]),
+    "mlg_op_conv2d_nhwc_epi": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 3
+                               + [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mlg_op_gemm_conv": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                 c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "mlg_op_gemm_conv_upadd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                       c_int, c_int, c_void_p]),
+    "mlg_op_gemm_bias_relu": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p]),
+    "mlg_op_gemm_bias_add_relu": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_int, c_int, c_int, c_void_p]),
+    "mlg_op_gemm_bias_f32_ld": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_void_p]),
+    "mlg_op_gemm_bias_split": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_void_p]),
+    "mlg_op_gemm_qkv": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p]),
+    "mlg_op_gemm_patch": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
+    "mlg_op_gemm_sim_split_loftr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                            c_long, c_void_p]),
+    "mlg_op_lg_ffn_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_int]
+                         + [c_void_p] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "mlg_op_preprocess_patches": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p,
                                           c_void_p]),
     "mlg_prof_enable": (c_int, [c_int]),

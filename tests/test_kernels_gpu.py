@@ -254,6 +254,143 @@ def test_lg_ffn_fused(dev, M):
     assert torch.equal(xc[:, :256].cpu(), bf16_bits(got))
 
 
+def _ffn_problem(M, seed, row_scale=None):
+    """Host operands of one block tail: bf16 weights, f32 biases / LayerNorm affine, X, ctx."""
+    g = torch.Generator().manual_seed(seed)
+    W = {k: bf16_bits(torch.randn(*s, generator=g) / s[1] ** 0.5)
+         for k, s in (("Wout", (256, 256)), ("Wf1", (512, 512)), ("Wf2", (256, 512)))}
+    b = {k: torch.randn(n, generator=g) * 0.1 for k, n in (("bout", 256), ("bf1", 512), ("bf2", 256))}
+    ln_g, ln_b = 1 + 0.1 * torch.randn(512, generator=g), 0.1 * torch.randn(512, generator=g)
+    X = torch.randn(M, 256, generator=g)
+    if row_scale is not None:
+        X = X * row_scale[:, None]
+    return W, b, ln_g, ln_b, X, bf16_bits(torch.randn(M, 256, generator=g))
+
+
+def _ffn_run(dev, M, W, b, ln_g, ln_b, X, ctx, relu, heads=None):
+    """mlg_op_lg_ffn_ex on device copies; returns the updated X and its bf16 copy (host).
+    `heads`: rowseg, wc, bc, wm, bm, lz, flags device tensors (wc / bc may be None), thr, width."""
+    from mlgate.lightglue import pack_kstep
+    N_ = lambda t: None if t is None else P(t)  # noqa: E731
+    Xd, ctxd = X.to(dev), ctx.to(dev)
+    xc = torch.zeros(M, 512, dtype=torch.bfloat16, device=dev)
+    xc[:, :256] = bf16_bits(X).to(dev)
+    dW = {k: torch.from_numpy(pack_kstep(v.float().numpy())).to(torch.bfloat16).to(dev) for k, v in W.items()}
+    db = {k: v.to(dev) for k, v in b.items()}
+    gd, bd = ln_g.to(dev), ln_b.to(dev)
+    h = heads or {}
+    _native.check(_native.lib().mlg_op_lg_ffn_ex(
+        P(ctxd), P(Xd), P(xc), 512, M, P(dW["Wout"]), P(db["bout"]), P(dW["Wf1"]), P(db["bf1"]), P(gd), P(bd),
+        P(dW["Wf2"]), P(db["bf2"]), relu, N_(h.get("rowseg")), N_(h.get("wc")), N_(h.get("bc")), N_(h.get("wm")),
+        N_(h.get("bm")), h.get("thr", 0.0), h.get("width", 0.0), N_(h.get("lz")), N_(h.get("flags")), S(dev)),
+        "lg_ffn_ex")
+    torch.cuda.synchronize()
+    return Xd.cpu(), xc[:, :256].cpu()
+
+
+@pytest.mark.parametrize("M", [192, 1000, 128])
+def test_lg_ffn_fused_relu(dev, M):
+    """relu = 1 (SuperGlue's MLP: ReLU, no LayerNorm) against float64 on the same bf16
+    operands: x + W2 bf16(relu(W1 cat[x, bf16(Wout ctx + bout)] + b1)) + b2."""
+    W, b, ln_g, ln_b, X, ctx = _ffn_problem(M, 100 + M)
+    got, xc = _ffn_run(dev, M, W, b, ln_g, ln_b, X, ctx, 1)
+    w = {k: v.double() for k, v in W.items()}
+    msg = bf16_bits(ctx.double() @ w["Wout"].T + b["bout"].double()).double()
+    cat = torch.cat([bf16_bits(X).double(), msg], -1)
+    h = bf16_bits(torch.relu(cat @ w["Wf1"].T + b["bf1"].double())).double()
+    ref = X.double() + h @ w["Wf2"].T + b["bf2"].double()
+    assert torch.isfinite(got).all()
+    assert rel_err(got - X, ref - X.double()) < 1e-2
+    assert torch.equal(xc, bf16_bits(got))
+
+
+@pytest.mark.parametrize("M", [192, 1000, 128])
+def test_lg_ffn_fused_loftr(dev, M):
+    """relu = 2 (a LoFTREncoderLayer tail) against float64 computed directly: msg =
+    LN256(Wout ctx), x += LN256(W2 relu(W1 cat[x, msg])), no biases, eps 1e-5, ln_g / ln_b =
+    [norm1 | norm2]."""
+    W, b, ln_g, ln_b, X, ctx = _ffn_problem(M, 200 + M)
+    got, xc = _ffn_run(dev, M, W, b, ln_g, ln_b, X, ctx, 2)
+    w = {k: v.double() for k, v in W.items()}
+    g64, b64 = ln_g.double(), ln_b.double()
+    msg = bf16_bits(F.layer_norm(ctx.double() @ w["Wout"].T, (256,), g64[:256], b64[:256], eps=1e-5)).double()
+    cat = torch.cat([bf16_bits(X).double(), msg], -1)
+    h = bf16_bits(torch.relu(cat @ w["Wf1"].T)).double()
+    ref = X.double() + F.layer_norm(h @ w["Wf2"].T, (256,), g64[256:], b64[256:], eps=1e-5)
+    assert torch.isfinite(got).all()
+    assert rel_err(got - X, ref - X.double()) < 1e-2
+    assert torch.equal(xc, bf16_bits(got))
+
+
+@pytest.mark.parametrize("M", [192, 1000, 128])
+def test_lg_ffn_fused_heads(dev, M):
+    """The heads fused into the block tail (relu = 0): lz = logsigmoid(x . wm + bm) and flags
+    = (c < thr) | keep << 1, c = sigmoid(x . wc + bc), keep = sigmoid(z) > 1 - width or c <=
+    thr, against float64 from the X the kernel itself wrote (the GEMMs' error stays out).
+    Bound on a 256-term f32 dot in any order, its bias add and the f32 logsigmoid /
+    sigmoid (1- and 1/4-Lipschitz): 4 u (1 + |z|) + 256 u (|x| . |w|), u = 2^-24.  Rows
+    whose sigmoid lies within that bound of its threshold may go either way and are left
+    out of the flags check: at most 1 % of the rows, checked on the float64 reference
+    before the launch.  Rows are scaled by their index in the 64-row tile, so a row that
+    the 64-lane reduce-scatter permutes lands on another row's value; about 20 % of the
+    rows are dead (rowseg < 0), among them the first and last row of a 64-row tile and of
+    a wave's 16-row share: they keep the NaN in lz and get flags 0."""
+    u = 2.0 ** -24
+    thr, width = 0.625, 0.25  # exact in f32
+    idx = torch.arange(M)
+    W, b, ln_g, ln_b, X, ctx = _ffn_problem(M, 300 + M, 0.25 + (idx % 64).float() / 32.0)
+    g = torch.Generator().manual_seed(M)
+    wm, wc = torch.randn(256, generator=g) / 16, torch.randn(256, generator=g) / 16
+    bm, bc = torch.randn(1, generator=g) * 0.1, torch.randn(1, generator=g) * 0.1
+    dead = torch.rand(M, generator=g) < 0.2
+    for r in (0, 15, 16, 31, 63, 64, 127, M - 1):
+        dead[r] = True
+    rowseg = torch.where(dead, -1, idx // 100).to(torch.int32)
+
+    def expect(x):
+        x = x.double()
+        z, a = x @ wm.double() + bm.double(), x @ wc.double() + bc.double()
+        bz = 4 * u * (1 + z.abs()) + 256 * u * (x.abs() @ wm.double().abs())
+        ba = 4 * u * (1 + a.abs()) + 256 * u * (x.abs() @ wc.double().abs())
+        c = torch.sigmoid(a)
+        near = ((c - thr).abs() < ba) | ((torch.sigmoid(z) - (1 - width)).abs() < bz)
+        flags = ((c < thr).to(torch.uint8) | (((torch.sigmoid(z) > 1 - width) | (c <= thr)).to(torch.uint8) << 1))
+        return z, bz, near, flags
+
+    # the excluded share and the mix of flag values, on the float64 reference alone
+    w = {k: v.double() for k, v in W.items()}
+    msg = bf16_bits(ctx.double() @ w["Wout"].T + b["bout"].double()).double()
+    hid = torch.cat([bf16_bits(X).double(), msg], -1) @ w["Wf1"].T + b["bf1"].double()
+    hid = bf16_bits(F.gelu(F.layer_norm(hid, (512,), ln_g.double(), ln_b.double()))).double()
+    _, _, near, fl = expect(X.double() + hid @ w["Wf2"].T + b["bf2"].double())
+    assert near[~dead].float().mean().item() <= 0.01
+    assert len(torch.unique(fl[~dead])) >= 3  # the thresholds split the rows
+
+    def run(with_conf):
+        h = dict(rowseg=rowseg.to(dev), wm=wm.to(dev), bm=bm.to(dev), thr=thr, width=width,
+                 lz=torch.full((M,), float("nan"), device=dev),
+                 flags=torch.full((M,), 0xAA, dtype=torch.uint8, device=dev))
+        if with_conf:
+            h.update(wc=wc.to(dev), bc=bc.to(dev))
+        got, _ = _ffn_run(dev, M, W, b, ln_g, ln_b, X, ctx, 0, h)
+        return got, h["lz"].cpu(), h["flags"].cpu()
+
+    got, lz, flags = run(True)
+    z, bz, near, want = expect(got)
+    live = ~dead
+    print(f"heads M={M}: {int((near & live).sum())} of {int(live.sum())} live rows within the bound of a threshold "
+          f"({100.0 * (near & live).sum().item() / live.sum().item():.3f} %), "
+          f"max lz err / bound {((lz.double() - F.logsigmoid(z)).abs() / bz)[live].max().item():.3f}")
+    assert bool(torch.isnan(lz[dead]).all()) and bool((flags[dead] == 0).all())
+    assert bool(((lz.double() - F.logsigmoid(z)).abs() <= bz)[live].all())
+    assert (near & live).float().sum().item() <= 0.01 * live.sum().item()
+    ok = live & ~near
+    assert torch.equal(flags[ok], want[ok])
+    got2, lz2, flags2 = run(False)  # heads without conf: flags are not written
+    assert torch.equal(got2, got) and torch.equal(lz2[live], lz[live]) and bool(torch.isnan(lz2[dead]).all())
+    assert bool((flags2 == 0xAA).all())
+
+
 @pytest.mark.parametrize("self_block", [True, False])
 def test_lg_proj(dev, self_block):
     """LightGlue projections (lg_proj.hip) vs float32 torch on the same bf16 operands:
