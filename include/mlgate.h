@@ -50,7 +50,7 @@ const char* mlg_strerror(int status);
 
 /* ------------------------------------------------------------------ ViT-B/14 --
  * Device weights of the hub dinov2_vitb14 network in kernel layout (see
- * mlgate/vit.py:_pack_weights): GEMM weights bf16 [out, in] (nn.Linear layout),
+ * mlgate/vit.py pack_weights): GEMM weights bf16 [out, in] (nn.Linear layout),
  * everything else float32.  `pos` is the position embedding already resampled to
  * the (S/14)^2 patch grid (hub interpolate_pos_encoding), [1 + (S/14)^2, 768].
  */
@@ -116,7 +116,7 @@ int mlg_vit_forward(const mlg_vit_weights* w, const uint8_t* frames, int batch, 
 /* ------------------------------------------------------------------- SALAD --
  * SALAD's native branch (place_recognition.py:357-368, 380-391): serizba/salad's
  * aggregator over the same DINOv2 ViT-B/14 (all final-LayerNorm tokens).  Weights in
- * kernel layout (mlgate/vpr.py SaladGPU._pack):
+ * kernel layout (mlgate/salad.py pack_aggregator):
  *   w1 bf16 [1024, 768]  rows 0..511 cluster_features.0, 512..1023 score.0 (1x1 convs)
  *   w2 bf16 [256, 1024]  rows 0..127 [cluster_features.3 | 0], 128..191 [0 | score.3],
  *                        192..255 zero; b1 [1024], b2 [256] float32

@@ -445,11 +445,6 @@ int mlg_proximity_emit(const double* pos, const int64_t* floor, int N, int row0,
                                   pairs, dist, valid, (hipStream_t)stream);
 }
 
-// the internal tables are the public structs past their 8-byte head
-static_assert(offsetof(mlg_rn_weights, stem_w) == 8 &&
-                  sizeof(mlg_rn_weights) - offsetof(mlg_rn_weights, stem_w) == sizeof(mlg_rn_weights_i),
-              "ResNet weight tables must match");
-
 size_t mlg_resnet50_workspace_bytes(int B, int H, int W) { return mlg_resnet50_ws_bytes(B, H, W); }
 
 int mlg_resnet50_forward(const mlg_rn_weights* w, const uint8_t* frames, int B, int H, int W, int C,
@@ -464,20 +459,17 @@ int mlg_resnet50_forward(const mlg_rn_weights* w, const uint8_t* frames, int B, 
         if (first != (b.wd != nullptr) || (b.wd && !b.bd)) return MLG_EINVAL;
     }
     if (frame_stride < (long)H * W * C) return MLG_EINVAL;
-    return mlg_resnet50_run(*reinterpret_cast<const mlg_rn_weights_i*>(&w->stem_w), frames, B, H, W, C, frame_stride,
-                            descriptor_dim, workspace, workspace_bytes, desc, nullptr, (hipStream_t)stream);
+    return mlg_resnet50_run(*w, frames, B, H, W, C, frame_stride, descriptor_dim, workspace, workspace_bytes, desc,
+                            nullptr, (hipStream_t)stream);
 }
 
 int mlg_op_pillow_resize_224(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, void* workspace,
                              size_t workspace_bytes, uint8_t* out, void* stream) {
     if (!frames || !workspace || !out || frame_stride < (long)H * W * C) return MLG_EINVAL;
-    mlg_rn_weights_i none{};
+    const mlg_rn_weights none{};  // the resize reads no weights
     return mlg_resnet50_run(none, frames, B, H, W, C, frame_stride, 1, workspace, workspace_bytes, nullptr, out,
                             (hipStream_t)stream);
 }
-
-static_assert(offsetof(mlg_mixvpr_weights, mix_w) + sizeof(mlg_mix_weights_i) == sizeof(mlg_mixvpr_weights),
-              "MixVPR head weight tables must match");
 
 size_t mlg_mixvpr_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -495,23 +487,20 @@ int mlg_mixvpr_forward(const mlg_mixvpr_weights* w, const uint8_t* frames, int B
         return MLG_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || frame_stride < (long)H * W * C)
         return MLG_EINVAL;
-    mlg_rn_weights_i rn{};
-    rn.stem_w = w->stem_w;
-    rn.stem_b = w->stem_b;
     for (int i = 0; i < 13; ++i) {
         const mlg_rn_block& b = w->blocks[i];
         if (!b.w1 || !b.b1 || !b.w2 || !b.b2 || !b.w3 || !b.b3) return MLG_EINVAL;
         const bool first = i == 0 || i == 3 || i == 7;
         if (first != (b.wd != nullptr) || (b.wd && !b.bd)) return MLG_EINVAL;
-        rn.blocks[i] = {b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, b.wd, b.bd};
     }
     if (workspace_bytes < mlg_mixvpr_workspace_bytes(B, H, W)) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
     MLG_TRY(mlg_mixvpr_preprocess(frames, B, H, W, C, frame_stride,
                                   mlg_resnet50_l3_image(workspace, B, MLG_MIXVPR_SIZE), s));
     float* feat = nullptr;
-    MLG_TRY(mlg_resnet50_l3_run(rn, B, MLG_MIXVPR_SIZE, workspace, workspace_bytes, &feat, s));
-    return mlg_mixvpr_head(*reinterpret_cast<const mlg_mix_weights_i*>(&w->mix_w), feat, B, desc, s);
+    MLG_TRY(mlg_resnet50_l3_run(w->stem_w, w->stem_b, w->blocks, B, MLG_MIXVPR_SIZE, workspace, workspace_bytes, &feat,
+                                s));
+    return mlg_mixvpr_head(*w, feat, B, desc, s);
 }
 
 int mlg_op_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, float* out,
@@ -521,8 +510,7 @@ int mlg_op_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, 
 
 int mlg_op_mixvpr_head(const mlg_mixvpr_weights* w, const float* features, int B, float* desc, void* stream) {
     if (!mlg_head_ok(w, MLG_ABI_VERSION) || !mixvpr_head_ok(w)) return MLG_EINVAL;
-    return mlg_mixvpr_head(*reinterpret_cast<const mlg_mix_weights_i*>(&w->mix_w), features, B, desc,
-                           (hipStream_t)stream);
+    return mlg_mixvpr_head(*w, features, B, desc, (hipStream_t)stream);
 }
 
 size_t mlg_superpoint_workspace_bytes(int B, int H, int W) { return mlg_superpoint_ws_bytes(B, H, W); }
@@ -534,26 +522,16 @@ int mlg_superpoint(const mlg_sp_weights* w, const uint8_t* frames, int B, int H,
     if (!mlg_head_ok(w, MLG_ABI_VERSION) || !frames || !workspace || !keypoints || !scores || !descriptors || !counts)
         return MLG_EINVAL;
     if (!w->conv1a_w || !w->conv1a_b) return MLG_EINVAL;
-    mlg_sp_weights_i wi;
-    wi.conv1a_w = w->conv1a_w;
-    wi.conv1a_b = w->conv1a_b;
     for (int i = 0; i < 11; ++i) {
         if (!w->w[i] || !w->b[i]) return MLG_EINVAL;
         if ((reinterpret_cast<uintptr_t>(w->w[i]) & 15) || (reinterpret_cast<uintptr_t>(w->b[i]) & 15))
             return MLG_EINVAL;
-        wi.w[i] = (const bf16_t*)w->w[i];
-        wi.b[i] = w->b[i];
     }
     if (frame_stride < (long)H * W * C) return MLG_EINVAL;
-    return mlg_superpoint_run(wi, frames, B, H, W, C, frame_stride, detection_threshold, max_keypoints, nms_radius,
+    return mlg_superpoint_run(*w, frames, B, H, W, C, frame_stride, detection_threshold, max_keypoints, nms_radius,
                               remove_borders, workspace, workspace_bytes, keypoints, scores, descriptors,
                               descriptors_bf16, counts, (hipStream_t)stream);
 }
-
-static_assert(offsetof(mlg_lg_weights, Wr) == 8 &&
-                  sizeof(mlg_lg_weights) - offsetof(mlg_lg_weights, Wr) == sizeof(mlg_lg_weights_i),
-              "LightGlue weight tables must match");
-static_assert(sizeof(mlg_lg_block) == sizeof(mlg_lg_block_i), "LightGlue block tables must match");
 
 size_t mlg_lightglue_workspace_bytes(int P, int kmax) { return mlg_lightglue_ws_bytes(P, kmax); }
 
@@ -567,15 +545,10 @@ int mlg_lightglue(const mlg_lg_weights* w, const float* keypoints, const float* 
         return MLG_EINVAL;
     for (int p = 0; p < P; ++p)
         if (pair_a[p] < 0 || pair_a[p] >= F || pair_b[p] < 0 || pair_b[p] >= F) return MLG_EINVAL;
-    const mlg_lg_weights_i& wi = *reinterpret_cast<const mlg_lg_weights_i*>(&w->Wr);
-    return mlg_lightglue_run(wi, keypoints, descriptors, counts, kmax, pair_a, pair_b, P, depth_confidence,
+    return mlg_lightglue_run(*w, keypoints, descriptors, counts, kmax, pair_a, pair_b, P, depth_confidence,
                              width_confidence, filter_threshold, pruning_min_kpts, workspace, workspace_bytes,
                              matches, scores, num_matches, stop_layer, (hipStream_t)stream);
 }
-
-static_assert(offsetof(mlg_sg_weights, kenc_w) == 8 &&
-                  sizeof(mlg_sg_weights) - offsetof(mlg_sg_weights, kenc_w) == sizeof(mlg_sg_weights_i),
-              "SuperGlue weight tables must match");
 
 size_t mlg_superglue_workspace_bytes(int P, int kmax) { return mlg_superglue_ws_bytes(P, kmax); }
 
@@ -588,8 +561,7 @@ int mlg_superglue(const mlg_sg_weights* w, const float* keypoints, const float* 
         return MLG_EINVAL;
     for (int p = 0; p < P; ++p)
         if (pair_a[p] < 0 || pair_a[p] >= F || pair_b[p] < 0 || pair_b[p] >= F) return MLG_EINVAL;
-    const mlg_sg_weights_i& wi = *reinterpret_cast<const mlg_sg_weights_i*>(&w->kenc_w);
-    return mlg_superglue_run(wi, keypoints, scores, descriptors, counts, kmax, W, H, pair_a, pair_b, P,
+    return mlg_superglue_run(*w, keypoints, scores, descriptors, counts, kmax, W, H, pair_a, pair_b, P,
                              sinkhorn_iterations, match_threshold, workspace, workspace_bytes, matches, match_scores,
                              num_matches, (hipStream_t)stream);
 }
@@ -682,7 +654,7 @@ int mlg_op_attention_varlen(const uint16_t* Q, const uint16_t* K, const uint16_t
 int mlg_op_lg_ffn(const uint16_t* ctx, float* X, uint16_t* xcopy, int ldc, int M, const uint16_t* Wout,
                   const float* bout, const uint16_t* Wf1, const float* bf1, const float* ln_g, const float* ln_b,
                   const uint16_t* Wf2, const float* bf2, void* stream) {
-    mlg_lg_block_i w{};
+    mlg_lg_block w{};
     w.Wout = Wout; w.bout = bout; w.Wf1 = Wf1; w.bf1 = bf1; w.ln_g = ln_g; w.ln_b = ln_b; w.Wf2 = Wf2; w.bf2 = bf2;
     return mlg_lg_ffn(ctx, X, xcopy, ldc, M, w, (hipStream_t)stream);
 }
@@ -745,7 +717,7 @@ int mlg_op_lg_ffn_ex(const uint16_t* ctx, float* X, uint16_t* xcopy, int ldc, in
                      const uint16_t* Wf2, const float* bf2, int relu, const int32_t* rowseg, const float* wc,
                      const float* bc, const float* wm, const float* bm, float thr, float width, float* lz,
                      uint8_t* flags, void* stream) {
-    mlg_lg_block_i w{};
+    mlg_lg_block w{};
     w.Wout = Wout; w.bout = bout; w.Wf1 = Wf1; w.bf1 = bf1; w.ln_g = ln_g; w.ln_b = ln_b; w.Wf2 = Wf2; w.bf2 = bf2;
     const mlg_lg_conf_i cf{rowseg, wc, bc, wm, bm, thr, width, lz, flags};
     return mlg_lg_ffn(ctx, X, xcopy, ldc, M, w, (hipStream_t)stream, &cf, relu);

@@ -7,7 +7,9 @@
 
 #include <algorithm>
 
-typedef uint16_t bf16_t;
+#include "../../include/mlgate.h"
+
+typedef uint16_t bf16_t;  // the public weight structs' uint16_t
 
 // The head every struct argument of the C ABI begins with (include/mlgate.h
 // MLG_STRUCT_INIT): true iff it names this struct's size and the library's ABI version.
@@ -155,33 +157,11 @@ int mlg_recover_pose_run(const float* kp1, const float* kp2, const int32_t* offs
                          int k_stride, const double* E, const uint8_t* mask, double* pose, hipStream_t s);
 
 // superpoint.hip -- SuperPoint detector / descriptor
-struct mlg_sp_weights_i {
-    const float* conv1a_w;  // f32 [64][9]
-    const float* conv1a_b;  // f32 [64]
-    const bf16_t* w[11];    // conv1b conv2a conv2b conv3a conv3b conv4a conv4b convPa convPb convDa convDb
-    const float* b[11];
-};
 size_t mlg_superpoint_ws_bytes(int B, int H, int W);
-int mlg_superpoint_run(const mlg_sp_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+int mlg_superpoint_run(const mlg_sp_weights& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                        float det_thr, int max_kp, int nms_radius, int border, void* ws, size_t ws_bytes, float* kpts,
                        float* kscores, float* desc, uint16_t* desc_bf16, int32_t* count, hipStream_t s);
 
-// lightglue.hip -- LightGlue matcher over a ragged batch of pairs
-struct mlg_lg_block_i {
-    const bf16_t* Wqkv; const float* bqkv;  // self: [768][256]; cross: [to_qk; to_v] [512][256] (k-step-major)
-    const bf16_t* Wout; const float* bout;  // [256][256]   } packed k-step-major,
-    const bf16_t* Wf1;  const float* bf1;   // [512][512]   } [K/16][N][16] (lg_ffn.hip)
-    const float* ln_g;  const float* ln_b;  // [512]
-    const bf16_t* Wf2;  const float* bf2;   // [256][512]   }
-};
-struct mlg_lg_weights_i {
-    const float* Wr;  // [32][2]
-    mlg_lg_block_i self[9], cross[9];
-    const bf16_t* Wfinal[9]; const float* bfinal[9];  // [256][256], [256]
-    const float* wmatch[9];  const float* bmatch[9];  // [256], [1]
-    const float* wconf[8];   const float* bconf[8];   // [256], [1]
-    const float* ones;                                 // [256] of 1.0f
-};
 // lg_ffn.hip -- fused out_proj + FFN (Linear, LayerNorm, GELU, Linear) + residual of one
 // LightGlue block over M token rows: X f32 [M][256] updated in place, its bf16 copy
 // xcopy [M][ldc] (cols 0..255; read as the GEMM operand, then rewritten); ctx bf16
@@ -200,7 +180,7 @@ struct mlg_lg_conf_i {
 // relu == 1: ReLU without LayerNorm (SuperGlue's MLP with BatchNorm folded into Wf1);
 // relu == 2: a LoFTREncoderLayer tail (no biases; Wout = merge, then norm1; ReLU MLP; norm2
 // before the residual; ln_g / ln_b = [norm1 | norm2], 256 each)
-int mlg_lg_ffn(const bf16_t* ctx, float* X, bf16_t* xcopy, int ldc, int M, const mlg_lg_block_i& w, hipStream_t s,
+int mlg_lg_ffn(const bf16_t* ctx, float* X, bf16_t* xcopy, int ldc, int M, const mlg_lg_block& w, hipStream_t s,
                const mlg_lg_conf_i* conf = nullptr, int relu = 0);
 // lg_proj.hip -- LightGlue q/k/v projections (+ rotary for the self block) straight into
 // the attention operands; W packed k-step-major [16][768 | 512][16]; Npad % 64 == 0.
@@ -208,66 +188,39 @@ int mlg_lg_ffn(const bf16_t* ctx, float* X, bf16_t* xcopy, int ldc, int M, const
 int mlg_lg_proj(bool self_block, const bf16_t* xcopy, int ldx, const bf16_t* W, const float* bias, const float* efac,
                 const uint8_t* live, bf16_t* Q, bf16_t* K, bf16_t* Vt, int Npad, hipStream_t s);
 // superglue.hip -- SuperGlue GNN + log-space optimal transport over a ragged batch of pairs
-struct mlg_sg_weights_i {
-    const float* kenc_w[3]; const float* kenc_b[3];
-    const bf16_t* kenc_w4; const float* kenc_b4;
-    const bf16_t* kenc_w5; const float* kenc_b5;
-    mlg_lg_block_i layer[18];
-    const bf16_t* Wfinal; const float* bfinal;
-    float bin_score;
-};
 size_t mlg_superglue_ws_bytes(int P, int kmax);
-int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float* kscores, const float* desc,
+int mlg_superglue_run(const mlg_sg_weights& w, const float* kpts, const float* kscores, const float* desc,
                       const int32_t* counts, int kmax, int W, int H, const int32_t* pa, const int32_t* pb, int P,
                       int iters, float thr, void* ws, size_t ws_bytes, int32_t* matches, float* mscores,
                       int32_t* nmatch, hipStream_t s);
+// lightglue.hip -- LightGlue matcher over a ragged batch of pairs
 size_t mlg_lightglue_ws_bytes(int P, int kmax);
-int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float* desc, const int32_t* counts, int kmax,
+int mlg_lightglue_run(const mlg_lg_weights& w, const float* kpts, const float* desc, const int32_t* counts, int kmax,
                       const int32_t* pa, const int32_t* pb, int P, float depth_conf, float width_conf,
                       float filter_thr, int pruning_min, void* ws, size_t ws_bytes, int32_t* matches, float* mscores,
                       int32_t* nmatch, int32_t* stop_layer, hipStream_t s);
 
 // resnet.hip -- ResNet-50 GAP descriptor (MixVPR / SALAD fallback)
-struct mlg_rn_block_i {
-    const bf16_t* w1; const float* b1;  // conv1 1x1 [max(width,128)][Cin] (BN folded; pad rows zero)
-    const bf16_t* w2; const float* b2;  // conv2 3x3 [max(width,128)][9 * width] (k = tap * width + c)
-    const bf16_t* w3; const float* b3;  // conv3 1x1 [4 width][width]
-    const bf16_t* wd; const float* bd;  // downsample 1x1 [4 width][Cin] or NULL
-};
-struct mlg_rn_weights_i {
-    const float* stem_w;  // f32 [64][7][7][3] (BN folded)
-    const float* stem_b;  // f32 [64]
-    mlg_rn_block_i blocks[16];
-};
 size_t mlg_resnet50_ws_bytes(int B, int H, int W);
 // resized_u8 != NULL: only the Pillow resize runs, into [B, 224, 224, 3] (parity entry)
-int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+int mlg_resnet50_run(const mlg_rn_weights& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                      int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s);
 
 // The same trunk cropped after layer3 at input side S (320: MixVPR's native branch): the
 // caller writes the normalised f32 NHWC image [B, S, S, 3] at mlg_resnet50_l3_image(ws),
 // the run leaves *feat -> the f32 residual stream [B, (S/16)^2, 1024] inside ws.
-// w.blocks[13..15] are not read.
+// blocks: the 13 bottlenecks of layer1..3.
 size_t mlg_resnet50_l3_ws_bytes(int B, int S);
 float* mlg_resnet50_l3_image(void* ws, int B, int S);
-int mlg_resnet50_l3_run(const mlg_rn_weights_i& w, int B, int S, void* ws, size_t ws_bytes, float** feat,
-                        hipStream_t s);
+int mlg_resnet50_l3_run(const float* stem_w, const float* stem_b, const mlg_rn_block* blocks, int B, int S, void* ws,
+                        size_t ws_bytes, float** feat, hipStream_t s);
 
 // mixvpr.hip -- MixVPR's native branch: cv2 preprocessing to 320 x 320 and the fused
 // feature-mixer head (4 mixer blocks + row_proj per 64-row tile, then channel_proj + L2 norm)
-struct mlg_mix_weights_i {
-    const bf16_t* mix_w;   // bf16 [4 blocks][2][26][416][16]: Linear1 / Linear2 k-step-major, zero-padded 400 -> 416
-    const float* mix_p;    // f32 [4 blocks][4][512]: LayerNorm gamma, beta, bias1, bias2 (zero past 400)
-    const float* row_w;    // f32 [4][512]: row_proj.weight (zero past 400)
-    const float* chan_w;   // f32 [1024][1024]: channel_proj.weight
-    const float* chan_b;   // f32 [1024]: channel_proj.bias
-    const float* row_s;    // f32 [4]: sum_i row_proj.weight[r][i]
-    const float* row_b;    // f32 [4]: row_proj.bias
-};
 int mlg_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, long frame_stride, float* out,
                           hipStream_t s);
 // feat f32 [B, 400, 1024] (NHWC layer3 stream) -> desc f32 [B, 4096], L2-normalised
-int mlg_mixvpr_head(const mlg_mix_weights_i& w, const float* feat, int B, float* desc, hipStream_t s);
+int mlg_mixvpr_head(const mlg_mixvpr_weights& w, const float* feat, int B, float* desc, hipStream_t s);
 
 // vlad.hip -- AnyLoc's native branch: hard-assignment VLAD over f32 tokens [B, P, 768] and
 // one Lloyd update of its vocabulary.  Both validate their arguments (MLG_EINVAL) and

@@ -161,7 +161,7 @@ __device__ __forceinline__ void zero(f32x16 (&acc)[NT][MT]) {
 // interleave groups across blocks).
 template <bool LOFTR = false, bool RELU = false>
 __global__ __launch_bounds__(64 * NW, 2) void k_lg_ffn(const bf16_t* __restrict__ ctx, float* __restrict__ X,
-                                                  bf16_t* __restrict__ xcopy, int ldc, int M, mlg_lg_block_i w,
+                                                  bf16_t* __restrict__ xcopy, int ldc, int M, mlg_lg_block w,
                                                   mlg_lg_conf_i cf) {
     constexpr bool relu = LOFTR || RELU;
 #if MLG_FFN_TRACE
@@ -540,7 +540,7 @@ extern "C" int mlg_dbg_ffn_trace(void* host, size_t bytes) {
 #endif
 }
 
-int mlg_lg_ffn(const bf16_t* ctx, float* X, bf16_t* xcopy, int ldc, int M, const mlg_lg_block_i& w, hipStream_t s,
+int mlg_lg_ffn(const bf16_t* ctx, float* X, bf16_t* xcopy, int ldc, int M, const mlg_lg_block& w, hipStream_t s,
                const mlg_lg_conf_i* conf, int relu) {
     if (M <= 0) return MLG_OK;
     if (ldc < 256 || (ldc % 8) || relu < 0 || relu > 2) return MLG_EINVAL;

@@ -836,7 +836,7 @@ size_t mlg_lightglue_ws_bytes(int P, int kmax) {
     return lg_carve(P, kmax, nullptr, nullptr);
 }
 
-int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float* desc, const int32_t* counts, int kmax,
+int mlg_lightglue_run(const mlg_lg_weights& w, const float* kpts, const float* desc, const int32_t* counts, int kmax,
                       const int32_t* pa, const int32_t* pb, int P, float depth_conf, float width_conf,
                       float filter_thr, int pruning_min, void* ws, size_t ws_bytes, int32_t* matches, float* mscores,
                       int32_t* nmatch, int32_t* stop_layer, hipStream_t s) {
@@ -892,7 +892,7 @@ int mlg_lightglue_run(const mlg_lg_weights_i& w, const float* kpts, const float*
     // with rotary + head split fused in the GEMM epilogue, ragged attention, then out_proj +
     // FFN + residual fused (lg_ffn.hip).  x / cat / ef: the primary buffers, or the secondary
     // ones holding layer 0's frame layout; np rows; trace tags tag + 10 .. 15.
-    auto self_block = [&](const mlg_lg_block_i& bw, float* x, bf16_t* cat, const float4* ef, const int4* tasks,
+    auto self_block = [&](const mlg_lg_block& bw, float* x, bf16_t* cat, const float4* ef, const int4* tasks,
                           const int* outoff, int nt, int np, int mq, double tok, double work, int tag) -> int {
         {
             MlgProfScope prof(6, s, 2.0 * tok * 768 * 256);

@@ -42,6 +42,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "model_shapes.h"
 #include "pair_plan.h"
 #include "ws_carve.h"
 #include "../../include/mlgate.h"
@@ -914,17 +915,6 @@ __global__ __launch_bounds__(64) void k_lf_fine_match(const float* __restrict__ 
     }
 }
 
-struct ConvSpec {
-    int cin, cout, k, s;
-};
-// mlg_loftr_weights.conv_w order (include/mlgate.h); 196-channel stages padded to 256
-constexpr ConvSpec CONVS[MLG_LOFTR_NCONV] = {
-    {128, 128, 3, 1}, {128, 128, 3, 1}, {128, 128, 3, 1}, {128, 128, 3, 1},                    // layer1
-    {128, 256, 3, 2}, {256, 256, 3, 1}, {128, 256, 1, 2}, {256, 256, 3, 1}, {256, 256, 3, 1},  // layer2
-    {256, 256, 3, 2}, {256, 256, 3, 1}, {256, 256, 1, 2}, {256, 256, 3, 1}, {256, 256, 3, 1},  // layer3
-    {256, 256, 1, 1}, {256, 256, 1, 1}, {256, 256, 3, 1}, {256, 256, 3, 1},                    // FPN 1/4
-    {128, 256, 1, 1}, {256, 256, 3, 1}, {256, 128, 3, 1}};                                     // FPN 1/2
-
 struct FeatBufs {
     float* xf;     // residual stream f32 (up to 256 channels)
     bf16_t* xb;    // its bf16 copy
@@ -1168,7 +1158,7 @@ int encoder_layer(const mlg_loftr_layer& lw, const LayerBufs& b, int d, long x0,
     }
     MLG_LAUNCH_CHECK();
     if (tw) {  // d == 256: merge -> norm1 -> MLP -> norm2 -> residual, fused
-        mlg_lg_block_i bw{};
+        mlg_lg_block bw{};
         bw.Wout = tw->wmerge;
         bw.Wf1 = tw->w1;
         bw.Wf2 = tw->w2;

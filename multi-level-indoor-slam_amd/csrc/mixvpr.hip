@@ -113,7 +113,14 @@ __device__ __forceinline__ void mix_gemm(const bf16_t* __restrict__ W, int n0, c
 #undef MIX_STEP
 }
 
-__global__ __launch_bounds__(64 * MIX_NW, 1) void k_mix_head(const float* __restrict__ feat, mlg_mix_weights_i w,
+// the head's weights as the kernels receive them (by value); mlg_mixvpr_head fills it by
+// field name from mlg_mixvpr_weights, whose comments give the layouts
+struct MixHeadArgs {
+    const bf16_t* mix_w;
+    const float *mix_p, *row_w, *chan_w, *chan_b, *row_s, *row_b;
+};
+
+__global__ __launch_bounds__(64 * MIX_NW, 1) void k_mix_head(const float* __restrict__ feat, MixHeadArgs w,
                                                              float* __restrict__ P) {
     __shared__ __attribute__((aligned(16))) char lds[MIX_R * ROWB];
     __shared__ float red[2][MIX_NW][MIX_R];
@@ -311,7 +318,7 @@ __global__ __launch_bounds__(64 * MIX_NW, 1) void k_mix_head(const float* __rest
 
 // channel_proj on the row-projected features + F.normalize, one workgroup per image, in
 // place: desc[b] holds P [1024][4] on entry and the unit descriptor [4096] (o * 4 + r) on exit
-__global__ __launch_bounds__(1024) void k_mix_proj(float* __restrict__ desc, mlg_mix_weights_i w) {
+__global__ __launch_bounds__(1024) void k_mix_proj(float* __restrict__ desc, MixHeadArgs w) {
     __shared__ __attribute__((aligned(16))) float sP[4 * MIX_C];
     __shared__ __attribute__((aligned(16))) float sO[4 * MIX_C];
     __shared__ float sred[16];
@@ -371,7 +378,15 @@ int mlg_mixvpr_preprocess(const uint8_t* frames, int B, int H, int W, int C, lon
     return MLG_OK;
 }
 
-int mlg_mixvpr_head(const mlg_mix_weights_i& w, const float* feat, int B, float* desc, hipStream_t s) {
+int mlg_mixvpr_head(const mlg_mixvpr_weights& pw, const float* feat, int B, float* desc, hipStream_t s) {
+    MixHeadArgs w;
+    w.mix_w = pw.mix_w;
+    w.mix_p = pw.mix_p;
+    w.row_w = pw.row_w;
+    w.chan_w = pw.chan_w;
+    w.chan_b = pw.chan_b;
+    w.row_s = pw.row_s;
+    w.row_b = pw.row_b;
     if (!feat || !desc || B <= 0 || B > (1 << 20) || !w.mix_w || !w.mix_p || !w.row_w || !w.chan_w || !w.chan_b ||
         !w.row_s || !w.row_b)
         return MLG_EINVAL;

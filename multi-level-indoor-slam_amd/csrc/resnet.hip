@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "model_shapes.h"
 #include "ws_carve.h"
 
 namespace {
@@ -278,22 +279,21 @@ struct CoeffCache {
 // b.img (f32 NHWC [B, S, S, 3]); *xout: the f32 residual stream [B, side, side, C] it ends
 // with (inside the workspace).  b: a copy, its xb pair is swapped along the way.
 template <int S>
-static int rn_trunk(const mlg_rn_weights_i& w, int B, int nstages, RnBufs b, hipStream_t s, float** xout,
-                    int* side) {
+static int rn_trunk(const float* stem_w, const float* stem_b, const mlg_rn_block* blocks, int B, int nstages, RnBufs b,
+                    hipStream_t s, float** xout, int* side) {
     const long ns = (long)B * (S / 2) * (S / 2);
-    hipLaunchKernelGGL(k_rn_stem<S>, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, b.img, w.stem_w, w.stem_b,
-                       b.stem, B);
+    hipLaunchKernelGGL(k_rn_stem<S>, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, b.img, stem_w, stem_b, b.stem,
+                       B);
     const long np = (long)B * (S / 4) * (S / 4) * 64;
     hipLaunchKernelGGL(k_rn_maxpool<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, b.stem, b.xf[0], b.xb[0],
                        B);
     MLG_LAUNCH_CHECK();
 
     int cur = 0, Hc = S / 4, Cc = 64, blk = 0;
-    const int widths[4] = {64, 128, 256, 512}, nblocks[4] = {3, 4, 6, 3};
     for (int st = 0; st < nstages; ++st) {
-        const int width = widths[st], wpad = width < 128 ? 128 : width;
-        for (int bi = 0; bi < nblocks[st]; ++bi, ++blk) {
-            const mlg_rn_block_i& bw = w.blocks[blk];
+        const int width = RN_WIDTHS[st], wpad = width < 128 ? 128 : width;
+        for (int bi = 0; bi < RN_NBLOCKS[st]; ++bi, ++blk) {
+            const mlg_rn_block& bw = blocks[blk];
             const int stride = (st > 0 && bi == 0) ? 2 : 1;
             const int Ho = (Hc - 1) / stride + 1;
             const int M_in = B * Hc * Hc, M_out = B * Ho * Ho;
@@ -349,7 +349,7 @@ size_t mlg_resnet50_ws_bytes(int B, int H, int W) {
     return rn_carve(B, H, RN_S, nullptr, nullptr);
 }
 
-int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+int mlg_resnet50_run(const mlg_rn_weights& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                      int D, void* ws, size_t ws_bytes, float* desc, uint8_t* resized_u8, hipStream_t s) {
     if (B <= 0 || H <= 0 || W <= 0 || (C != 1 && C != 3 && C != 4) || D <= 0) return MLG_EINVAL;
     RnBufs b;
@@ -384,7 +384,7 @@ int mlg_resnet50_run(const mlg_rn_weights_i& w, const uint8_t* frames, int B, in
     }
     float* x = nullptr;
     int Hc = 0;
-    MLG_TRY(rn_trunk<RN_S>(w, B, 4, b, s, &x, &Hc));
+    MLG_TRY(rn_trunk<RN_S>(w.stem_w, w.stem_b, w.blocks, B, RN_STAGES, b, s, &x, &Hc));
     const long nd = (long)B * D;
     hipLaunchKernelGGL(k_rn_avgpool, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, x, B, Hc * Hc, D, desc);
     MLG_LAUNCH_CHECK();
@@ -402,11 +402,11 @@ float* mlg_resnet50_l3_image(void* ws, int B, int S) {
     return b.img;
 }
 
-int mlg_resnet50_l3_run(const mlg_rn_weights_i& w, int B, int S, void* ws, size_t ws_bytes, float** feat,
-                        hipStream_t s) {
+int mlg_resnet50_l3_run(const float* stem_w, const float* stem_b, const mlg_rn_block* blocks, int B, int S, void* ws,
+                        size_t ws_bytes, float** feat, hipStream_t s) {
     if (B <= 0 || S != 320 || !feat) return MLG_EINVAL;  // one instantiation per supported side
     RnBufs b;
     if (rn_carve(B, 0, S, ws, &b) > ws_bytes) return MLG_ENOMEM;
     int side = 0;
-    return rn_trunk<320>(w, B, 3, b, s, feat, &side);
+    return rn_trunk<320>(stem_w, stem_b, blocks, B, 3, b, s, feat, &side);
 }

@@ -339,7 +339,7 @@ size_t mlg_superglue_ws_bytes(int P, int kmax) {
     return sg_carve(P, kmax, nullptr, nullptr);
 }
 
-int mlg_superglue_run(const mlg_sg_weights_i& w, const float* kpts, const float* kscores, const float* desc,
+int mlg_superglue_run(const mlg_sg_weights& w, const float* kpts, const float* kscores, const float* desc,
                       const int32_t* counts, int kmax, int W, int H, const int32_t* pa, const int32_t* pb, int P,
                       int iters, float thr, void* ws, size_t ws_bytes, int32_t* matches, float* mscores,
                       int32_t* nmatch, hipStream_t s) {

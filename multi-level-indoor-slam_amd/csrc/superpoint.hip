@@ -20,6 +20,7 @@
 // descriptor sampling are small memory-bound kernels.
 #include "common.h"
 #include "kernels.h"
+#include "model_shapes.h"
 #include "ws_carve.h"
 
 namespace {
@@ -713,6 +714,23 @@ int conv(const bf16_t* in, const bf16_t* w, const float* b, bf16_t* out, int B, 
     return MLG_OK;
 }
 
+// Layer L of SP_LAYERS (model_shapes.h), whose shapes size mlg_sp_weights.w[L] and .b[L] in the
+// weight table too: a 3 x 3 conv with at most 128 output channels per workgroup ...
+template <int L, bool POOL>
+int conv_layer(const mlg_sp_weights& w, const bf16_t* in, bf16_t* out, int B, int H, int W, hipStream_t s) {
+    constexpr SpLayer l = SP_LAYERS[L];
+    static_assert(l.k == 3, "conv_layer is the 3 x 3 kernel");
+    return conv<l.cin, (l.cout < 128 ? l.cout : 128), POOL>(in, w.w[L], w.b[L], out, B, H, W, l.cout, s);
+}
+
+// ... or a 1 x 1 conv as a GEMM over the M cells (its bias is added by the consumer)
+template <int L>
+int gemm_layer(const mlg_sp_weights& w, const bf16_t* in, float* out, int M, hipStream_t s) {
+    constexpr SpLayer l = SP_LAYERS[L];
+    static_assert(l.k == 1, "gemm_layer is the 1 x 1 kernel");
+    return mlg_gemm_f32out(in, w.w[L], out, M, l.cout, l.cin, s);
+}
+
 struct SpBufs {
     bf16_t *A, *Bf;  // ping-pong activations, each the size of conv1a's output (the largest)
     float *logits, *dmap, *sc;
@@ -750,7 +768,7 @@ size_t mlg_superpoint_ws_bytes(int B, int H, int W) {
     return sp_carve(B, H, W, nullptr, nullptr);
 }
 
-int mlg_superpoint_run(const mlg_sp_weights_i& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+int mlg_superpoint_run(const mlg_sp_weights& w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
                        float det_thr, int max_kp, int nms_radius, int border, void* ws, size_t ws_bytes, float* kpts,
                        float* kscores, float* desc, uint16_t* desc_bf16, int32_t* count, hipStream_t s) {
     if (B <= 0 || H < 16 || W < 16 || (C != 1 && C != 3 && C != 4) || max_kp <= 0 ||
@@ -763,23 +781,23 @@ int mlg_superpoint_run(const mlg_sp_weights_i& w, const uint8_t* frames, int B, 
                        frame_stride, H, W, C, w.conv1a_w, w.conv1a_b, b.A);
     MLG_LAUNCH_CHECK();
     int h = H, wd = W;
-    MLG_TRY((conv<64, 64, true>(b.A, w.w[0], w.b[0], b.Bf, B, h, wd, 64, s)));   // conv1b + pool
+    MLG_TRY((conv_layer<0, true>(w, b.A, b.Bf, B, h, wd, s)));   // conv1b + pool
     h /= 2; wd /= 2;
-    MLG_TRY((conv<64, 64, false>(b.Bf, w.w[1], w.b[1], b.A, B, h, wd, 64, s)));  // conv2a
-    MLG_TRY((conv<64, 64, true>(b.A, w.w[2], w.b[2], b.Bf, B, h, wd, 64, s)));   // conv2b + pool
+    MLG_TRY((conv_layer<1, false>(w, b.Bf, b.A, B, h, wd, s)));  // conv2a
+    MLG_TRY((conv_layer<2, true>(w, b.A, b.Bf, B, h, wd, s)));   // conv2b + pool
     h /= 2; wd /= 2;
-    MLG_TRY((conv<64, 128, false>(b.Bf, w.w[3], w.b[3], b.A, B, h, wd, 128, s)));   // conv3a
-    MLG_TRY((conv<128, 128, true>(b.A, w.w[4], w.b[4], b.Bf, B, h, wd, 128, s)));   // conv3b + pool
+    MLG_TRY((conv_layer<3, false>(w, b.Bf, b.A, B, h, wd, s)));  // conv3a
+    MLG_TRY((conv_layer<4, true>(w, b.A, b.Bf, B, h, wd, s)));   // conv3b + pool
     h /= 2; wd /= 2;
-    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[5], w.b[5], b.A, B, h, wd, 128, s)));  // conv4a
-    MLG_TRY((conv<128, 128, false>(b.A, w.w[6], w.b[6], b.Bf, B, h, wd, 128, s)));  // conv4b -> x (b.Bf)
+    MLG_TRY((conv_layer<5, false>(w, b.Bf, b.A, B, h, wd, s)));  // conv4a
+    MLG_TRY((conv_layer<6, false>(w, b.A, b.Bf, B, h, wd, s)));  // conv4b -> x (b.Bf)
     const int M = B * h * wd;
     bf16_t* cPa = b.A;
-    bf16_t* cDa = b.A + (size_t)M * 256;
-    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[7], w.b[7], cPa, B, h, wd, 256, s)));  // convPa
-    MLG_TRY((conv<128, 128, false>(b.Bf, w.w[9], w.b[9], cDa, B, h, wd, 256, s)));  // convDa
-    MLG_TRY(mlg_gemm_f32out(cPa, w.w[8], b.logits, M, 128, 256, s));                // convPb (65 of 128 rows)
-    MLG_TRY(mlg_gemm_f32out(cDa, w.w[10], b.dmap, M, 256, 256, s));                 // convDb
+    bf16_t* cDa = b.A + (size_t)M * SP_LAYERS[7].cout;
+    MLG_TRY((conv_layer<7, false>(w, b.Bf, cPa, B, h, wd, s)));  // convPa
+    MLG_TRY((conv_layer<9, false>(w, b.Bf, cDa, B, h, wd, s)));  // convDa
+    MLG_TRY((gemm_layer<8>(w, cPa, b.logits, M, s)));            // convPb (65 of 128 rows)
+    MLG_TRY((gemm_layer<10>(w, cDa, b.dmap, M, s)));             // convDb
     hipLaunchKernelGGL(k_sp_scores, dim3((M + 255) / 256), dim3(256), 0, s, b.logits, 128, w.b[8], B, h, wd, b.sc);
     MLG_LAUNCH_CHECK();
     // the score map is 8 * floor(H / 8) x 8 * floor(W / 8): the encoder convolved the

@@ -9,7 +9,8 @@
 // so the ops compose with torch streams, events and hipGraph capture (the ABI itself
 // never allocates or synchronises; LightGlue and the proximity emit read one small
 // device result back by design -- see the header).  Weights arrive as flat tensor
-// lists in the order of the ABI's weight structs (mlgate/*.py build them once).
+// lists (mlgate/*.py build them once); weight_tables.h holds each list's order and checks
+// every tensor of it before anything is launched.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "../../include/mlgate.h"
+#include "weight_tables.h"
 
 namespace {
 
@@ -61,43 +63,34 @@ Tensor workspace(size_t bytes, const Tensor& like) {
     return t;
 }
 
-// ------------------------------------------------------------------ ViT-B/14
-constexpr int kVitBlockTensors = 14;
-constexpr int kVitTensors = 4 + MLG_VIT_DEPTH * kVitBlockTensors + 2;
+// ------------------------------------------------------------ weight lists
+// Fill the pointer fields of *strukt from the list through its table (weight_tables.h).
+// dev: the device the op launches on (the list must live there); none: any one device.
+void fill_weights(const wt::Table& table, const char* model, at::TensorList w, void* strukt,
+                  c10::optional<c10::Device> dev) {
+    std::vector<wt::Desc> d;
+    d.reserve(w.size());
+    for (const Tensor& t : w) {
+        TORCH_CHECK(t.defined(), model, " weights: undefined tensor");
+        const at::ScalarType ty = t.scalar_type();
+        const wt::Kind kind = ty == at::kBFloat16 ? wt::BF16
+                              : ty == at::kFloat  ? wt::F32
+                              : ty == at::kByte   ? wt::U8
+                                                  : wt::OTHER;
+        d.push_back({t.numel() ? t.data_ptr() : nullptr, kind, t.numel(),
+                     t.device().is_cpu() ? -1 : (int)t.device().index(), t.is_contiguous()});
+    }
+    const std::string err = wt::fill(table, model, d.data(), d.size(), strukt);
+    TORCH_CHECK(err.empty(), err);
+    TORCH_CHECK(!dev.has_value() || (!w.empty() && w[0].device() == *dev), model, " weights must be on ", *dev);
+}
 
+// ------------------------------------------------------------------ ViT-B/14
 // split: weights packed for MLG_VIT_SPLIT ([W_hi | W_lo], 2x the reduction dim)
-mlg_vit_weights vit_weights(const std::vector<Tensor>& w, bool split = false) {
-    TORCH_CHECK((int)w.size() == kVitTensors, "vit weights: expected ", kVitTensors, " tensors, got ", w.size());
-    const int64_t m = split ? 2 : 1;
-    auto want_n = [&](const Tensor& t, int64_t n, const char* what) {
-        TORCH_CHECK(t.numel() == n * m && t.scalar_type() == at::kBFloat16, "vit weights: ", what, " must be bf16 with ",
-                    n * m, " elements", split ? " (split packing)" : "");
-    };
-    want_n(w[0], 768LL * MLG_VIT_PATCH_K, "patch_w");
-    for (int i = 0; i < MLG_VIT_DEPTH; ++i) {
-        const Tensor* b = &w[4 + i * kVitBlockTensors];
-        want_n(b[2], 2304LL * 768, "qkv_w");
-        want_n(b[4], 768LL * 768, "proj_w");
-        want_n(b[9], 3072LL * 768, "fc1_w");
-        want_n(b[11], 768LL * 3072, "fc2_w");
-    }
+mlg_vit_weights vit_weights(at::TensorList w, bool split, int64_t image_size, c10::Device dev) {
     mlg_vit_weights s = MLG_STRUCT_INIT(mlg_vit_weights);
-    s.patch_w = cp<uint16_t>(w[0]);
-    s.patch_b = cp<float>(w[1]);
-    s.cls = cp<float>(w[2]);
-    s.pos = cp<float>(w[3]);
-    for (int i = 0; i < MLG_VIT_DEPTH; ++i) {
-        const Tensor* b = &w[4 + i * kVitBlockTensors];
-        mlg_vit_block& o = s.blocks[i];
-        o.norm1_w = cp<float>(b[0]); o.norm1_b = cp<float>(b[1]);
-        o.qkv_w = cp<uint16_t>(b[2]); o.qkv_b = cp<float>(b[3]);
-        o.proj_w = cp<uint16_t>(b[4]); o.proj_b = cp<float>(b[5]); o.ls1 = cp<float>(b[6]);
-        o.norm2_w = cp<float>(b[7]); o.norm2_b = cp<float>(b[8]);
-        o.fc1_w = cp<uint16_t>(b[9]); o.fc1_b = cp<float>(b[10]);
-        o.fc2_w = cp<uint16_t>(b[11]); o.fc2_b = cp<float>(b[12]); o.ls2 = cp<float>(b[13]);
-    }
-    s.norm_w = cp<float>(w[kVitTensors - 2]);
-    s.norm_b = cp<float>(w[kVitTensors - 1]);
+    const int64_t grid = image_size / 14;
+    fill_weights(wt::vit_table(split, 1 + grid * grid), "vit", w, &s, dev);
     s.packing = split ? MLG_VIT_SPLIT : 0;
     return s;
 }
@@ -117,8 +110,7 @@ void vit_forward_into(const Tensor& frames, at::TensorList w, int64_t image_size
                         local->size(2) == MLG_VIT_EMBED, "local must be [B, (S/14)^2 - 1, 768]");
     }
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
-    std::vector<Tensor> wv(w.begin(), w.end());
-    const mlg_vit_weights s = vit_weights(wv, (flags & MLG_VIT_SPLIT) != 0);
+    const mlg_vit_weights s = vit_weights(w, (flags & MLG_VIT_SPLIT) != 0, image_size, frames.device());
     c10::DeviceGuard g(frames.device());
     const int64_t nb_max = std::min(B, max_batch);
     Tensor ws = workspace(mlg_vit_workspace_bytes((int)nb_max, (int)image_size), frames);
@@ -134,28 +126,16 @@ void vit_forward_into(const Tensor& frames, at::TensorList w, int64_t image_size
     }
 }
 
-// SALAD: frames uint8 [B, H, W, C] -> desc f32 [B, 8448]; salad = [w1, b1, w2, b2, wt1, bt1, wt2, bt2]
+// SALAD: frames uint8 [B, H, W, C] -> desc f32 [B, 8448]
 Tensor salad_forward(const Tensor& frames, at::TensorList w, at::TensorList salad, double dust_bin,
                      int64_t image_size, int64_t max_batch) {
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    TORCH_CHECK(salad.size() == 8, "salad weights: expected 8 tensors");
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
-    std::vector<Tensor> wv(w.begin(), w.end());
-    const mlg_vit_weights s = vit_weights(wv);
-    const at::ScalarType kinds[8] = {at::kBFloat16, at::kFloat, at::kBFloat16, at::kFloat,
-                                     at::kFloat,    at::kFloat, at::kFloat,    at::kFloat};
-    const int64_t numel[8] = {1024 * 768, 1024, 256 * 1024, 256, 512 * 768, 512, 256 * 512, 256};
-    for (int i = 0; i < 8; ++i) {
-        want(salad[i], kinds[i], "salad weight");
-        TORCH_CHECK(salad[i].numel() == numel[i], "salad weight ", i, ": expected ", numel[i], " elements");
-    }
+    const mlg_vit_weights s = vit_weights(w, false, image_size, frames.device());
     mlg_salad_weights sw = MLG_STRUCT_INIT(mlg_salad_weights);
-    sw.w1 = cp<uint16_t>(salad[0]); sw.b1 = cp<float>(salad[1]);
-    sw.w2 = cp<uint16_t>(salad[2]); sw.b2 = cp<float>(salad[3]);
-    sw.wt1 = cp<float>(salad[4]); sw.bt1 = cp<float>(salad[5]);
-    sw.wt2 = cp<float>(salad[6]); sw.bt2 = cp<float>(salad[7]);
+    fill_weights(wt::salad_table(), "salad", salad, &sw, frames.device());
     sw.dust_bin = (float)dust_bin;
     c10::DeviceGuard g(frames.device());
     Tensor desc = at::empty({B, MLG_SALAD_DIM}, frames.options().dtype(at::kFloat));
@@ -267,14 +247,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> superpoint(const Tensor& fram
                                                                int64_t border, bool with_bf16) {
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    TORCH_CHECK(w.size() == 24, "superpoint weights: expected 24 tensors");
     mlg_sp_weights s = MLG_STRUCT_INIT(mlg_sp_weights);
-    s.conv1a_w = cp<float>(w[0]);
-    s.conv1a_b = cp<float>(w[1]);
-    for (int i = 0; i < 11; ++i) {
-        s.w[i] = cp<uint16_t>(w[2 + i]);
-        s.b[i] = cp<float>(w[13 + i]);
-    }
+    fill_weights(wt::sp_table(), "superpoint", w, &s, frames.device());
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const size_t nbytes = mlg_superpoint_workspace_bytes((int)B, (int)H, (int)W);
     TORCH_CHECK(nbytes > 0, "SuperPoint needs H, W >= 16 (got ", H, "x", W, ")");
@@ -294,43 +268,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> superpoint(const Tensor& fram
 }
 
 // ------------------------------------------------------------------ LoFTR
-// weights: stem_w, stem_b, conv_w[21], conv_b[21] (empty = none), 8 coarse + 2 fine
-// layers x (w, wmerge, w1, w2, ln1_g, ln1_b, ln2_g, ln2_b), down_w, down_b, merge_wf,
-// merge_wc, merge_b (mlgate/loftr.py builds the list), optionally followed by the packed
-// coarse tails (uint8 [mlg_loftr_tails_bytes()], loftr_pack_tails)
-constexpr int kLoftrTensors = 2 + 2 * MLG_LOFTR_NCONV + 10 * 8 + 5;
+// the list with or without the packed coarse tails (loftr_pack_tails) at its end
+constexpr size_t kLoftrTensors = 2 + 2 * MLG_LOFTR_NCONV + 10 * 8 + 5;
 
-mlg_loftr_weights loftr_weights(at::TensorList w) {
-    TORCH_CHECK((int)w.size() == kLoftrTensors || (int)w.size() == kLoftrTensors + 1, "loftr weights: expected ",
-                kLoftrTensors, " (+ 1 packed tails) tensors, got ", w.size());
+mlg_loftr_weights loftr_weights(at::TensorList w, c10::optional<c10::Device> dev) {
     mlg_loftr_weights s = MLG_STRUCT_INIT(mlg_loftr_weights);
-    int i = 0;
-    s.stem_w = cp<float>(w[i++]);
-    s.stem_b = cp<float>(w[i++]);
-    for (int c = 0; c < MLG_LOFTR_NCONV; ++c) s.conv_w[c] = cp<uint16_t>(w[i++]);
-    for (int c = 0; c < MLG_LOFTR_NCONV; ++c) s.conv_b[c] = cp<float>(w[i++]);
-    for (int l = 0; l < 10; ++l) {
-        mlg_loftr_layer& L = l < 8 ? s.coarse[l] : s.fine[l - 8];
-        L.w = cp<uint16_t>(w[i++]);
-        L.wmerge = cp<uint16_t>(w[i++]);
-        L.w1 = cp<uint16_t>(w[i++]);
-        L.w2 = cp<uint16_t>(w[i++]);
-        L.ln1_g = cp<float>(w[i++]);
-        L.ln1_b = cp<float>(w[i++]);
-        L.ln2_g = cp<float>(w[i++]);
-        L.ln2_b = cp<float>(w[i++]);
-    }
-    s.down_w = cp<uint16_t>(w[i++]);
-    s.down_b = cp<float>(w[i++]);
-    s.merge_wf = cp<uint16_t>(w[i++]);
-    s.merge_wc = cp<uint16_t>(w[i++]);
-    s.merge_b = cp<float>(w[i++]);
-    if ((int)w.size() > kLoftrTensors) {
-        const Tensor& t = w[i];
-        TORCH_CHECK(t.scalar_type() == at::kByte && (size_t)t.numel() == mlg_loftr_tails_bytes() && t.is_contiguous(),
-                    "loftr packed tails must be uint8 [", mlg_loftr_tails_bytes(), "] (loftr_pack_tails)");
-        s.coarse_tails = t.data_ptr();
-    }
+    const int64_t tails = w.size() > kLoftrTensors ? (int64_t)mlg_loftr_tails_bytes() : 0;
+    fill_weights(wt::loftr_table(tails), "loftr", w, &s, dev);
     return s;
 }
 
@@ -341,7 +285,7 @@ void loftr_coarse_layer(const Tensor& x, const Tensor& cat, at::TensorList w, in
     want(cat, at::kBFloat16, "cat");
     TORCH_CHECK(x.numel() == 2 * nseg * L * 256 && cat.numel() == 2 * nseg * L * 512,
                 "x must be [2 nseg L, 256], cat [2 nseg L, 512]");
-    const mlg_loftr_weights s = loftr_weights(w);
+    const mlg_loftr_weights s = loftr_weights(w, x.device());
     c10::DeviceGuard g(x.device());
     Tensor ws = workspace(mlg_op_loftr_coarse_layer_ws_bytes((int)nseg, (int)L), x);
     check_rc(mlg_op_loftr_coarse_layer(&s, (int)layer, (int)fused, mp<float>(x), mp<uint16_t>(cat), (int)nseg, (int)L,
@@ -351,8 +295,9 @@ void loftr_coarse_layer(const Tensor& x, const Tensor& cat, at::TensorList w, in
 
 // the coarse block-tail weights packed once for the fused kernel (mlg_loftr_pack_tails)
 Tensor loftr_pack_tails(at::TensorList w) {
-    TORCH_CHECK((int)w.size() == kLoftrTensors, "loftr weights: expected ", kLoftrTensors, " tensors");
-    const mlg_loftr_weights s = loftr_weights(w);
+    TORCH_CHECK(w.size() == kLoftrTensors, "loftr weights: expected ", kLoftrTensors, " tensors, got ", w.size());
+    TORCH_CHECK(w[0].is_cuda(), "loftr weights must be on the HIP device");
+    const mlg_loftr_weights s = loftr_weights(w, w[0].device());
     c10::DeviceGuard g(w[0].device());
     Tensor out = at::empty({(int64_t)mlg_loftr_tails_bytes()}, w[0].options().dtype(at::kByte));
     check_rc(mlg_loftr_pack_tails(&s, out.data_ptr(), stream_of(w[0])), "mlg_loftr_pack_tails");
@@ -362,7 +307,7 @@ Tensor loftr_pack_tails(at::TensorList w) {
 std::tuple<Tensor, Tensor> loftr_features(const Tensor& frames, at::TensorList w) {
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    const mlg_loftr_weights s = loftr_weights(w);
+    const mlg_loftr_weights s = loftr_weights(w, frames.device());
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const size_t nbytes = mlg_loftr_features_ws_bytes((int)B, (int)H, (int)W);
     TORCH_CHECK(nbytes > 0, "LoFTR needs H, W >= 32 (got ", H, "x", W, ")");
@@ -396,7 +341,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> loftr_match(const Tensor& coarse, con
     const int32_t* b = pb.data_ptr<int32_t>();
     for (int64_t p = 0; p < P; ++p)
         TORCH_CHECK(a[p] >= 0 && a[p] < F && b[p] >= 0 && b[p] < F, "pair ", p, " indexes a missing frame");
-    const mlg_loftr_weights s = loftr_weights(w);
+    const mlg_loftr_weights s = loftr_weights(w, coarse.device());
     const size_t nbytes = mlg_loftr_match_ws_bytes((int)P, (int)H, (int)W);
     TORCH_CHECK(nbytes > 0, "LoFTR needs H, W >= 32 and multiples of 8");
     c10::DeviceGuard g(coarse.device());
@@ -412,10 +357,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> loftr_match(const Tensor& coarse, con
 }
 
 // --------------------------------------------------------------- SuperGlue
-// weights: kenc_w[0..2], kenc_b[0..2], kenc_w4, kenc_b4, kenc_w5, kenc_b5, 18 layers x
-// (Wqkv, bqkv, Wout, bout, Wf1, bf1, Wf2, bf2), Wfinal, bfinal; bin_score as a double
-constexpr int kSgTensors = 6 + 4 + 18 * 8 + 2;
-
+// bin_score arrives as a double beside the list
 std::tuple<Tensor, Tensor, Tensor> superglue(const Tensor& kpts, const Tensor& scores, const Tensor& desc,
                                              const Tensor& counts, const Tensor& pair_a, const Tensor& pair_b,
                                              at::TensorList w, double bin_score, int64_t W, int64_t H, int64_t iters,
@@ -426,7 +368,6 @@ std::tuple<Tensor, Tensor, Tensor> superglue(const Tensor& kpts, const Tensor& s
     want(counts, at::kInt, "counts", false);
     want(pair_a, at::kInt, "pair_a", false);
     want(pair_b, at::kInt, "pair_b", false);
-    TORCH_CHECK((int)w.size() == kSgTensors, "superglue weights: expected ", kSgTensors, " tensors");
     const int64_t F = kpts.size(0), kmax = kpts.size(1), P = pair_a.numel();
     TORCH_CHECK(kpts.dim() == 3 && kpts.size(2) == 2 && desc.dim() == 3 && desc.size(0) == F &&
                     desc.size(1) == kmax && desc.size(2) == 256 && scores.numel() == F * kmax,
@@ -435,22 +376,7 @@ std::tuple<Tensor, Tensor, Tensor> superglue(const Tensor& kpts, const Tensor& s
     const int32_t* cn = cp<int32_t>(counts);
     for (int64_t f = 0; f < F; ++f) TORCH_CHECK(cn[f] >= 0 && cn[f] <= kmax, "counts out of range");
     mlg_sg_weights s = MLG_STRUCT_INIT(mlg_sg_weights);
-    int i = 0;
-    for (int l = 0; l < 3; ++l) s.kenc_w[l] = cp<float>(w[i++]);
-    for (int l = 0; l < 3; ++l) s.kenc_b[l] = cp<float>(w[i++]);
-    s.kenc_w4 = cp<uint16_t>(w[i++]);
-    s.kenc_b4 = cp<float>(w[i++]);
-    s.kenc_w5 = cp<uint16_t>(w[i++]);
-    s.kenc_b5 = cp<float>(w[i++]);
-    for (int l = 0; l < 18; ++l) {
-        mlg_lg_block& b = s.layer[l];
-        b.Wqkv = cp<uint16_t>(w[i++]); b.bqkv = cp<float>(w[i++]);
-        b.Wout = cp<uint16_t>(w[i++]); b.bout = cp<float>(w[i++]);
-        b.Wf1 = cp<uint16_t>(w[i++]); b.bf1 = cp<float>(w[i++]);
-        b.Wf2 = cp<uint16_t>(w[i++]); b.bf2 = cp<float>(w[i++]);
-    }
-    s.Wfinal = cp<uint16_t>(w[i++]);
-    s.bfinal = cp<float>(w[i++]);
+    fill_weights(wt::sg_table(), "superglue", w, &s, kpts.device());
     s.bin_score = (float)bin_score;
     const size_t nbytes = mlg_superglue_workspace_bytes((int)P, (int)kmax);
     c10::DeviceGuard g(kpts.device());
@@ -485,8 +411,6 @@ Tensor xcorr_batch(const Tensor& feats, const Tensor& query, const Tensor& cand)
 }
 
 // --------------------------------------------------------------- LightGlue
-constexpr int kLgTensors = 1 + 9 * 10 * 2 + 9 * 4 + 8 * 2 + 1;
-
 std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const Tensor& desc, const Tensor& counts,
                                                      const Tensor& pair_a, const Tensor& pair_b, at::TensorList w,
                                                      double depth_conf, double width_conf, double filter_thr,
@@ -496,7 +420,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const T
     want(counts, at::kInt, "counts", false);
     want(pair_a, at::kInt, "pair_a", false);
     want(pair_b, at::kInt, "pair_b", false);
-    TORCH_CHECK((int)w.size() == kLgTensors, "lightglue weights: expected ", kLgTensors, " tensors");
     const int64_t F = kpts.size(0), kmax = kpts.size(1), P = pair_a.numel();
     TORCH_CHECK(kpts.dim() == 3 && kpts.size(2) == 2 && desc.dim() == 3 && desc.size(0) == F &&
                     desc.size(1) == kmax && desc.size(2) == 256, "kpts [F, kmax, 2] / desc [F, kmax, 256]");
@@ -508,24 +431,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const T
         TORCH_CHECK(pa[p] >= 0 && pa[p] < F && pb[p] >= 0 && pb[p] < F, "pair frame index out of range");
     for (int64_t f = 0; f < F; ++f) TORCH_CHECK(cn[f] >= 0 && cn[f] <= kmax, "counts out of range");
     mlg_lg_weights s = MLG_STRUCT_INIT(mlg_lg_weights);
-    int i = 0;
-    s.Wr = cp<float>(w[i++]);
-    for (mlg_lg_block* blocks : {s.self, s.cross})
-        for (int l = 0; l < 9; ++l) {
-            mlg_lg_block& b = blocks[l];
-            b.Wqkv = cp<uint16_t>(w[i++]); b.bqkv = cp<float>(w[i++]);
-            b.Wout = cp<uint16_t>(w[i++]); b.bout = cp<float>(w[i++]);
-            b.Wf1 = cp<uint16_t>(w[i++]); b.bf1 = cp<float>(w[i++]);
-            b.ln_g = cp<float>(w[i++]); b.ln_b = cp<float>(w[i++]);
-            b.Wf2 = cp<uint16_t>(w[i++]); b.bf2 = cp<float>(w[i++]);
-        }
-    for (int l = 0; l < 9; ++l) s.Wfinal[l] = cp<uint16_t>(w[i++]);
-    for (int l = 0; l < 9; ++l) s.bfinal[l] = cp<float>(w[i++]);
-    for (int l = 0; l < 9; ++l) s.wmatch[l] = cp<float>(w[i++]);
-    for (int l = 0; l < 9; ++l) s.bmatch[l] = cp<float>(w[i++]);
-    for (int l = 0; l < 8; ++l) s.wconf[l] = cp<float>(w[i++]);
-    for (int l = 0; l < 8; ++l) s.bconf[l] = cp<float>(w[i++]);
-    s.ones = cp<float>(w[i++]);
+    fill_weights(wt::lg_table(), "lightglue", w, &s, kpts.device());
     const size_t nbytes = mlg_lightglue_workspace_bytes((int)P, (int)kmax);
     TORCH_CHECK(nbytes > 0, "LightGlue supports up to 2048 keypoints per image (got ", kmax, ")");
     c10::DeviceGuard g(kpts.device());
@@ -616,18 +522,8 @@ Tensor recover_pose(const Tensor& k1, const Tensor& k2, const Tensor& offs, cons
 Tensor resnet50(const Tensor& frames, at::TensorList w, int64_t descriptor_dim) {
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    TORCH_CHECK(w.size() == 2 + 16 * 8, "resnet50 weights: expected 130 tensors");
     mlg_rn_weights s = MLG_STRUCT_INIT(mlg_rn_weights);
-    s.stem_w = cp<float>(w[0]);
-    s.stem_b = cp<float>(w[1]);
-    for (int b = 0; b < 16; ++b) {
-        const Tensor* t = &w[2 + 8 * b];
-        mlg_rn_block& o = s.blocks[b];
-        o.w1 = cp<uint16_t>(t[0]); o.b1 = cp<float>(t[1]);
-        o.w2 = cp<uint16_t>(t[2]); o.b2 = cp<float>(t[3]);
-        o.w3 = cp<uint16_t>(t[4]); o.b3 = cp<float>(t[5]);
-        o.wd = cp<uint16_t>(t[6]); o.bd = cp<float>(t[7]);
-    }
+    fill_weights(wt::rn_table(), "resnet50", w, &s, frames.device());
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     c10::DeviceGuard g(frames.device());
     Tensor out = at::empty({B, descriptor_dim}, frames.options().dtype(at::kFloat));
@@ -652,41 +548,14 @@ Tensor pillow_resize_224(const Tensor& frames) {
 }
 
 // ------------------------------------------------------------------ MixVPR
-// head = [mix_w bf16, mix_p, row_w, chan_w, chan_b, row_s, row_b] (mlgate/mixvpr.py pack_head)
-void mixvpr_head_weights(at::TensorList head, mlg_mixvpr_weights& s) {
-    TORCH_CHECK(head.size() == 7, "mixvpr head weights: expected 7 tensors");
-    const int64_t numel[7] = {4LL * 2 * 26 * 416 * 16, 4 * 4 * 512, 4 * 512, 1024 * 1024, 1024, 4, 4};
-    for (int i = 0; i < 7; ++i) {
-        want(head[i], i == 0 ? at::kBFloat16 : at::kFloat, "mixvpr head weight");
-        TORCH_CHECK(head[i].numel() == numel[i], "mixvpr head weight ", i, ": expected ", numel[i], " elements");
-    }
-    s.mix_w = cp<uint16_t>(head[0]);
-    s.mix_p = cp<float>(head[1]);
-    s.row_w = cp<float>(head[2]);
-    s.chan_w = cp<float>(head[3]);
-    s.chan_b = cp<float>(head[4]);
-    s.row_s = cp<float>(head[5]);
-    s.row_b = cp<float>(head[6]);
-}
-
-// frames uint8 [B, H, W, C] -> desc f32 [B, 4096]; trunk = [stem_w, stem_b] + 13 x mlg_rn_block
+// frames uint8 [B, H, W, C] -> desc f32 [B, 4096]
 Tensor mixvpr_forward(const Tensor& frames, at::TensorList trunk, at::TensorList head, int64_t max_batch) {
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    TORCH_CHECK(trunk.size() == 2 + 13 * 8, "mixvpr trunk weights: expected 106 tensors");
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
     mlg_mixvpr_weights s = MLG_STRUCT_INIT(mlg_mixvpr_weights);
-    s.stem_w = cp<float>(trunk[0]);
-    s.stem_b = cp<float>(trunk[1]);
-    for (int b = 0; b < 13; ++b) {
-        const Tensor* t = &trunk[2 + 8 * b];
-        mlg_rn_block& o = s.blocks[b];
-        o.w1 = cp<uint16_t>(t[0]); o.b1 = cp<float>(t[1]);
-        o.w2 = cp<uint16_t>(t[2]); o.b2 = cp<float>(t[3]);
-        o.w3 = cp<uint16_t>(t[4]); o.b3 = cp<float>(t[5]);
-        o.wd = cp<uint16_t>(t[6]); o.bd = cp<float>(t[7]);
-    }
-    mixvpr_head_weights(head, s);
+    fill_weights(wt::mixvpr_trunk_table(), "mixvpr trunk", trunk, &s, frames.device());
+    fill_weights(wt::mixvpr_head_table(), "mixvpr head", head, &s, frames.device());
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     c10::DeviceGuard g(frames.device());
     Tensor desc = at::empty({B, MLG_MIXVPR_DIM}, frames.options().dtype(at::kFloat));
@@ -708,7 +577,7 @@ Tensor mixvpr_head(const Tensor& feat, at::TensorList head) {
     want(feat, at::kFloat, "features");
     TORCH_CHECK(feat.dim() == 3 && feat.size(1) == 400 && feat.size(2) == 1024, "features must be [B, 400, 1024]");
     mlg_mixvpr_weights s = MLG_STRUCT_INIT(mlg_mixvpr_weights);
-    mixvpr_head_weights(head, s);
+    fill_weights(wt::mixvpr_head_table(), "mixvpr head", head, &s, feat.device());
     c10::DeviceGuard g(feat.device());
     Tensor desc = at::empty({feat.size(0), MLG_MIXVPR_DIM}, feat.options());
     check_rc(mlg_op_mixvpr_head(&s, cp<float>(feat), (int)feat.size(0), mp<float>(desc), stream_of(feat)),
@@ -768,8 +637,7 @@ Tensor anyloc_forward(const Tensor& frames, at::TensorList w, const Tensor& cent
     want(frames, at::kByte, "frames");
     TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
-    std::vector<Tensor> wv(w.begin(), w.end());
-    const mlg_vit_weights s = vit_weights(wv, (flags & MLG_VIT_SPLIT) != 0);
+    const mlg_vit_weights s = vit_weights(w, (flags & MLG_VIT_SPLIT) != 0, image_size, frames.device());
     const mlg_vlad_vocab v = vlad_vocab(centers);
     TORCH_CHECK(centers.device() == frames.device(), "centers and frames must be on one device");
     const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
@@ -865,6 +733,40 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> proximity(const Tensor& pos, const c1
                                     mp<double>(dist), mp<uint8_t>(valid), stream_of(pos)),
                  "mlg_proximity_emit");
     return {pairs, dist, valid, totals};
+}
+
+// The checks every weighted op applies to its list, on any one device (host included): lets
+// a machine without a GPU compare the Python packers with the tables.  "vit" / "vit_split"
+// take the token count from the list's own `pos` (the ops take it from image_size).
+void weights_check(std::string model, at::TensorList w) {
+    union {
+        mlg_vit_weights vit;
+        mlg_salad_weights salad;
+        mlg_sp_weights sp;
+        mlg_lg_weights lg;
+        mlg_sg_weights sg;
+        mlg_rn_weights rn;
+        mlg_mixvpr_weights mix;
+    } s;  // scratch: only the checks matter
+    const c10::optional<c10::Device> any;
+    const struct {
+        const char *model, *what;
+        const wt::Table& (*table)();
+    } fixed[] = {{"salad", "salad", wt::salad_table},
+                 {"superpoint", "superpoint", wt::sp_table},
+                 {"lightglue", "lightglue", wt::lg_table},
+                 {"superglue", "superglue", wt::sg_table},
+                 {"resnet50", "resnet50", wt::rn_table},
+                 {"mixvpr_trunk", "mixvpr trunk", wt::mixvpr_trunk_table},
+                 {"mixvpr_head", "mixvpr head", wt::mixvpr_head_table}};
+    for (const auto& f : fixed)
+        if (model == f.model) return fill_weights(f.table(), f.what, w, &s, any);
+    if (model == "vit" || model == "vit_split") {
+        const int64_t tokens = w.size() > 3 && w[3].defined() ? w[3].numel() / MLG_VIT_EMBED : 0;
+        return fill_weights(wt::vit_table(model == "vit_split", tokens), "vit", w, &s, any);
+    }
+    TORCH_CHECK(model == "loftr", "weights_check: unknown model '", model, "'");
+    loftr_weights(w, any);
 }
 
 // ------------------------------------------------------------- profiling
@@ -1114,6 +1016,7 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("jpeg_info(Tensor blob) -> Tensor");
     m.def("jpeg_coef_bytes(int H, int W) -> int");
     m.def("jpeg_pixels(Tensor coefs, Tensor qtabs, Tensor params, int H, int W) -> Tensor");
+    m.def("weights_check(str model, Tensor[] weights) -> ()");
     m.def("prof_enable(int mask) -> int");
     m.def("prof_reset() -> int");
     m.def("prof_read(int slot) -> (float, int, float)");
@@ -1151,6 +1054,7 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("lg_orient", &lg_orient);
     m.impl("orb_detect", &orb_detect);
     m.impl("orb_match", &orb_match);
+    m.impl("weights_check", &weights_check);  // device lists; host lists take the composite kernel below
 }
 
 TORCH_LIBRARY_IMPL(mlgate, CPU, m) {
@@ -1162,6 +1066,7 @@ TORCH_LIBRARY_IMPL(mlgate, CPU, m) {
 }
 
 TORCH_LIBRARY_IMPL(mlgate, CompositeExplicitAutograd, m) {
+    m.impl("weights_check", &weights_check);
     m.impl("prof_enable", &prof_enable);
     m.impl("jpeg_coef_bytes", &jpeg_coef_bytes);
     m.impl("prof_reset", &prof_reset);

@@ -20,7 +20,7 @@ OPS = ("vit_forward_into", "salad_forward", "knn_gate", "knn_query", "row_normal
        "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
        "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess", "vlad", "anyloc_forward", "kmeans_step",
-       "prof_enable", "prof_reset", "prof_read")
+       "weights_check", "prof_enable", "prof_reset", "prof_read")
 
 
 c_int, c_long, c_size_t, c_float, c_double, c_void_p = (

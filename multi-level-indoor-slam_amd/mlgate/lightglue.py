@@ -39,6 +39,52 @@ def pack_rotary(ecos, esin):
     return cs.reshape(n // 64, 64, 16, 4).permute(0, 2, 1, 3).contiguous()
 
 
+def pack_weights(sd, device):
+    """The torch.ops.mlgate.lightglue weight list on ``device``: Wr; the self then the cross
+    blocks (BLOCK_ORDER each); final_proj weights, biases; matchability weights, biases;
+    token-confidence weights, biases; a vector of ones."""
+    bf, f32 = torch.bfloat16, torch.float32
+
+    def t(a, dtype):
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32))).to(dtype).contiguous().to(device)
+
+    def ffn(b, p):
+        b["Wf1"], b["bf1"] = t(pack_kstep(sd[p + "ffn.0.weight"]), bf), t(sd[p + "ffn.0.bias"], f32)
+        b["ln_g"], b["ln_b"] = t(sd[p + "ffn.1.weight"], f32), t(sd[p + "ffn.1.bias"], f32)
+        b["Wf2"], b["bf2"] = t(pack_kstep(sd[p + "ffn.3.weight"]), bf), t(sd[p + "ffn.3.bias"], f32)
+        return b
+
+    blocks = {"self": [], "cross": []}
+    perm = qkv_row_order()
+    for i in range(LG_LAYERS):
+        p = f"transformers.{i}.self_attn."
+        b = {"Wqkv": t(pack_kstep(np.asarray(sd[p + "Wqkv.weight"])[perm]), bf),
+             "bqkv": t(np.asarray(sd[p + "Wqkv.bias"])[perm], f32),
+             "Wout": t(pack_kstep(sd[p + "out_proj.weight"]), bf),
+             "bout": t(sd[p + "out_proj.bias"], f32)}
+        blocks["self"].append(ffn(b, p))
+        p = f"transformers.{i}.cross_attn."
+        c = {"Wqkv": t(pack_kstep(np.concatenate([sd[p + "to_qk.weight"], sd[p + "to_v.weight"]])), bf),
+             "bqkv": t(np.concatenate([sd[p + "to_qk.bias"], sd[p + "to_v.bias"]]), f32),
+             "Wout": t(pack_kstep(sd[p + "to_out.weight"]), bf),
+             "bout": t(sd[p + "to_out.bias"], f32)}
+        blocks["cross"].append(ffn(c, p))
+    w = [t(sd["posenc.Wr.weight"], f32)]
+    for kind in ("self", "cross"):
+        for b in blocks[kind]:
+            w += [b[f] for f in BLOCK_ORDER]
+    la = [f"log_assignment.{i}." for i in range(LG_LAYERS)]
+    tc = [f"token_confidence.{i}.token.0." for i in range(LG_LAYERS - 1)]
+    w += [t(sd[p + "final_proj.weight"], bf) for p in la]
+    w += [t(sd[p + "final_proj.bias"], f32) for p in la]
+    w += [t(np.asarray(sd[p + "matchability.weight"]).reshape(-1), f32) for p in la]
+    w += [t(np.asarray(sd[p + "matchability.bias"]).reshape(-1), f32) for p in la]
+    w += [t(np.asarray(sd[p + "weight"]).reshape(-1), f32) for p in tc]
+    w += [t(np.asarray(sd[p + "bias"]).reshape(-1), f32) for p in tc]
+    w.append(t(np.ones(256, np.float32), f32))
+    return w
+
+
 class LightGlueGPU:
     """Batched LightGlue(features='superpoint') on the HIP device."""
 
@@ -55,50 +101,8 @@ class LightGlueGPU:
         self.pruning_min_kpts = int(pruning_min_kpts)
         self._w = self._pack(state_dict)
 
-    def _t(self, a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32))).to(dtype).contiguous().to(self.device)
-
     def _pack(self, sd):
-        """Device tensors in mlg_lg_weights order (torch.ops.mlgate.lightglue): Wr; the self
-        then the cross blocks (BLOCK_ORDER each); final_proj weights, biases; matchability
-        weights, biases; token-confidence weights, biases; a vector of ones."""
-        bf, f32 = torch.bfloat16, torch.float32
-        blocks = {"self": [], "cross": []}
-        perm = qkv_row_order()
-        for i in range(LG_LAYERS):
-            p = f"transformers.{i}.self_attn."
-            b = {"Wqkv": self._t(pack_kstep(np.asarray(sd[p + "Wqkv.weight"])[perm]), bf),
-                 "bqkv": self._t(np.asarray(sd[p + "Wqkv.bias"])[perm], f32),
-                 "Wout": self._t(pack_kstep(sd[p + "out_proj.weight"]), bf),
-                 "bout": self._t(sd[p + "out_proj.bias"], f32)}
-            blocks["self"].append(self._ffn(b, sd, p))
-            p = f"transformers.{i}.cross_attn."
-            c = {"Wqkv": self._t(pack_kstep(np.concatenate([sd[p + "to_qk.weight"], sd[p + "to_v.weight"]])), bf),
-                 "bqkv": self._t(np.concatenate([sd[p + "to_qk.bias"], sd[p + "to_v.bias"]]), f32),
-                 "Wout": self._t(pack_kstep(sd[p + "to_out.weight"]), bf),
-                 "bout": self._t(sd[p + "to_out.bias"], f32)}
-            blocks["cross"].append(self._ffn(c, sd, p))
-        w = [self._t(sd["posenc.Wr.weight"], f32)]
-        for kind in ("self", "cross"):
-            for b in blocks[kind]:
-                w += [b[f] for f in BLOCK_ORDER]
-        la = [f"log_assignment.{i}." for i in range(LG_LAYERS)]
-        tc = [f"token_confidence.{i}.token.0." for i in range(LG_LAYERS - 1)]
-        w += [self._t(sd[p + "final_proj.weight"], bf) for p in la]
-        w += [self._t(sd[p + "final_proj.bias"], f32) for p in la]
-        w += [self._t(np.asarray(sd[p + "matchability.weight"]).reshape(-1), f32) for p in la]
-        w += [self._t(np.asarray(sd[p + "matchability.bias"]).reshape(-1), f32) for p in la]
-        w += [self._t(np.asarray(sd[p + "weight"]).reshape(-1), f32) for p in tc]
-        w += [self._t(np.asarray(sd[p + "bias"]).reshape(-1), f32) for p in tc]
-        w.append(self._t(np.ones(256, np.float32), f32))
-        return w
-
-    def _ffn(self, b, sd, p):
-        bf, f32 = torch.bfloat16, torch.float32
-        b["Wf1"], b["bf1"] = self._t(pack_kstep(sd[p + "ffn.0.weight"]), bf), self._t(sd[p + "ffn.0.bias"], f32)
-        b["ln_g"], b["ln_b"] = self._t(sd[p + "ffn.1.weight"], f32), self._t(sd[p + "ffn.1.bias"], f32)
-        b["Wf2"], b["bf2"] = self._t(pack_kstep(sd[p + "ffn.3.weight"]), bf), self._t(sd[p + "ffn.3.bias"], f32)
-        return b
+        return pack_weights(sd, self.device)
 
     def match_device(self, kpts, desc, counts, pair_a, pair_b):
         """kpts f32 [F, kmax, 2], desc f32 [F, kmax, 256] on the device; counts, pair_a, pair_b

@@ -81,7 +81,7 @@ def position_encoding(hc, wc, d=D_C):
 
 
 def weight_list(sd, device):
-    """The torch.ops.mlgate.loftr_* weight tensor list (csrc/torch_ops.cpp loftr_weights)."""
+    """The torch.ops.mlgate.loftr_* weight tensor list on ``device`` (without the packed tails)."""
     dev = torch.device(device)
     bf = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev).to(torch.bfloat16)  # noqa: E731
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731

@@ -53,6 +53,12 @@ def pack_head(sd):
             g("row_proj.bias")]
 
 
+def head_list(sd, device):
+    """The torch.ops.mlgate.mixvpr_* ``head`` list on ``device`` (pack_head; mix_w in bf16)."""
+    return [torch.as_tensor(t).to(device, torch.bfloat16 if i == 0 else torch.float32).contiguous()
+            for i, t in enumerate(pack_head(sd))]
+
+
 class MixVprGPU:
     """Packed device weights for batched MixVPR descriptor extraction."""
 
@@ -65,8 +71,7 @@ class MixVprGPU:
         self.max_batch = max_batch
         backbone = {k[len("backbone.model."):]: v for k, v in state_dict.items() if k.startswith("backbone.model.")}
         self._trunk = pack_trunk(backbone, self.device, MIXVPR_STAGES)
-        self._head = [torch.as_tensor(t).to(self.device, torch.bfloat16 if i == 0 else torch.float32).contiguous()
-                      for i, t in enumerate(pack_head(state_dict))]
+        self._head = head_list(state_dict, self.device)
 
     def forward(self, frames):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, 4096]."""

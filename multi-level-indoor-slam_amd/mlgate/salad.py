@@ -42,6 +42,13 @@ def pack_aggregator(sd):
             g("token_features.2.weight"), g("token_features.2.bias")], dust
 
 
+def aggregator_list(sd, device):
+    """(the torch.ops.mlgate.salad_forward ``salad`` list on ``device``, dust_bin)."""
+    agg, dust = pack_aggregator(sd)
+    return [t.to(device, torch.bfloat16 if i in (0, 2) else torch.float32).contiguous()
+            for i, t in enumerate(agg)], dust
+
+
 class SaladGPU:
     """Packed device weights for batched SALAD descriptor extraction."""
 
@@ -55,10 +62,7 @@ class SaladGPU:
                            swap_rb=False, precise=False)  # mlg_salad_forward runs the plain bf16 trunk
         self.device = self._vit.device
         self.max_batch = max_batch
-        agg, self.dust_bin = pack_aggregator(state_dict)
-        bf = {0, 2}
-        self._agg = [t.to(self.device, torch.bfloat16 if i in bf else torch.float32).contiguous()
-                     for i, t in enumerate(agg)]
+        self._agg, self.dust_bin = aggregator_list(state_dict, self.device)
 
     def forward(self, frames):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, 8448]."""

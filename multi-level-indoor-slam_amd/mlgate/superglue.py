@@ -40,7 +40,7 @@ def fold_bn1d(w, b, sd, bn, eps=1e-5):
 
 
 def weight_list(sd, device, gemm_dtype=torch.bfloat16):
-    """Device tensors in mlg_sg_weights order (csrc/torch_ops.cpp superglue); GEMM weights
+    """The torch.ops.mlgate.superglue weight list on ``device``; GEMM weights
     in ``gemm_dtype`` (bf16 for the kernels; float32 lets tests check the layout exactly)."""
     dev = torch.device(device)
     bf = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev).to(gemm_dtype)  # noqa: E731

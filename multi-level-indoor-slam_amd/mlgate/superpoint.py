@@ -14,7 +14,6 @@ _ORDER = ["conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", 
           "convDb"]
 
 
-
 def pack_weights(sd, device):
     """Device tensors in the kernel layouts: bf16 [Cout][3][3][Cin] / [Cout][Cin]; convPb padded to 128 rows."""
     t = {}
@@ -33,6 +32,13 @@ def pack_weights(sd, device):
     return t
 
 
+def weight_list(sd, device):
+    """The torch.ops.mlgate.superpoint weight list on ``device``: conv1a w, b; the 11 bf16
+    weights (_ORDER); their 11 biases."""
+    t = pack_weights(sd, device)
+    return [t["conv1a.w"], t["conv1a.b"]] + [t[f"{n}.w"] for n in _ORDER] + [t[f"{n}.b"] for n in _ORDER]
+
+
 class SuperPointGPU:
     """Batched SuperPoint keypoints / descriptors on the HIP device."""
 
@@ -47,10 +53,7 @@ class SuperPointGPU:
         self.det_thr = float(detection_threshold)
         self.nms_radius = int(nms_radius)
         self.border = int(remove_borders)
-        self._t = pack_weights(state_dict, self.device)
-        # mlg_sp_weights order: conv1a w, b; the 11 bf16 weights; their 11 biases
-        self._w = ([self._t["conv1a.w"], self._t["conv1a.b"]] + [self._t[f"{n}.w"] for n in _ORDER]
-                   + [self._t[f"{n}.b"] for n in _ORDER])
+        self._w = weight_list(state_dict, self.device)
 
     def extract_device(self, frames, with_bf16=False):
         """frames: device uint8 [B, H, W, C] -> device (kpts [B, K, 2], scores [B, K], desc [B, K, 256],

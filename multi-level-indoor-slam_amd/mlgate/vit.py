@@ -48,6 +48,38 @@ def split_weight(w):
     return torch.cat([hi, lo], dim=1).contiguous()
 
 
+def pack_weights(sd, device, grid, precise):
+    """The torch.ops.mlgate.vit_forward_into weight list on ``device``: patch_w, patch_b, cls,
+    pos (resampled to ``grid`` x ``grid`` patches), DEPTH x BLOCK_ORDER, norm_w, norm_b; the
+    GEMM weights bf16, [W_hi | W_lo] with ``precise``."""
+    f32, bf = torch.float32, torch.bfloat16
+
+    def dev(a, dtype):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(device, torch.float32).to(dtype).contiguous()
+
+    def gemm_w(a):  # a GEMM weight in the layout of this forward
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        t = t.to(device, torch.float32)
+        return split_weight(t) if precise else t.to(bf).contiguous()
+
+    pw = torch.as_tensor(np.asarray(sd["patch_embed.proj.weight"], np.float32)).reshape(EMBED, -1)
+    pos = torch.as_tensor(np.asarray(sd["pos_embed"], np.float32)).to(device)
+    w = [gemm_w(F.pad(pw, (0, PATCH_K - pw.shape[1]))), dev(sd["patch_embed.proj.bias"], f32),
+         dev(np.asarray(sd["cls_token"], np.float32).reshape(EMBED), f32),
+         dev(resample_pos_embed(pos, grid).reshape(-1, EMBED), f32)]
+    names = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "qkv_w": "attn.qkv.weight",
+             "qkv_b": "attn.qkv.bias", "proj_w": "attn.proj.weight", "proj_b": "attn.proj.bias",
+             "ls1": "ls1.gamma", "norm2_w": "norm2.weight", "norm2_b": "norm2.bias", "fc1_w": "mlp.fc1.weight",
+             "fc1_b": "mlp.fc1.bias", "fc2_w": "mlp.fc2.weight", "fc2_b": "mlp.fc2.bias", "ls2": "ls2.gamma"}
+    for i in range(DEPTH):
+        for f in BLOCK_ORDER:
+            v = sd[f"blocks.{i}." + names[f]]
+            w.append(gemm_w(v) if f in BF16_FIELDS else dev(v, f32))
+    w += [dev(sd["norm.weight"], f32), dev(sd["norm.bias"], f32)]
+    return w
+
+
 class VitB14:
     """Packed device weights + workspace for batched CricaVPR descriptor extraction.
 
@@ -73,34 +105,8 @@ class VitB14:
                       | (MLG_VIT_SPLIT if self.precise else 0))
         self._w = self._pack(state_dict)
 
-    # ------------------------------------------------------------ weights
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(self.device, torch.float32).to(dtype).contiguous()
-
     def _pack(self, sd):
-        """Device tensors in mlg_vit_weights order (torch.ops.mlgate.vit_forward_into)."""
-        f32, bf = torch.float32, torch.bfloat16
-        pw = torch.as_tensor(np.asarray(sd["patch_embed.proj.weight"], np.float32)).reshape(EMBED, -1)
-        pos = torch.as_tensor(np.asarray(sd["pos_embed"], np.float32)).to(self.device)
-
-        def gemm_w(a):  # a GEMM weight in the layout of this forward
-            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-            t = t.to(self.device, torch.float32)
-            return split_weight(t) if self.precise else t.to(bf).contiguous()
-        w = [gemm_w(F.pad(pw, (0, PATCH_K - pw.shape[1]))), self._dev(sd["patch_embed.proj.bias"], f32),
-             self._dev(np.asarray(sd["cls_token"], np.float32).reshape(EMBED), f32),
-             self._dev(resample_pos_embed(pos, self.grid).reshape(-1, EMBED), f32)]
-        names = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "qkv_w": "attn.qkv.weight",
-                 "qkv_b": "attn.qkv.bias", "proj_w": "attn.proj.weight", "proj_b": "attn.proj.bias",
-                 "ls1": "ls1.gamma", "norm2_w": "norm2.weight", "norm2_b": "norm2.bias", "fc1_w": "mlp.fc1.weight",
-                 "fc1_b": "mlp.fc1.bias", "fc2_w": "mlp.fc2.weight", "fc2_b": "mlp.fc2.bias", "ls2": "ls2.gamma"}
-        for i in range(DEPTH):
-            for f in BLOCK_ORDER:
-                v = sd[f"blocks.{i}." + names[f]]
-                w.append(gemm_w(v) if f in BF16_FIELDS else self._dev(v, f32))
-        w += [self._dev(sd["norm.weight"], f32), self._dev(sd["norm.bias"], f32)]
-        return w
+        return pack_weights(sd, self.device, self.grid, self.precise)
 
     # ------------------------------------------------------------ forward
     def forward_into(self, frames, desc_out, local_out=None):

@@ -350,3 +350,12 @@ def test_abi_rejects_bad_arguments(dev):
     v = vocab(struct_size=8)
     assert lib.mlg_anyloc_forward(None, ctypes.byref(v), frames.data_ptr(), 1, 32, 32, 3, 32 * 32 * 3, 518, 6,
                                   ws.data_ptr(), n, desc.data_ptr(), stream) == EINVAL
+
+
+def test_malformed_weight_list_is_refused(dev, engine):
+    """anyloc_forward checks every tensor of the ViT list before launching (weight_tables.h)."""
+    from weight_corruptions import assert_refused
+    x = torch.zeros(1, 32, 32, 3, dtype=torch.uint8, device=dev)
+    vit = engine._vit
+    assert_refused(lambda b: _native.ops().anyloc_forward(x, b, engine.centers, engine.image_size, vit.flags, 1),
+                   vit._w, 0, "patch_w")

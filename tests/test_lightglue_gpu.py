@@ -209,3 +209,13 @@ def test_lightglue_no_early_stop_prunes_on_matchability_only(dev, sd):
     r = {tuple(x): i for i, x in enumerate(rm.tolist())}
     common = set(g) & set(r)
     assert len(common) >= 0.95 * max(len(g), len(r)), (len(common), len(g), len(r))
+
+
+def test_malformed_weight_list_is_refused(dev, lg):
+    """The lightglue op checks every tensor of its list before launching (weight_tables.h)."""
+    from mlgate import _native
+    from weight_corruptions import assert_refused
+    kp, ds = torch.zeros(2, 8, 2, device=dev), torch.zeros(2, 8, 256, device=dev)
+    host = lambda a: torch.tensor(a, dtype=torch.int32)  # noqa: E731
+    assert_refused(lambda b: _native.ops().lightglue(kp, ds, host([8, 8]), host([0]), host([1]), b, 0.95, 0.99, 0.1,
+                                                     1536), lg._w, 35, "self[3].Wf1")

@@ -322,3 +322,26 @@ def test_layer0_dedup_equals_plain_path(dev, setup):
     assert int(dedup[0].sum()) > 0, "no coarse match: the comparison would be vacuous"
     for name, a, b in zip(("n", "k0", "k1", "conf"), dedup, plain):
         assert torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("op", ["loftr_features", "loftr_match", "loftr_coarse_layer", "loftr_pack_tails"])
+def test_malformed_weight_list_is_refused(dev, setup, op):
+    """Every loftr_* op checks each tensor of its list before launching (weight_tables.h)."""
+    from weight_corruptions import assert_refused
+    lf = setup[1]
+    ops, w = lf.ops, lf.weights
+    H, W = 32, 32
+    L = (H // 8) * (W // 8)
+    call = {
+        "loftr_features": lambda b: ops.loftr_features(torch.zeros(1, H, W, 1, dtype=torch.uint8, device=dev), b),
+        "loftr_match": lambda b: ops.loftr_match(torch.zeros(2, L, 256, device=dev),
+                                                 torch.zeros(2, (H // 2) * (W // 2), 128, device=dev),
+                                                 torch.tensor([0], dtype=torch.int32), torch.tensor([1], dtype=torch.int32),
+                                                 torch.zeros(L, 256, device=dev), b, H, W),
+        "loftr_coarse_layer": lambda b: ops.loftr_coarse_layer(torch.zeros(2 * L, 256, device=dev),
+                                                               torch.zeros(2 * L, 512, device=dev, dtype=torch.bfloat16),
+                                                               b, 0, 1, 1, L),
+        "loftr_pack_tails": lambda b: ops.loftr_pack_tails(b[:129]),
+    }[op]
+    assert len(w) == 130
+    assert_refused(call, w, 46, "coarse[0].w1")

@@ -133,3 +133,14 @@ def test_place_recognition_with_native_mixvpr(dev, monkeypatch):
     of4 = [m for m in spr.find_loop_closures(k=5) if m.query_idx == 4]
     best = max(of4, key=lambda m: m.similarity)
     assert best.match_idx == 0 and best.similarity >= 0.9999, [(m.match_idx, m.similarity) for m in of4]
+
+
+def test_malformed_weight_lists_are_refused(engine, dev):
+    """mixvpr_forward and mixvpr_head check their lists before launching (weight_tables.h)."""
+    from weight_corruptions import assert_refused
+    ops = _native.ops()
+    x = torch.zeros(1, 32, 32, 3, dtype=torch.uint8, device=dev)
+    f = torch.zeros(1, 400, 1024, device=dev)
+    assert_refused(lambda b: ops.mixvpr_forward(x, b, engine._head, 2), engine._trunk, 100, "blocks[12].w2")
+    assert_refused(lambda b: ops.mixvpr_forward(x, engine._trunk, b, 2), engine._head, 0, "mix_w")
+    assert_refused(lambda b: ops.mixvpr_head(f, b), engine._head, 0, "mix_w")

@@ -58,3 +58,12 @@ def test_mixvpr_salad_dropin(dev):
     assert ds.shape == (8448,) and np.allclose(ds[:2048], d[:2048]) and np.all(ds[2048:] == 0)
     gray = img[..., 0]
     assert m.extract_descriptor(gray).shape == (4096,)
+
+
+def test_malformed_weight_list_is_refused(dev):
+    """The resnet50 op checks every tensor of its list before launching (weight_tables.h)."""
+    from mlgate.resnet import pack_trunk
+    from weight_corruptions import assert_refused
+    w = pack_trunk(resnet50_state_dict(0), dev)
+    x = torch.zeros(1, 32, 32, 3, dtype=torch.uint8, device=dev)
+    assert_refused(lambda b: _native.ops().resnet50(x, b, 2048), w, 32, "blocks[3].wd")

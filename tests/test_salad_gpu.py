@@ -87,3 +87,18 @@ def test_salad_dropin_native_and_fallback(dev, frames, monkeypatch):
     with pytest.warns(UserWarning, match="MixVPR fallback"):
         fb = SALAD(device=str(dev)).extract_descriptor(frames[0])
     assert fb.shape == (8448,) and np.all(fb[2048:] == 0)
+
+
+def test_malformed_weight_lists_are_refused(dev, sd):
+    """salad_forward checks both of its lists before launching (weight_tables.h)."""
+    from mlgate import _native
+    from mlgate.salad import IMAGE_SIZE, aggregator_list
+    from mlgate.vit import pack_weights
+    from weight_corruptions import assert_refused
+    backbone = {k[len("backbone.model."):]: v for k, v in sd.items() if k.startswith("backbone.model.")}
+    w = pack_weights(backbone, dev, IMAGE_SIZE // 14, False)
+    agg, dust = aggregator_list(sd, dev)
+    x = torch.zeros(1, 32, 32, 3, dtype=torch.uint8, device=dev)
+    ops = _native.ops()
+    assert_refused(lambda b: ops.salad_forward(x, w, b, dust, IMAGE_SIZE, 2), agg, 2, "w2")
+    assert_refused(lambda b: ops.salad_forward(x, b, agg, dust, IMAGE_SIZE, 2), w, 167, "blocks[11].fc1_w")

@@ -138,3 +138,13 @@ def test_superglue_verifier_native(dev, monkeypatch):
     assert np.all(conf > 0.2)
     out = m.detect_and_match_batch(torch.from_numpy(fr).to(dev), [(0, 1)])
     assert np.array_equal(out[0][0], k0) and np.array_equal(out[0][2], conf)
+
+
+def test_malformed_weight_list_is_refused(dev, sg):
+    """The superglue op checks every tensor of its list before launching (weight_tables.h)."""
+    from mlgate import _native
+    from weight_corruptions import assert_refused
+    kp, sc, ds = torch.zeros(2, 8, 2, device=dev), torch.zeros(2, 8, device=dev), torch.zeros(2, 8, 256, device=dev)
+    host = lambda a: torch.tensor(a, dtype=torch.int32)  # noqa: E731
+    assert_refused(lambda b: _native.ops().superglue(kp, sc, ds, host([8, 8]), host([0]), host([1]), b, 1.0, W, H, 20,
+                                                     0.2), sg._w, 28, "layer[2].Wout")

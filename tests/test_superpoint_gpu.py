@@ -136,3 +136,12 @@ def test_superpoint_against_fp32_reference(dev, sd):
         print(f"fp32 SuperPoint: keypoint overlap {overlap:.4f}, descriptor cosine min {cos.min():.4f} "
               f"median {np.median(cos):.5f}")
         assert overlap >= 0.95 and cos.min() >= 0.98
+
+
+def test_malformed_weight_list_is_refused(dev, sd):
+    """The superpoint op checks every tensor of its list before launching (weight_tables.h)."""
+    from mlgate import _native
+    from mlgate.superpoint import weight_list
+    from weight_corruptions import assert_refused
+    x = torch.zeros(1, 32, 32, 1, dtype=torch.uint8, device=dev)
+    assert_refused(lambda b: _native.ops().superpoint(x, b, 0.001, 64, 4, 4, False), weight_list(sd, dev), 10, "w[8]")

@@ -125,3 +125,22 @@ def test_precise_batch_split_bit_identical_walking_tiles(dev, sd, frames):
     d4 = VitB14(sd, device="cuda", max_batch=4, precise=True).forward(x)
     torch.cuda.synchronize()
     assert torch.equal(d16, d4)
+
+
+def test_malformed_weight_list_is_refused(dev, sd):
+    """vit_forward_into checks every tensor of its list before launching (weight_tables.h);
+    `pos` is sized by image_size and the GEMM weights by the packing flag.  Every replacement
+    is at least as large as what the flags ask for."""
+    from mlgate import _native
+    from mlgate.vit import pack_weights
+    from weight_corruptions import assert_refused
+    w = pack_weights(sd, dev, 23, False)
+    x = torch.zeros(1, 32, 32, 3, dtype=torch.uint8, device=dev)
+    desc = torch.empty(1, 768, device=dev)
+    assert_refused(lambda b: _native.ops().vit_forward_into(x, b, 322, 0, 2, desc, None), w, 6, "blocks[0].qkv_w")
+    with pytest.raises(RuntimeError, match=r"weights\[3\] \(pos\)"):
+        _native.ops().vit_forward_into(x, w, 308, 0, 2, desc, None)  # 22 x 22 patches: a smaller table than pos
+    # a list packed [W_hi | W_lo] for MLG_VIT_SPLIT, without the flag: every GEMM weight is twice the plain size
+    # (the other way round, a plain list with the flag, is too short: tests/test_weight_lists_cpu.py)
+    with pytest.raises(RuntimeError, match=r"weights\[0\] \(patch_w\)"):
+        _native.ops().vit_forward_into(x, pack_weights(sd, dev, 23, True), 322, 0, 2, desc, None)
