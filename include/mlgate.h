@@ -35,7 +35,7 @@ extern "C" {
 #define MLG_VIT_PATCH_K 768 /* 3*14*14 = 588 patch inputs, zero-padded to 12 K-tiles of 64 */
 
 /* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_salad_weights, mlg_vlad_vocab,
- * mlg_rn_weights, mlg_mixvpr_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
+ * mlg_crica_weights, mlg_rn_weights, mlg_mixvpr_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
  * mlg_orb_params) begins with a head: struct_size = sizeof(the struct) and abi_version =
  * MLG_ABI_VERSION, both set by initialising it with MLG_STRUCT_INIT(type).  A struct whose
  * head disagrees -- built against another version of this header (a shorter or longer
@@ -190,6 +190,80 @@ int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, co
 size_t mlg_kmeans_workspace_bytes(long M, int K);
 int mlg_kmeans_step(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
                     int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- CricaVPR --
+ * CricaVPR's native branch: the descriptor its class declares (place_recognition.py:528-533,
+ * descriptor_dim 10752) and never builds (:558-578 always falls back to DINOv2 + GeM).
+ * Upstream CricaVPRNet.forward (Lu-Feng/CricaVPR) over the final-LayerNormed tokens of
+ * ViT-B/14, a row-major g x g patch grid (g = image_size / 14 >= MLG_CRICA_MIN_GRID):
+ *   pyramid  14 rows of 768 per frame.  Row 0: the normed CLS token.  The patch tokens are
+ *            L2-normalised per token (x / max(|x|, 1e-12)), then GeM-pooled per region,
+ *            mean(clamp(x, 1e-6)^p)^(1/p) per channel with the learned scalar p = gem_p.
+ *            Rows 1-4: patch rows [0:8], [8:g] x columns [0:8], [8:g]; rows 5-13: [0:5],
+ *            [5:11], [11:g] x the same, row band major -- upstream's literal slices, so at
+ *            g = 23 the bands are 8 / 15 and 5 / 6 / 12 wide.  All g^2 patches take part.
+ *   encoder  nn.TransformerEncoder, 2 post-LN layers (d_model 768, 16 heads of 48,
+ *            feed-forward 2048, erf GELU, LayerNorm eps 1e-5), applied to [B, 14, 768] with
+ *            batch_first = False: the sequence axis is the images.  Row r of a frame
+ *            attends over row r of the frames of its group.
+ *   output   the 14 x 768 values flattened and divided by max(|.|, 1e-12).
+ * Groups: frames [j * group, (j + 1) * group) of a call form group j (the last may be short);
+ * group 1 is a frame alone (softmax = 1: attention reduces to out_proj(V)).  Every sum has a
+ * fixed order inside its group and there are no floating-point atomics: a group's
+ * descriptors are the same bits whatever else is in the call and wherever the group sits.
+ * The four linear layers run as split-bf16 GEMMs (MLG_VIT_SPLIT packing, three MFMA products
+ * per product); pooling, attention, LayerNorm and the normalisations are f32. */
+#define MLG_CRICA_ROWS 14
+#define MLG_CRICA_DIM 10752 /* MLG_CRICA_ROWS x 768 */
+#define MLG_CRICA_MAX_GROUP 32
+#define MLG_CRICA_MAX_BATCH 4096
+#define MLG_CRICA_MIN_GRID 12 /* image_size >= 168: every region non-empty */
+typedef struct mlg_crica_layer {
+    const uint16_t* in_w; /* self_attn.in_proj_weight, bf16 [2304][2 x 768] = [W_hi | W_lo] */
+    const float* in_b;    /* [2304] */
+    const uint16_t* out_w; /* self_attn.out_proj.weight [768][2 x 768] */
+    const float *out_b, *ln1_g, *ln1_b; /* [768] each: out_proj.bias, norm1 */
+    const uint16_t* fc1_w; /* linear1.weight [2048][2 x 768] */
+    const float* fc1_b;    /* [2048] */
+    const uint16_t* fc2_w; /* linear2.weight [768][2 x 2048] */
+    const float *fc2_b, *ln2_g, *ln2_b; /* [768] each: linear2.bias, norm2 */
+} mlg_crica_layer;
+typedef struct mlg_crica_weights {
+    uint32_t struct_size, abi_version; /* MLG_STRUCT_INIT(mlg_crica_weights) */
+    float gem_p;                       /* aggregation.1.p (3 at initialisation); > 0 */
+    mlg_crica_layer layers[2];
+} mlg_crica_weights;
+/* Workspace of mlg_op_crica_encoder for B frames: linear in B, sufficient for B in
+ * 1 .. MLG_CRICA_MAX_BATCH (14 rows per frame of 26624 bytes: the f32 stream, in_proj's f32
+ * output and the [hi | lo] operands of in_proj, out_proj and linear2; 16 KiB of fixed data
+ * and alignment).  The op returns MLG_ENOMEM below what it carves. */
+#define MLG_CRICA_HEAD_WS_BYTES(B) ((size_t)(B) * (MLG_CRICA_ROWS * 26624) + 16384)
+/* Every entry point below returns MLG_EINVAL, before any GPU call, for a foreign struct head,
+ * a null or misaligned (16 bytes) pointer, B outside 1 .. MLG_CRICA_MAX_BATCH, group outside
+ * 1 .. MLG_CRICA_MAX_GROUP and a gem_p that is not a finite positive number.
+ *
+ * The whole branch for a batch of frames: mlg_vit_forward's trunk (flags must carry
+ * MLG_VIT_SPLIT; CricaVPR._preprocess: image_size 322, channels swapped), then the head on its
+ * residual stream.  workspace: mlg_vit_workspace_bytes(B, image_size) -- the head's buffers
+ * alias trunk buffers that are dead by then (MLG_ENOMEM if short).  desc_out f32
+ * [B, MLG_CRICA_DIM].  local_out (or NULL): what mlg_vit_forward writes there, by the same
+ * kernel from the same forward, f32 [B, (S/14)^2 - 1, 768].  image_size < 168: MLG_EINVAL. */
+int mlg_crica_forward(const mlg_vit_weights* w, const mlg_crica_weights* cw, const uint8_t* frames, int B, int H,
+                      int W, int C, long frame_stride, int image_size, int flags, int group, void* workspace,
+                      size_t workspace_bytes, float* desc_out, float* local_out_or_null, void* stream);
+/* The trunk alone (test access): the residual stream before the final LayerNorm, f32
+ * [B, 1 + (S/14)^2, 768], CLS first -- what mlg_op_crica_pool takes. */
+int mlg_op_vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+                     int image_size, int flags, void* workspace, size_t workspace_bytes, float* tokens_prenorm,
+                     void* stream);
+/* The pyramid alone: tokens_prenorm f32 [B, 1 + grid^2, 768], the trunk's final LayerNorm
+ * (norm_w, norm_b; eps 1e-6) -> out f32 [B, 14, 768].  grid in MLG_CRICA_MIN_GRID .. 64. */
+int mlg_op_crica_pool(const float* tokens_prenorm, const float* norm_w, const float* norm_b, int B, int grid,
+                      float gem_p, float* out, void* stream);
+/* The encoder and the final normalisation alone: pooled f32 [B, 14, 768] -> desc f32
+ * [B, MLG_CRICA_DIM]; workspace_bytes >= MLG_CRICA_HEAD_WS_BYTES(B). */
+int mlg_op_crica_encoder(const mlg_crica_weights* cw, const float* pooled, int B, int group, void* workspace,
+                         size_t workspace_bytes, float* desc, void* stream);
 
 /* --------------------------------------------------------------- retrieval --
  * SemanticPlaceRecognition.find_loop_closures (place_recognition.py:851-911) for

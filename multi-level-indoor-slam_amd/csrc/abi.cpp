@@ -84,6 +84,33 @@ size_t anyloc_carve(const VitGeom& g, int K, void* base, AnylocBufs* out) {
     return b.head_bytes ? c.total() : 0;
 }
 
+// CricaVPR's head inside the ViT workspace: the pooled rows, and the GeM descriptor the final
+// norm kernel also writes (unused), in `h`, dead after the last block; the encoder's buffers
+// in `x`, dead once the pyramid and the final norm have read it
+struct CricaBufs {
+    VitWorkspace vit;
+    float *pooled, *gem;  // [B, 14, 768]; [B, 768]
+    void* head;
+    size_t head_bytes;
+};
+
+// 0 when the head does not fit the dead trunk buffers (never at image_size >= 168)
+size_t crica_carve(const VitGeom& g, void* base, CricaBufs* out) {
+    const size_t rows = (size_t)g.B * g.T;
+    WsCarver c(base);
+    CricaBufs b;
+    b.vit = vit_take(c, g);
+    WsCarver in_h(b.vit.h);
+    b.pooled = in_h.take<float>((size_t)g.B * MLG_CRICA_ROWS * 768);
+    b.gem = in_h.take<float>((size_t)g.B * 768);
+    b.head = b.vit.x;
+    b.head_bytes = mlg_crica_head_ws_bytes(g.B);
+    if (out) *out = b;
+    const bool fits = b.head_bytes && in_h.total() <= rows * 3072 * 2 * sizeof(bf16_t) &&
+                      b.head_bytes <= rows * 768 * sizeof(float);
+    return fits ? c.total() : 0;
+}
+
 // k <= 32 and D % 4 == 0 take the fused scan (no [Q, N] matrix): normalised rows plus
 // the per-split partial lists
 bool knn_fused(int D, int k) { return k >= 1 && k <= 32 && D % 4 == 0; }
@@ -353,6 +380,63 @@ int mlg_kmeans_step(const float* tokens, long M, float* centers, int K, int32_t*
                     int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
     return mlg_kmeans_step_run(tokens, M, centers, K, labels, changed, counts, workspace, workspace_bytes,
                                (hipStream_t)stream);
+}
+
+static int crica_trunk_args_ok(const mlg_vit_weights* w, const uint8_t* frames, int B, int image_size, int flags,
+                               const void* workspace) {
+    if (!mlg_head_ok(w, MLG_ABI_VERSION) || !frames || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return 0;
+    if (B < 1 || B > MLG_CRICA_MAX_BATCH || image_size <= 0 || image_size % PATCH) return 0;
+    return (flags & MLG_VIT_SPLIT) && w->packing == MLG_VIT_SPLIT;
+}
+
+int mlg_crica_forward(const mlg_vit_weights* w, const mlg_crica_weights* cw, const uint8_t* frames, int B, int H,
+                      int W, int C, long frame_stride, int image_size, int flags, int group, void* workspace,
+                      size_t workspace_bytes, float* desc_out, float* local_out_or_null, void* stream) {
+    if (!mlg_head_ok(cw, MLG_ABI_VERSION) || !crica_trunk_args_ok(w, frames, B, image_size, flags, workspace))
+        return MLG_EINVAL;
+    if (!mlg_crica_weights_ok(*cw) || group < 1 || group > MLG_CRICA_MAX_GROUP) return MLG_EINVAL;
+    if (!desc_out || ((reinterpret_cast<uintptr_t>(desc_out) | reinterpret_cast<uintptr_t>(local_out_or_null)) & 15))
+        return MLG_EINVAL;
+    if (image_size < MLG_CRICA_MIN_GRID * PATCH) return MLG_EINVAL;
+    const VitGeom g(B, image_size);
+    CricaBufs b;
+    const size_t need = crica_carve(g, workspace, &b);
+    if (!need) return MLG_EINVAL;
+    if (need > workspace_bytes) return MLG_ENOMEM;
+    hipStream_t s = (hipStream_t)stream;
+    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s, 1));
+    MLG_TRY(mlg_crica_pool_run(b.vit.x, w->norm_w, w->norm_b, g.B, g.grid, cw->gem_p, b.pooled, s));
+    if (local_out_or_null)  // the rerank cache: mlg_vit_forward's local features from this forward
+        MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, local_out_or_null, b.vit.partial, b.gem, g.B, g.T,
+                                   /*mean_pool=*/0, s));
+    return mlg_crica_encoder_run(*cw, b.pooled, g.B, group, b.head, b.head_bytes, desc_out, s);
+}
+
+int mlg_op_vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, int B, int H, int W, int C, long frame_stride,
+                     int image_size, int flags, void* workspace, size_t workspace_bytes, float* tokens_prenorm,
+                     void* stream) {
+    if (!crica_trunk_args_ok(w, frames, B, image_size, flags, workspace) || !tokens_prenorm) return MLG_EINVAL;
+    const VitGeom g(B, image_size);
+    VitWorkspace ws;
+    if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
+    hipStream_t s = (hipStream_t)stream;
+    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s, 1));
+    if (hipMemcpyAsync(tokens_prenorm, ws.x, (size_t)g.B * g.T * 768 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
+        hipSuccess)
+        return MLG_EHIP;
+    return MLG_OK;
+}
+
+int mlg_op_crica_pool(const float* tokens_prenorm, const float* norm_w, const float* norm_b, int B, int grid,
+                      float gem_p, float* out, void* stream) {
+    return mlg_crica_pool_run(tokens_prenorm, norm_w, norm_b, B, grid, gem_p, out, (hipStream_t)stream);
+}
+
+int mlg_op_crica_encoder(const mlg_crica_weights* cw, const float* pooled, int B, int group, void* workspace,
+                         size_t workspace_bytes, float* desc, void* stream) {
+    if (!mlg_head_ok(cw, MLG_ABI_VERSION)) return MLG_EINVAL;
+    return mlg_crica_encoder_run(*cw, pooled, B, group, workspace, workspace_bytes, desc, (hipStream_t)stream);
 }
 
 size_t mlg_knn_workspace_bytes(int N, int D, int Q) {

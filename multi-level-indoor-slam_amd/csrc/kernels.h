@@ -232,6 +232,17 @@ size_t mlg_kmeans_ws_bytes(long M, int K);
 int mlg_kmeans_step_run(const float* tokens, long M, float* centers, int K, int32_t* labels, int64_t* changed,
                         int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
 
+// crica.hip -- CricaVPR's native branch: the 14-region GeM pyramid over the trunk's residual
+// stream [B, 1 + grid^2, 768] and the cross-image encoder over its rows [B, 14, 768].  Both
+// validate their arguments (MLG_EINVAL) before launching; the encoder returns MLG_ENOMEM
+// below mlg_crica_head_ws_bytes(B) (0 for an unsupported B).
+bool mlg_crica_weights_ok(const mlg_crica_weights& cw);
+size_t mlg_crica_head_ws_bytes(int B);
+int mlg_crica_pool_run(const float* tokens, const float* norm_w, const float* norm_b, int B, int grid, float gem_p,
+                       float* out, hipStream_t s);
+int mlg_crica_encoder_run(const mlg_crica_weights& cw, const float* pooled, int B, int group, void* ws,
+                          size_t ws_bytes, float* desc, hipStream_t s);
+
 // plane.hip -- batched LiDAR ground-plane RANSAC
 size_t mlg_plane_ws_bytes(int S, int H);
 int mlg_plane_ransac_run(const float* pts, const int32_t* offs, int S, int H, uint64_t seed, double thr, void* ws,

@@ -683,6 +683,113 @@ std::tuple<Tensor, Tensor> kmeans_step(const Tensor& tokens, const Tensor& cente
     return {changed, counts};
 }
 
+// ---------------------------------------------------------------- CricaVPR
+mlg_crica_weights crica_weights(at::TensorList head, double gem_p, c10::Device dev) {
+    mlg_crica_weights cw = MLG_STRUCT_INIT(mlg_crica_weights);
+    fill_weights(wt::crica_table(), "crica", head, &cw, dev);
+    cw.gem_p = (float)gem_p;
+    return cw;
+}
+
+// frames uint8 [B, H, W, C] -> (desc f32 [B, 10752], local f32 [B, (S/14)^2 - 1, 768] or
+// an empty tensor).  Frames [j group, (j + 1) group) form group j; calls of at most
+// max_batch frames end on group boundaries.
+std::tuple<Tensor, Tensor> crica_forward(const Tensor& frames, at::TensorList w, at::TensorList head, double gem_p,
+                                         int64_t image_size, int64_t flags, int64_t group, int64_t max_batch,
+                                         bool with_local) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    TORCH_CHECK(group >= 1 && group <= MLG_CRICA_MAX_GROUP, "group must be in 1 .. ", MLG_CRICA_MAX_GROUP);
+    TORCH_CHECK(max_batch >= group, "max_batch must hold one group");
+    TORCH_CHECK(flags & MLG_VIT_SPLIT, "crica_forward runs the split-bf16 trunk (MLG_VIT_SPLIT)");
+    const mlg_vit_weights s = vit_weights(w, true, image_size, frames.device());
+    const mlg_crica_weights cw = crica_weights(head, gem_p, frames.device());
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    const int64_t grid = image_size / 14, n_local = grid * grid - 1;
+    const int64_t step = std::min<int64_t>(max_batch / group * group, MLG_CRICA_MAX_BATCH / group * group);
+    c10::DeviceGuard g(frames.device());
+    Tensor desc = at::empty({B, MLG_CRICA_DIM}, frames.options().dtype(at::kFloat));
+    Tensor local = at::empty({with_local ? B : 0, n_local, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
+    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(B, step), (int)image_size);
+    TORCH_CHECK(nbytes > 0, "crica_forward: unsupported image_size / batch");
+    Tensor ws = workspace(nbytes, frames);
+    const long stride = (long)(H * W * C);
+    for (int64_t b0 = 0; b0 < B; b0 += step) {
+        const int nb = (int)std::min(step, B - b0);
+        check_rc(mlg_crica_forward(&s, &cw, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
+                                   (int)image_size, (int)flags, (int)group, ws.data_ptr(), (size_t)ws.numel(),
+                                   mp<float>(desc) + b0 * MLG_CRICA_DIM,
+                                   with_local ? mp<float>(local) + b0 * n_local * MLG_VIT_EMBED : nullptr,
+                                   stream_of(frames)),
+                 "mlg_crica_forward");
+    }
+    return {desc, local};
+}
+
+// The trunk's residual stream before the final LayerNorm: f32 [B, 1 + (S/14)^2, 768]
+Tensor vit_trunk(const Tensor& frames, at::TensorList w, int64_t image_size, int64_t flags, int64_t max_batch) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    TORCH_CHECK(flags & MLG_VIT_SPLIT, "vit_trunk runs the split-bf16 trunk (MLG_VIT_SPLIT)");
+    const mlg_vit_weights s = vit_weights(w, true, image_size, frames.device());
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    const int64_t grid = image_size / 14, T = grid * grid + 1;
+    c10::DeviceGuard g(frames.device());
+    Tensor tokens = at::empty({B, T, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
+    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(B, max_batch), (int)image_size);
+    TORCH_CHECK(nbytes > 0, "vit_trunk: unsupported image_size / batch");
+    Tensor ws = workspace(nbytes, frames);
+    const long stride = (long)(H * W * C);
+    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
+        const int nb = (int)std::min(max_batch, B - b0);
+        check_rc(mlg_op_vit_trunk(&s, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
+                                  (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
+                                  mp<float>(tokens) + b0 * T * MLG_VIT_EMBED, stream_of(frames)),
+                 "mlg_op_vit_trunk");
+    }
+    return tokens;
+}
+
+// tokens_prenorm f32 [B, 1 + g^2, 768] -> the 14 pyramid rows f32 [B, 14, 768]
+Tensor crica_pool(const Tensor& tokens, const Tensor& norm_w, const Tensor& norm_b, double gem_p) {
+    want(tokens, at::kFloat, "tokens");
+    want(norm_w, at::kFloat, "norm_w");
+    want(norm_b, at::kFloat, "norm_b");
+    TORCH_CHECK(tokens.dim() == 3 && tokens.size(0) > 0 && tokens.size(2) == MLG_VIT_EMBED,
+                "tokens must be [B, 1 + g^2, 768]");
+    TORCH_CHECK(norm_w.numel() == MLG_VIT_EMBED && norm_b.numel() == MLG_VIT_EMBED, "norm_w / norm_b must be [768]");
+    TORCH_CHECK(norm_w.device() == tokens.device() && norm_b.device() == tokens.device(),
+                "tokens, norm_w and norm_b must be on one device");
+    const int64_t B = tokens.size(0), T = tokens.size(1);
+    int64_t grid = 0;
+    while (grid * grid + 1 < T) ++grid;
+    TORCH_CHECK(grid * grid + 1 == T, "tokens: ", T, " is not 1 + a square");
+    c10::DeviceGuard g(tokens.device());
+    Tensor out = at::empty({B, MLG_CRICA_ROWS, MLG_VIT_EMBED}, tokens.options());
+    check_rc(mlg_op_crica_pool(cp<float>(tokens), cp<float>(norm_w), cp<float>(norm_b), (int)B, (int)grid,
+                               (float)gem_p, mp<float>(out), stream_of(tokens)),
+             "mlg_op_crica_pool");
+    return out;
+}
+
+// pooled f32 [B, 14, 768] -> desc f32 [B, 10752]
+Tensor crica_encoder(const Tensor& pooled, at::TensorList head, double gem_p, int64_t group) {
+    want(pooled, at::kFloat, "pooled");
+    TORCH_CHECK(pooled.dim() == 3 && pooled.size(0) > 0 && pooled.size(0) <= MLG_CRICA_MAX_BATCH &&
+                    pooled.size(1) == MLG_CRICA_ROWS && pooled.size(2) == MLG_VIT_EMBED,
+                "pooled must be [B, 14, 768], B <= ", MLG_CRICA_MAX_BATCH);
+    const mlg_crica_weights cw = crica_weights(head, gem_p, pooled.device());
+    const int64_t B = pooled.size(0);
+    c10::DeviceGuard g(pooled.device());
+    Tensor desc = at::empty({B, MLG_CRICA_DIM}, pooled.options());
+    Tensor ws = workspace(MLG_CRICA_HEAD_WS_BYTES(B), pooled);
+    check_rc(mlg_op_crica_encoder(&cw, cp<float>(pooled), (int)B, (int)group, ws.data_ptr(), (size_t)ws.numel(),
+                                  mp<float>(desc), stream_of(pooled)),
+             "mlg_op_crica_encoder");
+    return desc;
+}
+
 // ---------------------------------------------------- LiDAR plane RANSAC
 std::tuple<Tensor, Tensor, Tensor> plane_ransac(const Tensor& pts, const Tensor& offsets, int64_t iterations,
                                                 int64_t seed, double threshold) {
@@ -742,6 +849,7 @@ void weights_check(std::string model, at::TensorList w) {
     union {
         mlg_vit_weights vit;
         mlg_salad_weights salad;
+        mlg_crica_weights crica;
         mlg_sp_weights sp;
         mlg_lg_weights lg;
         mlg_sg_weights sg;
@@ -753,6 +861,7 @@ void weights_check(std::string model, at::TensorList w) {
         const char *model, *what;
         const wt::Table& (*table)();
     } fixed[] = {{"salad", "salad", wt::salad_table},
+                 {"crica", "crica", wt::crica_table},
                  {"superpoint", "superpoint", wt::sp_table},
                  {"lightglue", "lightglue", wt::lg_table},
                  {"superglue", "superglue", wt::sg_table},
@@ -991,6 +1100,10 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("vlad(Tensor tokens, Tensor centers) -> (Tensor, Tensor)");
     m.def("anyloc_forward(Tensor frames, Tensor[] weights, Tensor centers, int image_size, int flags, int max_batch) -> Tensor");
     m.def("kmeans_step(Tensor tokens, Tensor(a!) centers, Tensor(b!) labels) -> (Tensor, Tensor)");
+    m.def("crica_forward(Tensor frames, Tensor[] weights, Tensor[] head, float gem_p, int image_size, int flags, int group, int max_batch, bool with_local) -> (Tensor, Tensor)");
+    m.def("vit_trunk(Tensor frames, Tensor[] weights, int image_size, int flags, int max_batch) -> Tensor");
+    m.def("crica_pool(Tensor tokens_prenorm, Tensor norm_w, Tensor norm_b, float gem_p) -> Tensor");
+    m.def("crica_encoder(Tensor pooled, Tensor[] head, float gem_p, int group) -> Tensor");
     m.def("loftr_features(Tensor frames, Tensor[] weights) -> (Tensor, Tensor)");
     m.def("loftr_pack_tails(Tensor[] weights) -> Tensor");
     m.def("loftr_coarse_layer(Tensor(a!) x, Tensor(b!) cat, Tensor[] weights, int layer, int fused, int nseg, int L) -> ()");
@@ -1042,6 +1155,10 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("vlad", &vlad);
     m.impl("anyloc_forward", &anyloc_forward);
     m.impl("kmeans_step", &kmeans_step);
+    m.impl("crica_forward", &crica_forward);
+    m.impl("vit_trunk", &vit_trunk);
+    m.impl("crica_pool", &crica_pool);
+    m.impl("crica_encoder", &crica_encoder);
     m.impl("loftr_features", &loftr_features);
     m.impl("loftr_pack_tails", &loftr_pack_tails);
     m.impl("loftr_coarse_layer", &loftr_coarse_layer);

@@ -147,6 +147,31 @@ inline const Table& salad_table() {
     });
 }
 
+// CricaVPR's cross-image encoder: 2 nn.TransformerEncoderLayer, GEMM weights [W_hi | W_lo]
+inline const Table& crica_table() {
+    return built_once([](Table& t) {
+        using W = mlg_crica_weights;
+        using L = mlg_crica_layer;
+        const int64_t E = MLG_VIT_EMBED, F = 2048;
+        for (int i = 0; i < 2; ++i) {
+            const size_t o = offsetof(W, layers) + i * sizeof(L);
+            const std::string p = at("layers", i) + ".";
+            WT_FIELD(t, o, p, L, in_w, BF16, 3 * E * 2 * E);
+            WT_FIELD(t, o, p, L, in_b, F32, 3 * E);
+            WT_FIELD(t, o, p, L, out_w, BF16, E * 2 * E);
+            WT_FIELD(t, o, p, L, out_b, F32, E);
+            WT_FIELD(t, o, p, L, ln1_g, F32, E);
+            WT_FIELD(t, o, p, L, ln1_b, F32, E);
+            WT_FIELD(t, o, p, L, fc1_w, BF16, F * 2 * E);
+            WT_FIELD(t, o, p, L, fc1_b, F32, F);
+            WT_FIELD(t, o, p, L, fc2_w, BF16, E * 2 * F);
+            WT_FIELD(t, o, p, L, fc2_b, F32, E);
+            WT_FIELD(t, o, p, L, ln2_g, F32, E);
+            WT_FIELD(t, o, p, L, ln2_b, F32, E);
+        }
+    });
+}
+
 inline const Table& sp_table() {
     return built_once([](Table& t) {
         using W = mlg_sp_weights;

@@ -20,6 +20,7 @@ OPS = ("vit_forward_into", "salad_forward", "knn_gate", "knn_query", "row_normal
        "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
        "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess", "vlad", "anyloc_forward", "kmeans_step",
+       "crica_forward", "vit_trunk", "crica_pool", "crica_encoder",
        "weights_check", "prof_enable", "prof_reset", "prof_read")
 
 
@@ -79,6 +80,12 @@ EXPORTS = {
     "mlg_kmeans_workspace_bytes": (c_size_t, [c_long, c_int]),
     "mlg_kmeans_step": (c_int, [c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),
+    "mlg_crica_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_int,
+                                  c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mlg_op_vit_trunk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_void_p,
+                                 c_size_t, c_void_p, c_void_p]),
+    "mlg_op_crica_pool": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "mlg_op_crica_encoder": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mlg_superpoint_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mlg_superpoint": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_float, c_int, c_int, c_int,
                                c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -5,8 +5,10 @@ behaviour as the reference; the compute runs on the mlgate HIP kernels:
 
   * CricaVPR -> DINOv2 ViT-B/14 + GeM on MI355X (mlgate.vit.VitB14); ONE forward per
     keyframe feeds both the descriptor and the local-feature cache (the reference runs
-    the same forward twice, place_recognition.py:765/777).
-  * AnyLoc   -> the same ViT at 518^2 with mean pooling and unswapped channels
+    the same forward twice, place_recognition.py:765/777); opt-in
+    (MLGATE_CRICAVPR_NATIVE=1) the 10752-dim descriptor the class declares, from the same
+    forward: mlgate.crica.
+  * AnyLoc  -> the same ViT at 518^2 with mean pooling and unswapped channels
     (place_recognition.py:467-505); opt-in (MLGATE_ANYLOC_NATIVE=1) the VLAD descriptor
     the class declares, over the same tokens: mlgate.anyloc.
   * retrieval (find_loop_closures / query / pairwise similarities / cross-correlation
@@ -467,6 +469,45 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
         self._model_loaded = False
         self._vit = None
         self._feature_cache = {}  # idx -> device float32 [1, 528, 768]
+        self.native = None  # None: MLGATE_CRICAVPR_NATIVE decides; True / False force it
+        self.cross_image_group = 1  # images of a call that attend to each other (native branch)
+        self._crica = None
+
+    def _native_selected(self):
+        return self.native if self.native is not None else os.environ.get("MLGATE_CRICAVPR_NATIVE") == "1"
+
+    def _native_engine(self):
+        """The CricaGPU engine when the native branch is selected, else None."""
+        if not self._native_selected():
+            return None
+        if self._crica is None or self._crica.group != int(self.cross_image_group):
+            if self.descriptor_dim != 10752:
+                raise ValueError(f"native CricaVPR produces 14 x 768 = 10752-dim descriptors, not "
+                                 f"{self.descriptor_dim}")
+            if self.backbone_name != 'dinov2_vitb14':
+                raise ValueError(f"{self.backbone_name}: only the dinov2_vitb14 backbone has MI355X kernels")
+            from .crica import CricaGPU, check_group
+            from .weights import resolve_crica_state_dict
+            group = check_group(self.cross_image_group)
+            if self._crica is not None:  # the group changed: the packed weights stay
+                self._crica.group = group
+                return self._crica
+            sd, source = resolve_crica_state_dict(self.pretrained_path)
+            if source.startswith('synthetic'):
+                warnings.warn("CricaVPR weights are not available offline; using seeded synthetic weights (set "
+                              "pretrained_path or MLGATE_CRICAVPR_WEIGHTS to a local CricaVPRNet checkpoint for "
+                              "real descriptors).")
+            self._crica = CricaGPU(sd, device=self.device, image_size=self._image_size,
+                                   max_batch=max(64, group), group=group)
+            self.feat_dim = 768
+            self._model_loaded = True
+        return self._crica
+
+    def _forward(self, images, with_local=False):
+        eng = self._native_engine()
+        if eng is None:
+            return super()._forward(images, with_local)
+        return eng.forward(_device_frames(images, eng.device), with_local=with_local)
 
     def extract_local_features(self, image: np.ndarray) -> np.ndarray:
         _, local = self._forward([image], with_local=True)

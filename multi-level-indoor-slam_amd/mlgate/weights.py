@@ -748,3 +748,93 @@ def resolve_vocabulary(path=None, num_clusters=64, seed=0):
     if path:
         return load_vocabulary(path, num_clusters), path
     return synthetic_vocabulary(num_clusters, seed), f"synthetic(seed={seed})"
+
+
+# ----------------------------------------------------------------- CricaVPR
+# Lu-Feng/CricaVPR CricaVPRNet state dict (CricaVPR's native branch, place_recognition.py:
+# 528-578): the DINOv2 ViT-B/14 backbone under ``backbone.``, the GeM exponent
+# ``aggregation.1.p`` and ``encoder`` = nn.TransformerEncoder(d_model 768, nhead 16,
+# dim_feedforward 2048, gelu, 2 layers).  (``encoder_layer.*``, the template the two layers
+# were copied from, is not used by the forward and is ignored.)
+CRICA_LAYERS, CRICA_HEADS, CRICA_FF, CRICA_ROWS = 2, 16, 2048, 14
+CRICA_DIM = CRICA_ROWS * EMBED
+CRICA_UNUSED_BACKBONE_KEYS = ("mask_token",)  # a hub parameter the forward never reads
+
+
+def crica_head_shapes():
+    shapes = {"aggregation.1.p": (1,)}
+    for i in range(CRICA_LAYERS):
+        p = f"encoder.layers.{i}."
+        shapes.update({p + "self_attn.in_proj_weight": (3 * EMBED, EMBED), p + "self_attn.in_proj_bias": (3 * EMBED,),
+                       p + "self_attn.out_proj.weight": (EMBED, EMBED), p + "self_attn.out_proj.bias": (EMBED,),
+                       p + "linear1.weight": (CRICA_FF, EMBED), p + "linear1.bias": (CRICA_FF,),
+                       p + "linear2.weight": (EMBED, CRICA_FF), p + "linear2.bias": (EMBED,),
+                       p + "norm1.weight": (EMBED,), p + "norm1.bias": (EMBED,),
+                       p + "norm2.weight": (EMBED,), p + "norm2.bias": (EMBED,)})
+    return shapes
+
+
+def crica_keys():
+    return ["backbone." + k for k in hub_keys()] + list(crica_head_shapes())
+
+
+def crica_head_state_dict(seed=0):
+    """The seeded head alone: Xavier-normal linear layers, LayerNorms near identity, p = 3."""
+    rng = np.random.default_rng(seed + 11)
+    sd = {}
+    for k, shp in crica_head_shapes().items():
+        if k == "aggregation.1.p":
+            sd[k] = np.full(shp, 3.0, np.float32)
+        elif ".norm" in k:
+            sd[k] = rng.standard_normal(shp, dtype=np.float32) * np.float32(0.1 if k.endswith("weight") else 0.05)
+            if k.endswith("weight"):
+                sd[k] += np.float32(1.0)
+        elif len(shp) == 1:
+            sd[k] = rng.standard_normal(shp, dtype=np.float32) * np.float32(0.02)
+        else:
+            sd[k] = rng.standard_normal(shp, dtype=np.float32) * np.float32(np.sqrt(2.0 / (shp[0] + shp[1])))
+    return sd
+
+
+def crica_state_dict(seed=0):
+    """Seeded float32 weights with CricaVPRNet's key names and shapes: the synthetic trunk
+    under ``backbone.`` plus a seeded head."""
+    sd = {"backbone." + k: v for k, v in synthetic_state_dict(seed).items()}
+    sd.update(crica_head_state_dict(seed))
+    return sd
+
+
+def load_crica_state_dict(path):
+    """CricaVPRNet checkpoint from a local file, weights only: a plain state dict or one under
+    'model_state_dict' / 'state_dict', with or without DataParallel's 'module.' prefix.
+    A backbone with tensors the hub ViT-B/14 does not have (upstream's per-block adapters,
+    whose layout cannot be checked here) is refused by name, never silently dropped."""
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    for nest in ("model_state_dict", "state_dict"):
+        if nest in sd and isinstance(sd[nest], dict):
+            sd = sd[nest]
+            break
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    known = {"backbone." + k for k in hub_keys()} | {"backbone." + k for k in CRICA_UNUSED_BACKBONE_KEYS}
+    foreign = [k for k in sd if k.startswith("backbone.") and k not in known]
+    if foreign:
+        raise ValueError(f"checkpoint {path}: {len(foreign)} backbone tensors are not part of dinov2_vitb14, the "
+                         f"first is '{foreign[0]}'; a backbone with adapters is not supported")
+    missing = [k for k in crica_keys() if k not in sd]
+    if missing:
+        raise KeyError(f"checkpoint {path} lacks CricaVPR keys, e.g. {missing[:3]}")
+    out = {"backbone." + k: sd["backbone." + k].float().cpu().numpy() for k in hub_keys()}
+    for k, shp in crica_head_shapes().items():
+        a = sd[k].float().cpu().numpy()
+        if a.size != int(np.prod(shp)):
+            raise ValueError(f"checkpoint {path}: '{k}' has shape {tuple(a.shape)}, expected {shp}")
+        out[k] = a.reshape(shp)
+    return out
+
+
+def resolve_crica_state_dict(path=None, seed=0):
+    path = path or os.environ.get("MLGATE_CRICAVPR_WEIGHTS")
+    if path:
+        return load_crica_state_dict(path), path
+    return crica_state_dict(seed), f"synthetic(seed={seed})"
