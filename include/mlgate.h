@@ -34,7 +34,7 @@ extern "C" {
 #define MLG_VIT_EMBED 768
 #define MLG_VIT_PATCH_K 768 /* 3*14*14 = 588 patch inputs, zero-padded to 12 K-tiles of 64 */
 
-/* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_salad_weights, mlg_vlad_vocab,
+/* Struct arguments.  Every struct an entry point takes (mlg_vit_weights, mlg_dino_weights, mlg_salad_weights, mlg_vlad_vocab,
  * mlg_crica_weights, mlg_rn_weights, mlg_mixvpr_weights, mlg_sp_weights, mlg_lg_weights, mlg_sg_weights, mlg_loftr_weights,
  * mlg_orb_params) begins with a head: struct_size = sizeof(the struct) and abi_version =
  * MLG_ABI_VERSION, both set by initialising it with MLG_STRUCT_INIT(type).  A struct whose
@@ -112,6 +112,53 @@ size_t mlg_vit_workspace_bytes(int batch, int image_size);
 int mlg_vit_forward(const mlg_vit_weights* w, const uint8_t* frames, int batch, int H, int W, int C,
                     long frame_stride, int image_size, int flags, void* workspace, size_t workspace_bytes,
                     float* desc_out, float* local_out, void* stream);
+
+/* ------------------------------------------------- DINOv2 ViT-S / B / L-14 --
+ * The same forward for the three hub networks the reference's `backbone` argument names
+ * (place_recognition.py:536, :594-602):
+ *   dinov2_vits14  embed  384  depth 12  heads  6
+ *   dinov2_vitb14  embed  768  depth 12  heads 12
+ *   dinov2_vitl14  embed 1024  depth 24  heads 16
+ * (heads of 64, MLP 4 * embed, patch 14; everything else as mlg_vit_weights).  Tensor
+ * layouts are mlg_vit_weights' with 768 read as `embed`; `blocks` is a HOST array of
+ * `depth` mlg_vit_block (read during the call only).
+ * MLG_VIT_SPLIT packing at embed 384: the split GEMM runs 256-column tiles, so the four
+ * GEMM weights whose row count is 128 past a multiple of 256 carry zero rows up to the
+ * next multiple: patch_w [512, 2 * MLG_VIT_PATCH_K], qkv_w [1280, 768], proj_w [512, 768],
+ * fc2_w [512, 3072] (fc1_w stays [1536, 768]); biases, LayerScale and outputs keep their
+ * true widths.  The plain packing has no padding at any width. */
+#define MLG_DINO_MAX_DEPTH 24
+typedef struct mlg_dino_weights {
+    uint32_t struct_size, abi_version; /* MLG_STRUCT_INIT(mlg_dino_weights) */
+    int embed, depth, heads;           /* one row of the table above */
+    const uint16_t* patch_w;           /* [embed, MLG_VIT_PATCH_K], k = c*196 + ky*14 + kx */
+    const float* patch_b;
+    const float* cls;                  /* [embed] */
+    const float* pos;                  /* [1 + P, embed] */
+    const mlg_vit_block* blocks;       /* host array of `depth` */
+    const float *norm_w, *norm_b;
+    int packing; /* 0 or MLG_VIT_SPLIT, must match the flag */
+} mlg_dino_weights;
+
+/* mlg_vit_workspace_bytes for a network of width `embed`; 0 for a width other than 384 /
+ * 768 / 1024 (at 768: mlg_vit_workspace_bytes(batch, image_size)).  The layout, every buffer
+ * rounded up to 256 bytes, with rows = batch * T, T = 1 + (S/14)^2, Tpad = T rounded up to 64:
+ *   patches bf16 [batch * (T - 1), 2 * MLG_VIT_PATCH_K]   x f32 [rows, embed]
+ *   xn, o bf16 [rows, 2 * embed]   q, k, vt bf16 [2, embed / 64, batch * Tpad, 64]
+ *   h bf16 [rows, 8 * embed]   GeM partials f32 [batch, 8, embed]   tasks int32 [5 * batch]
+ * (tests/test_dino_backbones_cpu.py restates it; the sizes recorded in
+ * tests/golden/workspace_sizes.json are those of the fixed-width queries.) */
+extern size_t mlg_dino_workspace_bytes(int embed, int batch, int image_size);
+
+/* mlg_vit_forward (same arguments and flags) for one of the three networks.  desc_out:
+ * float32 [batch, embed].  local_out: float32 [batch, (S/14)^2 - 1, embed] or NULL.
+ * MLG_EINVAL, before any GPU call, for a struct head that disagrees, a configuration that
+ * is not a row of the table (heads * 64 != embed, another depth for the width, blocks
+ * NULL), a packing that disagrees with the flag, or a NULL frames / workspace / desc_out;
+ * MLG_ENOMEM for a workspace below mlg_dino_workspace_bytes(embed, batch, image_size). */
+int mlg_dino_forward(const mlg_dino_weights* w, const uint8_t* frames, int batch, int H, int W, int C,
+                     long frame_stride, int image_size, int flags, void* workspace, size_t workspace_bytes,
+                     float* desc_out, float* local_out, void* stream);
 
 /* ------------------------------------------------------------------- SALAD --
  * SALAD's native branch (place_recognition.py:357-368, 380-391): serizba/salad's

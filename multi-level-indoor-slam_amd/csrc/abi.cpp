@@ -1,4 +1,4 @@
-// Public C ABI (include/mlgate.h): ViT-B/14 forward orchestration, kNN gate,
+// Public C ABI (include/mlgate.h): DINOv2 ViT forward orchestration, kNN gate,
 // op-level entry points and HIP-event profiling.
 #include <hip/hip_runtime.h>
 
@@ -18,12 +18,33 @@ namespace {
 
 constexpr int PATCH = 14;
 
+// E: the token width of the network (384 ViT-S, 768 ViT-B, 1024 ViT-L); heads of 64, MLP 4 E
 struct VitGeom {
-    int B, S, grid, P, T, Tpad;
-    explicit VitGeom(int b, int s) : B(b), S(s), grid(s / PATCH), P(grid * grid), T(grid * grid + 1) {
+    int B, S, grid, P, T, Tpad, E, heads;
+    explicit VitGeom(int b, int s, int e = MLG_VIT_EMBED)
+        : B(b), S(s), grid(s / PATCH), P(grid * grid), T(grid * grid + 1), E(e), heads(e / 64) {
         Tpad = (T + 63) / 64 * 64;
     }
 };
+
+// depth of the hub network of width E, 0: no such network
+int dino_depth(int E) { return E == 384 || E == 768 ? 12 : E == 1024 ? 24 : 0; }
+
+// The trunk's view of a weight struct (mlg_vit_weights: 12 blocks inline; mlg_dino_weights: a
+// host array of `depth`)
+struct VitNet {
+    const uint16_t* patch_w;
+    const float *patch_b, *cls, *pos;
+    const mlg_vit_block* blocks;
+    int depth;
+    const float *norm_w, *norm_b;
+};
+VitNet net_of(const mlg_vit_weights* w) {
+    return {w->patch_w, w->patch_b, w->cls, w->pos, w->blocks, MLG_VIT_DEPTH, w->norm_w, w->norm_b};
+}
+VitNet net_of(const mlg_dino_weights* w) {
+    return {w->patch_w, w->patch_b, w->cls, w->pos, w->blocks, w->depth, w->norm_w, w->norm_b};
+}
 
 // Operand buffers are sized for the split-bf16 forward (MLG_VIT_SPLIT): [hi | lo] rows
 // for patches / xn / o / h, and q / k / vt as a hi plane followed by a lo plane (lo_elems
@@ -38,19 +59,19 @@ struct VitWorkspace {
 // the ViT buffers at the carver's position (AnyLoc carves its own behind them)
 VitWorkspace vit_take(WsCarver& c, const VitGeom& g) {
     const size_t rows = (size_t)g.B * g.T;
-    const size_t heads = (size_t)g.B * 12;
+    const size_t heads = (size_t)g.B * g.heads, E = g.E;
     VitWorkspace w{};
     w.patches = c.take<bf16_t>((size_t)g.B * g.P * MLG_VIT_PATCH_K * 2);
-    w.x = c.take<float>(rows * 768);
-    w.xn = c.take<bf16_t>(rows * 768 * 2);
+    w.x = c.take<float>(rows * E);
+    w.xn = c.take<bf16_t>(rows * E * 2);
     w.lo_elems = heads * g.Tpad * 64;
     w.q_bytes = w.vt_bytes = 2 * w.lo_elems * sizeof(bf16_t);
     w.q = c.take<bf16_t>(2 * w.lo_elems);
     w.k = c.take<bf16_t>(2 * w.lo_elems);
     w.vt = c.take<bf16_t>(2 * w.lo_elems);
-    w.o = c.take<bf16_t>(rows * 768 * 2);
-    w.h = c.take<bf16_t>(rows * 3072 * 2);
-    w.partial = c.take<float>(mlg_gem_partial_bytes(g.B) / sizeof(float));
+    w.o = c.take<bf16_t>(rows * E * 2);
+    w.h = c.take<bf16_t>(rows * 4 * E * 2);
+    w.partial = c.take<float>(mlg_gem_partial_bytes(g.B, g.E) / sizeof(float));
     w.tasks = c.take<int32_t>((size_t)g.B * 5);
     return w;
 }
@@ -220,76 +241,92 @@ size_t mlg_vit_workspace_bytes(int batch, int image_size) {
 
 }  // extern "C"
 
-// Preprocess + patch embedding + the 12 blocks; leaves the residual stream in ws->x.
+// Preprocess + patch embedding + the blocks; leaves the residual stream in ws->x.
 // split: the MLG_VIT_SPLIT forward (weights packed [W_hi | W_lo], 2x the reduction dimension).
-static int vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, const VitGeom& g, int H, int W, int C,
+static int vit_trunk(const VitNet& w, const uint8_t* frames, const VitGeom& g, int H, int W, int C,
                      long frame_stride, int swap_rb, const VitWorkspace& ws, hipStream_t s, int split = 0) {
-    const int M = g.B * g.T;
+    const int M = g.B * g.T, E = g.E, F = 4 * g.E;
     MLG_TRY(mlg_preprocess_patches(frames, g.B, H, W, C, frame_stride, g.S, MLG_VIT_PATCH_K, swap_rb, ws.patches, s,
                                    split));
     if (split)
-        MLG_TRY(mlg_gemm_patch_split(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P,
-                                     MLG_VIT_PATCH_K, s));
+        MLG_TRY(mlg_gemm_patch_split(ws.patches, w.patch_w, w.patch_b, w.pos, ws.x, g.B * g.P, g.P,
+                                     MLG_VIT_PATCH_K, s, E));
     else
-        MLG_TRY(mlg_gemm_patch(ws.patches, w->patch_w, w->patch_b, w->pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K,
-                               s));
-    MLG_TRY(mlg_cls_rows(ws.x, w->cls, w->pos, g.B, g.T, s));
+        MLG_TRY(mlg_gemm_patch(ws.patches, w.patch_w, w.patch_b, w.pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K, s, E));
+    MLG_TRY(mlg_cls_rows(ws.x, w.cls, w.pos, g.B, g.T, s, E));
     // padded key columns of V^T must be finite (masked keys multiply them by p = 0); padded
     // query rows are never stored but are zeroed too, so no lane computes on stale bits
     if (hipMemsetAsync(ws.vt, 0, ws.vt_bytes, s) != hipSuccess) return MLG_EHIP;
     if (hipMemsetAsync(ws.q, 0, ws.q_bytes, s) != hipSuccess) return MLG_EHIP;
 
     const double mul = split ? 3.0 : 1.0;  // MFMA products per algorithmic product
-    for (int l = 0; l < MLG_VIT_DEPTH && split; ++l) {
-        const mlg_vit_block& bl = w->blocks[l];
-        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
+    for (int l = 0; l < w.depth && split; ++l) {
+        const mlg_vit_block& bl = w.blocks[l];
+        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s, E));
         {
-            MlgProfScope p(2, s, mul * 2.0 * M * 2304 * 768);
-            MLG_TRY(mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems, s));
+            MlgProfScope p(2, s, mul * 2.0 * M * (3.0 * E) * E);
+            MLG_TRY(mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems, s, E));
         }
         {
-            MlgProfScope p(4, s, mul * 4.0 * g.B * 12 * (double)g.T * g.T * 64);
-            MLG_TRY(mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s));
+            MlgProfScope p(4, s, mul * 4.0 * g.B * g.heads * (double)g.T * g.T * 64);
+            MLG_TRY(mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s, g.heads));
         }
         {
-            MlgProfScope p(3, s, mul * 2.0 * M * 768 * 768);
-            MLG_TRY(mlg_gemm_residual_split(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
+            MlgProfScope p(3, s, mul * 2.0 * M * (double)E * E);
+            MLG_TRY(mlg_gemm_residual_split(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, E, E, s));
         }
-        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
+        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s, E));
         {
-            MlgProfScope p(0, s, mul * 2.0 * M * 3072 * 768);
-            MLG_TRY(mlg_gemm_bias_gelu_split(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
-        }
-        {
-            MlgProfScope p(1, s, mul * 2.0 * M * 768 * 3072);
-            MLG_TRY(mlg_gemm_residual_split(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
-        }
-    }
-    for (int l = 0; l < MLG_VIT_DEPTH && !split; ++l) {
-        const mlg_vit_block& bl = w->blocks[l];
-        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s));
-        {
-            MlgProfScope p(2, s, 2.0 * M * 2304 * 768);
-            MLG_TRY(mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s));
+            MlgProfScope p(0, s, mul * 2.0 * M * (double)F * E);
+            MLG_TRY(mlg_gemm_bias_gelu_split(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, F, E, s));
         }
         {
-            MlgProfScope p(4, s, 4.0 * g.B * 12 * (double)g.T * g.T * 64);
-            MLG_TRY(mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s));
-        }
-        {
-            MlgProfScope p(3, s, 2.0 * M * 768 * 768);
-            MLG_TRY(mlg_gemm_residual(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, 768, 768, s));
-        }
-        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s));
-        {
-            MlgProfScope p(0, s, 2.0 * M * 3072 * 768);
-            MLG_TRY(mlg_gemm_bias_gelu_bf16(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, 3072, 768, s));
-        }
-        {
-            MlgProfScope p(1, s, 2.0 * M * 768 * 3072);
-            MLG_TRY(mlg_gemm_residual(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, 768, 3072, s));
+            MlgProfScope p(1, s, mul * 2.0 * M * (double)E * F);
+            MLG_TRY(mlg_gemm_residual_split(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, E, F, s));
         }
     }
+    for (int l = 0; l < w.depth && !split; ++l) {
+        const mlg_vit_block& bl = w.blocks[l];
+        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s, E));
+        {
+            MlgProfScope p(2, s, 2.0 * M * (3.0 * E) * E);
+            MLG_TRY(mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s, E));
+        }
+        {
+            MlgProfScope p(4, s, 4.0 * g.B * g.heads * (double)g.T * g.T * 64);
+            MLG_TRY(mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s, g.heads));
+        }
+        {
+            MlgProfScope p(3, s, 2.0 * M * (double)E * E);
+            MLG_TRY(mlg_gemm_residual(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, E, E, s));
+        }
+        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s, E));
+        {
+            MlgProfScope p(0, s, 2.0 * M * (double)F * E);
+            MLG_TRY(mlg_gemm_bias_gelu_bf16(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, F, E, s));
+        }
+        {
+            MlgProfScope p(1, s, 2.0 * M * (double)E * F);
+            MLG_TRY(mlg_gemm_residual(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, E, F, s));
+        }
+    }
+    return MLG_OK;
+}
+
+// What mlg_vit_forward and mlg_dino_forward share once their struct is checked
+static int vit_forward_run(const VitNet& net, int packing, const VitGeom& g, const uint8_t* frames, int H, int W,
+                           int C, long frame_stride, int flags, void* workspace, size_t workspace_bytes,
+                           float* desc_out, float* local_out, void* stream) {
+    // the split forward reads 2x-wide weight rows: plain weights with the flag would be read out of bounds
+    if (packing != ((flags & MLG_VIT_SPLIT) ? MLG_VIT_SPLIT : 0)) return MLG_EINVAL;
+    VitWorkspace ws;
+    if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
+    hipStream_t s = (hipStream_t)stream;
+    const int swap_rb = (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1;
+    const int mean_pool = (flags & MLG_VIT_POOL_MEAN) ? 1 : 0;
+    MLG_TRY(vit_trunk(net, frames, g, H, W, C, frame_stride, swap_rb, ws, s, (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    MLG_TRY(mlg_final_norm_gem(ws.x, net.norm_w, net.norm_b, local_out, ws.partial, desc_out, g.B, g.T, mean_pool, s,
+                               g.E));
     return MLG_OK;
 }
 
@@ -300,17 +337,26 @@ int mlg_vit_forward(const mlg_vit_weights* w, const uint8_t* frames, int batch, 
                     float* desc_out, float* local_out, void* stream) {
     if (!mlg_head_ok(w, MLG_ABI_VERSION) || !frames || !workspace || !desc_out || batch <= 0 || image_size % PATCH)
         return MLG_EINVAL;
-    // the split forward reads 2x-wide weight rows: plain weights with the flag would be read out of bounds
-    if (w->packing != ((flags & MLG_VIT_SPLIT) ? MLG_VIT_SPLIT : 0)) return MLG_EINVAL;
-    const VitGeom g(batch, image_size);
-    VitWorkspace ws;
-    if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    const int swap_rb = (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1;
-    const int mean_pool = (flags & MLG_VIT_POOL_MEAN) ? 1 : 0;
-    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, swap_rb, ws, s, (flags & MLG_VIT_SPLIT) ? 1 : 0));
-    MLG_TRY(mlg_final_norm_gem(ws.x, w->norm_w, w->norm_b, local_out, ws.partial, desc_out, g.B, g.T, mean_pool, s));
-    return MLG_OK;
+    return vit_forward_run(net_of(w), w->packing, VitGeom(batch, image_size), frames, H, W, C, frame_stride, flags,
+                           workspace, workspace_bytes, desc_out, local_out, stream);
+}
+
+size_t mlg_dino_workspace_bytes(int embed, int batch, int image_size) {
+    if (!dino_depth(embed) || batch <= 0 || image_size <= 0 || image_size % PATCH) return 0;
+    return carve(VitGeom(batch, image_size, embed), nullptr, nullptr);
+}
+
+int mlg_dino_forward(const mlg_dino_weights* w, const uint8_t* frames, int batch, int H, int W, int C,
+                     long frame_stride, int image_size, int flags, void* workspace, size_t workspace_bytes,
+                     float* desc_out, float* local_out, void* stream) {
+    if (!mlg_head_ok(w, MLG_ABI_VERSION) || !frames || !workspace || !desc_out || batch <= 0 || image_size <= 0 ||
+        image_size % PATCH)
+        return MLG_EINVAL;
+    // one of the three hub networks: width, its depth, heads of 64
+    if (!dino_depth(w->embed) || w->depth != dino_depth(w->embed) || w->heads * 64 != w->embed || !w->blocks)
+        return MLG_EINVAL;
+    return vit_forward_run(net_of(w), w->packing, VitGeom(batch, image_size, w->embed), frames, H, W, C, frame_stride,
+                           flags, workspace, workspace_bytes, desc_out, local_out, stream);
 }
 
 size_t mlg_salad_workspace_bytes(int batch, int image_size) {
@@ -332,7 +378,7 @@ int mlg_salad_forward(const mlg_vit_weights* w, const mlg_salad_weights* sw, con
     hipStream_t s = (hipStream_t)stream;
     const int M = g.B * g.T;
     // SALAD._preprocess keeps the stored channel order (place_recognition.py:395-397)
-    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, /*swap_rb=*/0, ws, s));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, /*swap_rb=*/0, ws, s));
     MLG_TRY(mlg_layernorm_bf16(ws.x, w->norm_w, w->norm_b, ws.xn, M, s));  // backbone norm_layer, all tokens
     MLG_TRY(mlg_gemm_bias_relu_bf16(ws.xn, 768, sw->w1, sw->b1, ws.h, 1024, 1024, M, 1024, 768, s));
     float* y = ws.x;  // [M, 256]
@@ -366,7 +412,7 @@ int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, co
     AnylocBufs b;
     if (anyloc_carve(g, vocab->num_clusters, workspace, &b) > workspace_bytes) return MLG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s,
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s,
                       (flags & MLG_VIT_SPLIT) ? 1 : 0));
     MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, b.tokens, b.vit.partial, b.pooled, g.B, g.T,
                                /*mean_pool=*/1, s));
@@ -405,7 +451,7 @@ int mlg_crica_forward(const mlg_vit_weights* w, const mlg_crica_weights* cw, con
     if (!need) return MLG_EINVAL;
     if (need > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s, 1));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s, 1));
     MLG_TRY(mlg_crica_pool_run(b.vit.x, w->norm_w, w->norm_b, g.B, g.grid, cw->gem_p, b.pooled, s));
     if (local_out_or_null)  // the rerank cache: mlg_vit_forward's local features from this forward
         MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, local_out_or_null, b.vit.partial, b.gem, g.B, g.T,
@@ -421,7 +467,7 @@ int mlg_op_vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, int B, int
     VitWorkspace ws;
     if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(w, frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s, 1));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s, 1));
     if (hipMemcpyAsync(tokens_prenorm, ws.x, (size_t)g.B * g.T * 768 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
         hipSuccess)
         return MLG_EHIP;

@@ -711,30 +711,32 @@ extern "C" int mlg_dbg_att_trace(void* host, size_t bytes) {
 }
 
 int mlg_attention(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int T, int Tpad,
-                  int32_t* task_ws, hipStream_t s) {
-    if (B <= 0 || T <= 0 || Tpad % 64 || Tpad < T || !task_ws || (long)B * Tpad * 64 >= (1L << 31)) return MLG_EINVAL;
+                  int32_t* task_ws, hipStream_t s, int heads) {
+    if (B <= 0 || T <= 0 || Tpad % 64 || Tpad < T || !task_ws || (long)B * Tpad * 64 >= (1L << 31) || heads <= 0)
+        return MLG_EINVAL;
     int4* tasks = reinterpret_cast<int4*>(task_ws);
     int* out_off = task_ws + 4 * B;
     hipLaunchKernelGGL(k_vit_tasks, dim3(1), dim3(256), 0, s, tasks, out_off, B, T, Tpad);
     MLG_LAUNCH_CHECK();
-    return varlen_launch<true>(Q, K, Vt, O, 768, B * Tpad, 12, tasks, out_off, B, T, s);
+    return varlen_launch<true>(Q, K, Vt, O, 64 * heads, B * Tpad, heads, tasks, out_off, B, T, s);
 }
 
 // Split-bf16 ViT attention (MLG_VIT_SPLIT): Q, K, Vt hi planes with the lo planes
-// lo_off elements further; O rows of 1536 = [hi | lo].  MLG_ATTN_SPLIT_WAVES: 4 (64 queries
+// lo_off elements further; O rows of 2 * 64 heads = [hi | lo].  MLG_ATTN_SPLIT_WAVES: 4 (64 queries
 // per wave, one wave per SIMD: 288 registers) or 8 (32 per wave, two per SIMD).
 #ifndef MLG_ATTN_SPLIT_WAVES
 #define MLG_ATTN_SPLIT_WAVES 8
 #endif
 int mlg_attention_split(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int T, int Tpad,
-                        size_t lo_off, int32_t* task_ws, hipStream_t s) {
-    if (B <= 0 || T <= 0 || Tpad % 64 || Tpad < T || !task_ws || (long)B * Tpad * 64 >= (1L << 31)) return MLG_EINVAL;
+                        size_t lo_off, int32_t* task_ws, hipStream_t s, int heads) {
+    if (B <= 0 || T <= 0 || Tpad % 64 || Tpad < T || !task_ws || (long)B * Tpad * 64 >= (1L << 31) || heads <= 0)
+        return MLG_EINVAL;
     int4* tasks = reinterpret_cast<int4*>(task_ws);
     int* out_off = task_ws + 4 * B;
     hipLaunchKernelGGL(k_vit_tasks, dim3(1), dim3(256), 0, s, tasks, out_off, B, T, Tpad);
     MLG_LAUNCH_CHECK();
-    return varlen_launch<true, true, MLG_ATTN_SPLIT_WAVES>(Q, K, Vt, O, 1536, B * Tpad, 12, tasks, out_off, B, T, s,
-                                                          lo_off, 768);
+    return varlen_launch<true, true, MLG_ATTN_SPLIT_WAVES>(Q, K, Vt, O, 128 * heads, B * Tpad, heads, tasks, out_off, B,
+                                                          T, s, lo_off, 64 * heads);
 }
 
 // LightGlue: MLG_ATTN_LG_WAVES = 4 (64 queries per wave; two workgroups per CU give two

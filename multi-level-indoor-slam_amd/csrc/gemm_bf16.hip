@@ -212,14 +212,17 @@ struct EpiResidual {  // X += gamma * (acc + b)   (attn.proj / mlp.fc2 + LayerSc
     }
 };
 
-// qkv -> Q, K bf16 [12][B * Tpad][64] and V^T bf16 tiled [12][B * Tpad / 64][64 d][64 keys]
-// (the layouts k_attention_varlen reads; image b is the segment b * Tpad of each head)
+// qkv -> Q, K bf16 [E / 64][B * Tpad][64] and V^T bf16 tiled [E / 64][B * Tpad / 64][64 d][64 keys]
+// (the layouts k_attention_varlen reads; image b is the segment b * Tpad of each head).  E, the
+// ViT width, is a template constant so that n / E strength-reduces; E % 64 == 0, so a wave's
+// 64 columns are one head of one of q / k / v.
+template <int E>
 struct EpiQKV {
     bf16_t* Q; bf16_t* K; bf16_t* Vt; const float* bias; int T, Tpad, Np;
     __device__ void operator()(int m, int n, const f32x4& v) const {
         const float4 b = *reinterpret_cast<const float4*>(bias + n);
         const int bi = m / T, t = m - bi * T;
-        const int which = n / 768, c = n - which * 768, h = c >> 6, d = c & 63;
+        const int which = n / E, c = n - which * E, h = c >> 6, d = c & 63;
         const size_t key = (size_t)bi * Tpad + t;
         if (which < 2) {
             uint2 o;
@@ -237,6 +240,7 @@ struct EpiQKV {
 };
 
 // EpiQKV for the split forward: hi planes as EpiQKV, lo planes lo_off elements further
+template <int E>
 struct EpiQKVSplit {
     bf16_t* Q; bf16_t* K; bf16_t* Vt; const float* bias; int T, Tpad, Np; size_t lo_off;
     struct Col { float4 b; };
@@ -251,17 +255,17 @@ struct EpiQKVSplit {
     // staged form (k_gemm256s) for the Q / K waves (a wave's 64 columns are one head of one
     // of q, k, v): whole 128-B token rows of the head-major planes; V^T keeps apply
     static constexpr int STAGED = 1;
-    __device__ bool staged_wave(int n) const { return n < 2 * 768; }
+    __device__ bool staged_wave(int n) const { return n < 2 * E; }
     __device__ void stage2(const f32x4& v, const Col& c, uint2& h, uint2& l) const {
         split_bf16x4(v[0] + c.b.x, v[1] + c.b.y, v[2] + c.b.z, v[3] + c.b.w, h, l);
     }
     __device__ void put(int, int n, int plane, size_t key, const uint4& dd) const {
-        const int which = n / 768, c = n - which * 768, h = c >> 6, d = c & 63;
+        const int which = n / E, c = n - which * E, h = c >> 6, d = c & 63;
         *reinterpret_cast<uint4*>((which == 0 ? Q : K) + ((size_t)h * Np + key) * 64 + d + (plane ? lo_off : 0)) = dd;
     }
     __device__ void apply(int, int n, const f32x4& v, const Col& cd, const Row& rw, const Pre&) const {
         const float4 b = cd.b;
-        const int which = n / 768, c = n - which * 768, h = c >> 6, d = c & 63;
+        const int which = n / E, c = n - which * E, h = c >> 6, d = c & 63;
         const size_t key = rw.key;
         uint2 hi, lo;
         split_bf16x4(v[0] + b.x, v[1] + b.y, v[2] + b.z, v[3] + b.w, hi, lo);
@@ -393,7 +397,8 @@ struct EpiConvUp {
     }
 };
 
-struct EpiPatch {  // patch tokens: X[b, 1 + p, :] = acc + b + pos[1 + p]
+template <int E>
+struct EpiPatch {  // patch tokens: X[b, 1 + p, :] = acc + b + pos[1 + p], rows of E
     float* X; const float* bias; const float* pos; int P;  // P = patches per image
     struct Col { float4 b; };
     struct Row { int bi, p; };
@@ -404,11 +409,11 @@ struct EpiPatch {  // patch tokens: X[b, 1 + p, :] = acc + b + pos[1 + p]
         return {bi, m - bi * P};
     }
     __device__ Pre pre(int, int n, const Col&, const Row& r) const {
-        return {*reinterpret_cast<const float4*>(pos + (size_t)(1 + r.p) * 768 + n)};
+        return {*reinterpret_cast<const float4*>(pos + (size_t)(1 + r.p) * E + n)};
     }
     __device__ void apply(int, int n, const f32x4& v, const Col& c, const Row& r, const Pre& pq) const {
         const float4 b = c.b, q = pq.q;
-        *reinterpret_cast<float4*>(X + ((size_t)r.bi * (P + 1) + 1 + r.p) * 768 + n) =
+        *reinterpret_cast<float4*>(X + ((size_t)r.bi * (P + 1) + 1 + r.p) * E + n) =
             make_float4(v[0] + b.x + q.x, v[1] + b.y + q.y, v[2] + b.z + q.z, v[3] + b.w + q.w);
     }
     __device__ void operator()(int m, int n, const f32x4& v) const {
@@ -416,6 +421,16 @@ struct EpiPatch {  // patch tokens: X[b, 1 + p, :] = acc + b + pos[1 + p]
         const Row r = row(m);
         apply(m, n, v, c, r, pre(m, n, c, r));
     }
+};
+
+// A split GEMM whose N is 128 past a multiple of 256 (k_gemm256s, ViT-S): W carries zero rows up
+// to the next multiple of 256 and the kernel runs whole 256-column tiles; a wave owns 64 columns
+// and nvalid % 64 == 0, so a wave is either wholly inside the nvalid columns or wholly on the
+// padding, and the padding waves skip their epilogue (no bias / residual read, no store).
+template <class Epi>
+struct EpiTail : Epi {
+    static constexpr bool TAIL = true;
+    int nvalid;
 };
 
 // ------------------------------------------------- pieces every kernel shares
@@ -928,6 +943,17 @@ struct staged_of { static constexpr int value = 0; };
 template <class E>
 struct staged_of<E, std::void_t<decltype(E::STAGED)>> { static constexpr int value = E::STAGED; };
 
+// EpiTail: the wave columns at or past epi.nvalid skip the epilogue
+template <class E, class = void>
+struct tail_of { static constexpr bool value = false; };
+template <class E>
+struct tail_of<E, std::void_t<decltype(E::TAIL)>> { static constexpr bool value = E::TAIL; };
+template <class Epi>
+__device__ __forceinline__ bool tail_dead(const Epi& epi, int nw) {
+    if constexpr (tail_of<Epi>::value) return nw >= epi.nvalid;
+    else return false;
+}
+
 // s_setprio(1) / (0) around each MFMA cluster of k_gemm256s: hipcc then keeps the cluster
 // between its barriers (about -1 % on qkv / proj / fc2, profiles/r04aq_ab_split_gemm_setprio.txt)
 template <class Epi>
@@ -1176,7 +1202,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
         // stores cost a third of the fc1 GEMM (profiles/r04af_split_gemm_epilogue_probe.txt).
         if constexpr (STG == 1) {
             const int nw = n0 + wn * 64;
-            if (epi.staged_wave(nw)) {
+            if (tail_dead(epi, nw)) {
+                // a wave on the zero padding past N: nothing to store
+            } else if (epi.staged_wave(nw)) {
                 char* img = st1 + wave * 8192;
                 typename Epi::Col cols[4];
 #pragma unroll
@@ -1225,44 +1253,51 @@ __global__ __launch_bounds__(512, 1) void k_gemm256s(const bf16_t* __restrict__ 
             __syncthreads();  // every wave's image read: the next tile DMAs into st1
         } else if constexpr (STG == 2) {
             const int nw = n0 + wn * 64;
-            char* img = st1 + wave * 8192;
-            typename Epi::Col cols[4];
+            if (!tail_dead(epi, nw)) {  // else: a wave on the zero padding past N
+                char* img = st1 + wave * 8192;
+                typename Epi::Col cols[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) cols[i] = epi.col(nw + i * 16 + (lane >> 4) * 4);
+                for (int i = 0; i < 4; ++i) cols[i] = epi.col(nw + i * 16 + (lane >> 4) * 4);
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
+                for (int p = 0; p < 4; ++p) {
 #pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const int j = 2 * p + jj, r = jj * 16 + (lane & 15);
+                    for (int jj = 0; jj < 2; ++jj) {
+                        const int j = 2 * p + jj, r = jj * 16 + (lane & 15);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int ch = 4 * i + (lane >> 4);  // 16-B f32 chunk of the 256-B row
-                        *reinterpret_cast<float4*>(img + r * 256 + ((ch ^ (r & 15)) << 4)) =
-                            epi.stage4(acc[i][j], cols[i]);
+                        for (int i = 0; i < 4; ++i) {
+                            const int ch = 4 * i + (lane >> 4);  // 16-B f32 chunk of the 256-B row
+                            *reinterpret_cast<float4*>(img + r * 256 + ((ch ^ (r & 15)) << 4)) =
+                                epi.stage4(acc[i][j], cols[i]);
+                        }
                     }
-                }
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_wave_barrier();
-                float4 xv[8];
+                    __builtin_amdgcn_s_waitcnt(0xc07f);
+                    __builtin_amdgcn_wave_barrier();
+                    float4 xv[8];
 #pragma unroll
-                for (int it = 0; it < 8; ++it) {
-                    const int L = it * 64 + lane, r = L >> 4, ch = L & 15;
-                    xv[it] = epi.load4(mz + min(m0 + wm * 128 + p * 32 + r, M - 1), nw + ch * 4);
-                }
+                    for (int it = 0; it < 8; ++it) {
+                        const int L = it * 64 + lane, r = L >> 4, ch = L & 15;
+                        xv[it] = epi.load4(mz + min(m0 + wm * 128 + p * 32 + r, M - 1), nw + ch * 4);
+                    }
 #pragma unroll
-                for (int it = 0; it < 8; ++it) {
-                    const int L = it * 64 + lane, r = L >> 4, ch = L & 15;
-                    const int m = m0 + wm * 128 + p * 32 + r;
-                    const float4 y = *reinterpret_cast<const float4*>(img + r * 256 + ((ch ^ (r & 15)) << 4));
-                    if (m < M) epi.put4(mz + m, nw + ch * 4, xv[it], y);
+                    for (int it = 0; it < 8; ++it) {
+                        const int L = it * 64 + lane, r = L >> 4, ch = L & 15;
+                        const int m = m0 + wm * 128 + p * 32 + r;
+                        const float4 y = *reinterpret_cast<const float4*>(img + r * 256 + ((ch ^ (r & 15)) << 4));
+                        if (m < M) epi.put4(mz + m, nw + ch * 4, xv[it], y);
+                    }
+                    __builtin_amdgcn_s_waitcnt(0xc07f);
+                    __builtin_amdgcn_wave_barrier();
                 }
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_wave_barrier();
             }
             __syncthreads();  // every wave's image read: the next tile DMAs into st1
         } else {
-            if (m0 + TM <= M) epilogue(std::false_type{});
-            else epilogue(std::true_type{});
+            if (tail_dead(epi, n0 + wn * 64)) {
+                // a wave on the zero padding past N: nothing to store
+            } else if (m0 + TM <= M) {
+                epilogue(std::false_type{});
+            } else {
+                epilogue(std::true_type{});
+            }
         }
         rm = nrm;
         sa = nsa;
@@ -1527,10 +1562,17 @@ int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda
     // batched products: staged-f32 epilogues only (their row index is the only per-problem
     // output coordinate), 16-B aligned problem bases
     if (nb < 1 || (nb > 1 && (dma::staged_of<Epi>::value != 2 || ((sA | sW) & 7)))) return MLG_EINVAL;
-    if (N % 256) return MLG_EINVAL;
-    const long ntiles = (long)nb * (N / 256) * ((M + 255) / 256);
+    // EpiTail: N % 128 == 0, W zero-padded to Np rows, the kernel runs Np columns
+    int Np = N;
+    if constexpr (dma::tail_of<Epi>::value) {
+        if (N <= 0 || N % 128 || epi.nvalid != N) return MLG_EINVAL;
+        Np = (N + 255) / 256 * 256;
+    } else if (N % 256) {
+        return MLG_EINVAL;
+    }
+    const long ntiles = (long)nb * (Np / 256) * ((M + 255) / 256);
     if (ntiles > INT32_MAX) return MLG_EINVAL;
-    hipLaunchKernelGGL(dma::k_gemm256s<Epi>, dim3(persistent_grid(ntiles)), dim3(512), 0, s, A, W, M, N, K0, lda, ldw, epi, nb,
+    hipLaunchKernelGGL(dma::k_gemm256s<Epi>, dim3(persistent_grid(ntiles)), dim3(512), 0, s, A, W, M, Np, K0, lda, ldw, epi, nb,
                        sA, sW);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
@@ -1539,13 +1581,25 @@ int launch_split(const bf16_t* A, const bf16_t* W, int M, int N, int K0, int lda
 }  // namespace
 
 int mlg_gemm_qkv_split(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* Q, bf16_t* Kh, bf16_t* V, int M,
-                       int T, int Tpad, size_t lo_off, hipStream_t s) {
+                       int T, int Tpad, size_t lo_off, hipStream_t s, int E) {
     if (M % T) return MLG_EINVAL;
-    return launch_split(A, W, M, 3 * 768, 768, 2 * 768, 2 * 768,
-                        EpiQKVSplit{Q, Kh, V, bias, T, Tpad, (M / T) * Tpad, lo_off}, s);
+    const int Np = (M / T) * Tpad;
+    switch (E) {
+        case 384:  // 1152 = 4 x 256 + 128
+            return launch_split(A, W, M, 3 * 384, 384, 2 * 384, 2 * 384,
+                                EpiTail<EpiQKVSplit<384>>{{Q, Kh, V, bias, T, Tpad, Np, lo_off}, 3 * 384}, s);
+        case 768:
+            return launch_split(A, W, M, 3 * 768, 768, 2 * 768, 2 * 768,
+                                EpiQKVSplit<768>{Q, Kh, V, bias, T, Tpad, Np, lo_off}, s);
+        case 1024:
+            return launch_split(A, W, M, 3 * 1024, 1024, 2 * 1024, 2 * 1024,
+                                EpiQKVSplit<1024>{Q, Kh, V, bias, T, Tpad, Np, lo_off}, s);
+        default: return MLG_EINVAL;
+    }
 }
 int mlg_gemm_residual_split(const bf16_t* A, const bf16_t* W, const float* bias, const float* gamma, float* X, int M,
                             int N, int K0, hipStream_t s) {
+    if (N % 256) return launch_split(A, W, M, N, K0, 2 * K0, 2 * K0, EpiTail<EpiResidual>{{X, N, bias, gamma}, N}, s);
     return launch_split(A, W, M, N, K0, 2 * K0, 2 * K0, EpiResidual{X, N, bias, gamma}, s);
 }
 int mlg_gemm_bias_gelu_split(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* C, int M, int N, int K0,
@@ -1553,9 +1607,15 @@ int mlg_gemm_bias_gelu_split(const bf16_t* A, const bf16_t* W, const float* bias
     return launch_split(A, W, M, N, K0, 2 * K0, 2 * K0, EpiBiasGeluSplit{C, 2 * N, N, bias}, s);
 }
 int mlg_gemm_patch_split(const bf16_t* A, const bf16_t* W, const float* bias, const float* pos, float* X, int M, int P,
-                         int Kpad, hipStream_t s) {
+                         int Kpad, hipStream_t s, int E) {
     if (M % P) return MLG_EINVAL;
-    return launch_split(A, W, M, 768, Kpad, 2 * Kpad, 2 * Kpad, EpiPatch{X, bias, pos, P}, s);
+    switch (E) {
+        case 384:
+            return launch_split(A, W, M, 384, Kpad, 2 * Kpad, 2 * Kpad, EpiTail<EpiPatch<384>>{{X, bias, pos, P}, 384}, s);
+        case 768: return launch_split(A, W, M, 768, Kpad, 2 * Kpad, 2 * Kpad, EpiPatch<768>{X, bias, pos, P}, s);
+        case 1024: return launch_split(A, W, M, 1024, Kpad, 2 * Kpad, 2 * Kpad, EpiPatch<1024>{X, bias, pos, P}, s);
+        default: return MLG_EINVAL;
+    }
 }
 
 int mlg_gemm_sim_split_loftr(const bf16_t* A, const bf16_t* B, int M, int Npad, int K0, float* S, int lds, int ncols,
@@ -1616,14 +1676,25 @@ int mlg_gemm_residual(const bf16_t* A, const bf16_t* W, const float* bias, const
     return launch(A, W, M, N, K, K, K, EpiResidual{X, N, bias, gamma}, s);
 }
 int mlg_gemm_qkv(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* Q, bf16_t* Kh, bf16_t* V, int M,
-                 int T, int Tpad, hipStream_t s) {
+                 int T, int Tpad, hipStream_t s, int E) {
     if (M % T || Tpad % 64 || Tpad < T) return MLG_EINVAL;
-    return launch(A, W, M, 3 * 768, 768, 768, 768, EpiQKV{Q, Kh, V, bias, T, Tpad, (M / T) * Tpad}, s);
+    const int Np = (M / T) * Tpad;
+    switch (E) {
+        case 384: return launch(A, W, M, 3 * 384, 384, 384, 384, EpiQKV<384>{Q, Kh, V, bias, T, Tpad, Np}, s);
+        case 768: return launch(A, W, M, 3 * 768, 768, 768, 768, EpiQKV<768>{Q, Kh, V, bias, T, Tpad, Np}, s);
+        case 1024: return launch(A, W, M, 3 * 1024, 1024, 1024, 1024, EpiQKV<1024>{Q, Kh, V, bias, T, Tpad, Np}, s);
+        default: return MLG_EINVAL;
+    }
 }
 int mlg_gemm_patch(const bf16_t* A, const bf16_t* W, const float* bias, const float* pos, float* X, int M, int P,
-                   int Kpad, hipStream_t s) {
+                   int Kpad, hipStream_t s, int E) {
     if (M % P) return MLG_EINVAL;
-    return launch(A, W, M, 768, Kpad, Kpad, Kpad, EpiPatch{X, bias, pos, P}, s);
+    switch (E) {
+        case 384: return launch(A, W, M, 384, Kpad, Kpad, Kpad, EpiPatch<384>{X, bias, pos, P}, s);
+        case 768: return launch(A, W, M, 768, Kpad, Kpad, Kpad, EpiPatch<768>{X, bias, pos, P}, s);
+        case 1024: return launch(A, W, M, 1024, Kpad, Kpad, Kpad, EpiPatch<1024>{X, bias, pos, P}, s);
+        default: return MLG_EINVAL;
+    }
 }
 int mlg_conv_implicit(const bf16_t* in, const bf16_t* zero, int B, int H, int W, int C, int k, int s,
                       const bf16_t* Wt, const float* bias, const float* R, int ldr, float* X, int ldx, bf16_t* Cout,

@@ -73,37 +73,42 @@ int mlg_gemm_bias_gelu_bf16(const bf16_t* A, const bf16_t* W, const float* bias,
                             hipStream_t s);
 int mlg_gemm_residual(const bf16_t* A, const bf16_t* W, const float* bias, const float* gamma, float* X, int M,
                       int N, int K, hipStream_t s);
+// E: the ViT width (384 / 768 / 1024; MLG_EINVAL otherwise): N = 3 E, K = E for qkv, N = E for patch
 int mlg_gemm_qkv(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* Q, bf16_t* K, bf16_t* Vt, int M,
-                 int T, int Tpad, hipStream_t s);
+                 int T, int Tpad, hipStream_t s, int E = 768);
 int mlg_gemm_patch(const bf16_t* A, const bf16_t* W, const float* bias, const float* pos, float* X, int M, int P,
-                   int Kpad, hipStream_t s);
+                   int Kpad, hipStream_t s, int E = 768);
 
 // attention.hip
-// ViT self-attention through k_attention_varlen (Q, K [12][B * Tpad][64], V^T tiled
-// [12][B * Tpad / 64][64][64], O [B * T][768]); task_ws: 5 * B int32 of device memory
+// ViT self-attention through k_attention_varlen (Q, K [heads][B * Tpad][64], V^T tiled
+// [heads][B * Tpad / 64][64][64], O [B * T][64 heads]); task_ws: 5 * B int32 of device memory
 int mlg_attention(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int T, int Tpad,
-                  int32_t* task_ws, hipStream_t s);
+                  int32_t* task_ws, hipStream_t s, int heads = 12);
 
 // vit_ops.hip
 int mlg_preprocess_patches(const uint8_t* img, int B, int H, int W, int C, long img_stride, int S, int Kpad,
                            int swap_rb, bf16_t* out, hipStream_t s, int split = 0);
-int mlg_cls_rows(float* X, const float* cls, const float* pos, int B, int T, hipStream_t s);
-int mlg_layernorm_bf16(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s);
+// E: the token width, 384 / 768 / 1024 (MLG_EINVAL otherwise)
+int mlg_cls_rows(float* X, const float* cls, const float* pos, int B, int T, hipStream_t s, int E = 768);
+int mlg_layernorm_bf16(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s, int E = 768);
 // split-bf16 forward (MLG_VIT_SPLIT): [hi | lo] operand rows, weights [W_hi | W_lo] (2x the reduction dim)
-int mlg_layernorm_split(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s);
+int mlg_layernorm_split(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s, int E = 768);
+// The split GEMMs tile N by 256.  N % 256 == 128 (ViT-S: 1152, 384) is taken with W zero-padded
+// to the next multiple of 256 rows: the last tile's upper two wave columns run on the padding
+// and skip their epilogue, so bias / gamma / outputs keep their N columns (gemm_bf16.hip EpiTail).
 int mlg_gemm_qkv_split(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* Q, bf16_t* K, bf16_t* Vt, int M,
-                       int T, int Tpad, size_t lo_off, hipStream_t s);
+                       int T, int Tpad, size_t lo_off, hipStream_t s, int E = 768);
 int mlg_gemm_residual_split(const bf16_t* A, const bf16_t* W, const float* bias, const float* gamma, float* X, int M,
                             int N, int K0, hipStream_t s);
 int mlg_gemm_bias_gelu_split(const bf16_t* A, const bf16_t* W, const float* bias, bf16_t* C, int M, int N, int K0,
                              hipStream_t s);
 int mlg_gemm_patch_split(const bf16_t* A, const bf16_t* W, const float* bias, const float* pos, float* X, int M, int P,
-                         int Kpad, hipStream_t s);
+                         int Kpad, hipStream_t s, int E = 768);
 int mlg_attention_split(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int T, int Tpad,
-                        size_t lo_off, int32_t* task_ws, hipStream_t s);
+                        size_t lo_off, int32_t* task_ws, hipStream_t s, int heads = 12);
 int mlg_final_norm_gem(const float* X, const float* g, const float* b, float* local, float* partial, float* desc,
-                       int B, int T, int mean_pool, hipStream_t s);
-size_t mlg_gem_partial_bytes(int B);
+                       int B, int T, int mean_pool, hipStream_t s, int E = 768);
+size_t mlg_gem_partial_bytes(int B, int E = 768);
 
 // salad.hip -- SALAD head per frame (token MLP, Sinkhorn, aggregation, normalisation)
 int mlg_salad_head(const bf16_t* xn, const float* Y, int B, int T, const float* wt1, const float* bt1,

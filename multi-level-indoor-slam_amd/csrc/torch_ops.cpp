@@ -126,6 +126,67 @@ void vit_forward_into(const Tensor& frames, at::TensorList w, int64_t image_size
     }
 }
 
+// ------------------------------------------------------- DINOv2 ViT-S / B / L-14
+// depth of the hub network of width `embed`; refuses any other width
+int64_t dino_depth(int64_t embed) {
+    TORCH_CHECK(embed == 384 || embed == 768 || embed == 1024, "dino: embed must be 384 (dinov2_vits14), 768 "
+                "(dinov2_vitb14) or 1024 (dinov2_vitl14), got ", embed);
+    return embed == 1024 ? 24 : 12;
+}
+
+void dino_weights(wt::DinoFlat& f, at::TensorList w, bool split, int64_t tokens, int64_t embed,
+                  c10::optional<c10::Device> dev) {
+    f.w = MLG_STRUCT_INIT(mlg_dino_weights);
+    f.w.embed = (int)embed;
+    f.w.depth = (int)dino_depth(embed);
+    f.w.heads = (int)embed / 64;
+    fill_weights(wt::dino_table(split, tokens, embed, f.w.depth), "dino", w, &f, dev);
+    f.w.blocks = f.blocks;
+    f.w.packing = split ? MLG_VIT_SPLIT : 0;
+}
+
+// vit_forward_into for the network of width `embed`: desc f32 [B, embed], local f32
+// [B, n_local, embed]
+void dino_forward_into(const Tensor& frames, at::TensorList w, int64_t embed, int64_t image_size, int64_t flags,
+                       int64_t max_batch, const Tensor& desc, const c10::optional<Tensor>& local) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    want(desc, at::kFloat, "desc");
+    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    dino_depth(embed);
+    TORCH_CHECK(desc.dim() == 2 && desc.size(0) == B && desc.size(1) == embed, "desc must be [B, ", embed, "]");
+    const int64_t grid = image_size / 14, n_local = grid * grid - 1;
+    if (local.has_value() && local->defined()) {
+        want(*local, at::kFloat, "local");
+        TORCH_CHECK(local->dim() == 3 && local->size(0) == B && local->size(1) == n_local && local->size(2) == embed,
+                    "local must be [B, (S/14)^2 - 1, ", embed, "]");
+    }
+    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    wt::DinoFlat f;
+    dino_weights(f, w, (flags & MLG_VIT_SPLIT) != 0, 1 + grid * grid, embed, frames.device());
+    c10::DeviceGuard g(frames.device());
+    const int64_t nb_max = std::min(B, max_batch);
+    Tensor ws = workspace(mlg_dino_workspace_bytes((int)embed, (int)nb_max, (int)image_size), frames);
+    const long stride = (long)(H * W * C);
+    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
+        const int nb = (int)std::min(max_batch, B - b0);
+        float* lo = (local.has_value() && local->defined()) ? mp<float>(*local) + b0 * n_local * embed : nullptr;
+        check_rc(mlg_dino_forward(&f.w, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
+                                  (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
+                                  mp<float>(desc) + b0 * embed, lo, stream_of(frames)),
+                 "mlg_dino_forward");
+    }
+}
+
+// weights_check for a dino list (any one device, host included); the token count comes from
+// the list's own `pos`
+void dino_weights_check(at::TensorList w, int64_t embed, bool split) {
+    dino_depth(embed);
+    const int64_t tokens = w.size() > 3 && w[3].defined() ? w[3].numel() / embed : 0;
+    wt::DinoFlat f;
+    dino_weights(f, w, split, tokens, embed, c10::nullopt);
+}
+
 // SALAD: frames uint8 [B, H, W, C] -> desc f32 [B, 8448]
 Tensor salad_forward(const Tensor& frames, at::TensorList w, at::TensorList salad, double dust_bin,
                      int64_t image_size, int64_t max_batch) {
@@ -1076,6 +1137,9 @@ Tensor jpeg_pixels(const Tensor& coefs, const Tensor& qtabs, const Tensor& param
 TORCH_LIBRARY(mlgate, m) {
     m.def("vit_forward_into(Tensor frames, Tensor[] weights, int image_size, int flags, int max_batch, "
           "Tensor(a!) desc, Tensor(b!)? local) -> ()");
+    m.def("dino_forward_into(Tensor frames, Tensor[] weights, int embed, int image_size, int flags, int max_batch, "
+          "Tensor(a!) desc, Tensor(b!)? local) -> ()");
+    m.def("dino_weights_check(Tensor[] weights, int embed, bool split) -> ()");
     m.def("salad_forward(Tensor frames, Tensor[] weights, Tensor[] salad, float dust_bin, int image_size, "
           "int max_batch) -> Tensor");
     m.def("knn_gate(Tensor desc, Tensor t, Tensor floor, Tensor has_floor, float min_gap, float thr, int k, "
@@ -1137,6 +1201,8 @@ TORCH_LIBRARY(mlgate, m) {
 
 TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("vit_forward_into", &vit_forward_into);
+    m.impl("dino_forward_into", &dino_forward_into);
+    m.impl("dino_weights_check", &dino_weights_check);  // device lists; host lists: the composite kernel below
     m.impl("salad_forward", &salad_forward);
     m.impl("knn_gate", &knn_gate);
     m.impl("knn_query", &knn_query);
@@ -1184,6 +1250,7 @@ TORCH_LIBRARY_IMPL(mlgate, CPU, m) {
 
 TORCH_LIBRARY_IMPL(mlgate, CompositeExplicitAutograd, m) {
     m.impl("weights_check", &weights_check);
+    m.impl("dino_weights_check", &dino_weights_check);
     m.impl("prof_enable", &prof_enable);
     m.impl("jpeg_coef_bytes", &jpeg_coef_bytes);
     m.impl("prof_reset", &prof_reset);

@@ -1,9 +1,11 @@
-// Memory-bound ViT-B/14 ops around the GEMMs (gfx950): preprocessing + patch
+// Memory-bound DINOv2 ViT-S/B/L-14 ops around the GEMMs (gfx950): preprocessing + patch
 // extraction, CLS rows, LayerNorm, and the fused final-LayerNorm + local-feature +
 // GeM pooling of the CricaVPR descriptor.
 #include "common.h"
 #include "kernels.h"
 #include "resize_cv.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -72,125 +74,207 @@ __global__ __launch_bounds__(256) void k_preprocess_patches(PrepParams pp, int t
     }
 }
 
-// LayerNorm as split-bf16 pairs: rows of 1536, hi in columns 0..767, lo in 768..1535
-__global__ __launch_bounds__(256) void k_layernorm_split(const float* __restrict__ X, const float* __restrict__ g,
-                                                         const float* __restrict__ b, bf16_t* __restrict__ Y, int M);
-
 // X[b, 0, :] = cls + pos[0]
+template <int E>
 __global__ void k_cls_rows(float* X, const float* cls, const float* pos, int T) {
     const int b = blockIdx.x;
-    for (int c = threadIdx.x; c < 768; c += blockDim.x) X[(size_t)b * T * 768 + c] = cls[c] + pos[c];
+    for (int c = threadIdx.x; c < E; c += blockDim.x) X[(size_t)b * T * E + c] = cls[c] + pos[c];
 }
 
 // ---------------------------------------------------------------- LayerNorm ---
-// torch.nn.LayerNorm(768, eps=1e-6): biased variance, one wave per token row.
-__device__ __forceinline__ void ln_row(const float* x, const float* g, const float* bt, int lane, float4 (&y)[3]) {
-    float4 v[3];
+// torch.nn.LayerNorm(E, eps=1e-6): biased variance, one wave per token row, E = 384 (ViT-S),
+// 768 (ViT-B) or 1024 (ViT-L).  A lane holds NV vectors of W floats, vector i at column
+// i * 64 W + lane * W: float4 chunks of 256 columns at 768 (3) and 1024 (4); 384 is one and a
+// half such chunks, so it takes float2 chunks of 128 columns (3): 64 lanes x 6 floats, every
+// wave load still a whole contiguous 512 B.
+template <int E>
+struct LnMap {
+    using Vec = float4;
+    static constexpr int W = 4, NV = E / 256;
+    static_assert(E % 256 == 0, "float4 mapping: E a multiple of 256");
+};
+template <>
+struct LnMap<384> {
+    using Vec = float2;
+    static constexpr int W = 2, NV = 3;
+};
+
+// per-vector pieces, fixed summation order: (x + y) + (z + w)
+__device__ __forceinline__ float vsum(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float vsum(const float2& v) { return v.x + v.y; }
+__device__ __forceinline__ float vsqdev(const float4& v, float mean) {
+    const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
+    return (a * a + b * b) + (c * c + d * d);
+}
+__device__ __forceinline__ float vsqdev(const float2& v, float mean) {
+    const float a = v.x - mean, b = v.y - mean;
+    return a * a + b * b;
+}
+__device__ __forceinline__ float4 vnorm(const float4& v, float mean, float rstd, const float4& gg, const float4& bb) {
+    float4 y;
+    y.x = (v.x - mean) * rstd * gg.x + bb.x;
+    y.y = (v.y - mean) * rstd * gg.y + bb.y;
+    y.z = (v.z - mean) * rstd * gg.z + bb.z;
+    y.w = (v.w - mean) * rstd * gg.w + bb.w;
+    return y;
+}
+__device__ __forceinline__ float2 vnorm(const float2& v, float mean, float rstd, const float2& gg, const float2& bb) {
+    float2 y;
+    y.x = (v.x - mean) * rstd * gg.x + bb.x;
+    y.y = (v.y - mean) * rstd * gg.y + bb.y;
+    return y;
+}
+// the pooling sums of a vector's columns: mean (AnyLoc) and GeM p = 3, clamp(min=1e-6)^3
+__device__ __forceinline__ void vacc_mean(float* a, const float4& y) {
+    a[0] += y.x;
+    a[1] += y.y;
+    a[2] += y.z;
+    a[3] += y.w;
+}
+__device__ __forceinline__ void vacc_mean(float* a, const float2& y) {
+    a[0] += y.x;
+    a[1] += y.y;
+}
+__device__ __forceinline__ void vacc_gem(float* a, const float4& y) {
+    const float c0 = fmaxf(y.x, 1e-6f), c1 = fmaxf(y.y, 1e-6f);
+    const float c2 = fmaxf(y.z, 1e-6f), c3 = fmaxf(y.w, 1e-6f);
+    a[0] += c0 * c0 * c0;
+    a[1] += c1 * c1 * c1;
+    a[2] += c2 * c2 * c2;
+    a[3] += c3 * c3 * c3;
+}
+__device__ __forceinline__ void vacc_gem(float* a, const float2& y) {
+    const float c0 = fmaxf(y.x, 1e-6f), c1 = fmaxf(y.y, 1e-6f);
+    a[0] += c0 * c0 * c0;
+    a[1] += c1 * c1 * c1;
+}
+// bf16 stores of a vector: plain, and the split pair (hi at p, lo at p + lo_col)
+__device__ __forceinline__ void vstore_bf16(bf16_t* p, const float4& y) {
+    *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(y.x, y.y), pack_bf16x2(y.z, y.w));
+}
+__device__ __forceinline__ void vstore_bf16(bf16_t* p, const float2& y) {
+    *reinterpret_cast<uint32_t*>(p) = pack_bf16x2(y.x, y.y);
+}
+__device__ __forceinline__ void vstore_split(bf16_t* p, int lo_col, const float4& y) {
+    uint2 h, l;
+    split_bf16x4(y.x, y.y, y.z, y.w, h, l);
+    *reinterpret_cast<uint2*>(p) = h;
+    *reinterpret_cast<uint2*>(p + lo_col) = l;
+}
+__device__ __forceinline__ void vstore_split(bf16_t* p, int lo_col, const float2& y) {
+    const uint32_t h = pack_bf16x2(y.x, y.y);
+    *reinterpret_cast<uint32_t*>(p) = h;
+    *reinterpret_cast<uint32_t*>(p + lo_col) =
+        pack_bf16x2(y.x - __uint_as_float(h << 16), y.y - __uint_as_float(h & 0xffff0000u));
+}
+
+template <int E>
+__device__ __forceinline__ void ln_row(const float* x, const float* g, const float* bt, int lane,
+                                       typename LnMap<E>::Vec (&y)[LnMap<E>::NV]) {
+    using Vec = typename LnMap<E>::Vec;
+    constexpr int W = LnMap<E>::W, NV = LnMap<E>::NV;
+    Vec v[NV];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) v[i] = *reinterpret_cast<const float4*>(x + i * 256 + lane * 4);
+    for (int i = 0; i < NV; ++i) v[i] = *reinterpret_cast<const Vec*>(x + i * 64 * W + lane * W);
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    const float mean = wave_sum(s) * (1.0f / 768.0f);
+    for (int i = 0; i < NV; ++i) s += vsum(v[i]);
+    const float mean = wave_sum(s) * (1.0f / (float)E);
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-        q += (a * a + b * b) + (c * c + d * d);
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / 768.0f) + 1e-6f);
+    for (int i = 0; i < NV; ++i) q += vsqdev(v[i], mean);
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / (float)E) + 1e-6f);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float4 gg = *reinterpret_cast<const float4*>(g + i * 256 + lane * 4);
-        const float4 bb = *reinterpret_cast<const float4*>(bt + i * 256 + lane * 4);
-        y[i].x = (v[i].x - mean) * rstd * gg.x + bb.x;
-        y[i].y = (v[i].y - mean) * rstd * gg.y + bb.y;
-        y[i].z = (v[i].z - mean) * rstd * gg.z + bb.z;
-        y[i].w = (v[i].w - mean) * rstd * gg.w + bb.w;
+    for (int i = 0; i < NV; ++i) {
+        const Vec gg = *reinterpret_cast<const Vec*>(g + i * 64 * W + lane * W);
+        const Vec bb = *reinterpret_cast<const Vec*>(bt + i * 64 * W + lane * W);
+        y[i] = vnorm(v[i], mean, rstd, gg, bb);
     }
 }
 
+template <int E>
 __global__ __launch_bounds__(256) void k_layernorm_bf16(const float* __restrict__ X, const float* __restrict__ g,
                                                         const float* __restrict__ b, bf16_t* __restrict__ Y, int M) {
+    constexpr int W = LnMap<E>::W, NV = LnMap<E>::NV;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
-    float4 y[3];
-    ln_row(X + (size_t)row * 768, g, b, lane, y);
+    typename LnMap<E>::Vec y[NV];
+    ln_row<E>(X + (size_t)row * E, g, b, lane, y);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-        *reinterpret_cast<uint2*>(Y + (size_t)row * 768 + i * 256 + lane * 4) =
-            make_uint2(pack_bf16x2(y[i].x, y[i].y), pack_bf16x2(y[i].z, y[i].w));
+    for (int i = 0; i < NV; ++i) vstore_bf16(Y + (size_t)row * E + i * 64 * W + lane * W, y[i]);
 }
 
+// LayerNorm as split-bf16 pairs: rows of 2 E, hi in columns 0..E-1, lo in E..2E-1
+template <int E>
 __global__ __launch_bounds__(256) void k_layernorm_split(const float* __restrict__ X, const float* __restrict__ g,
                                                          const float* __restrict__ b, bf16_t* __restrict__ Y, int M) {
+    constexpr int W = LnMap<E>::W, NV = LnMap<E>::NV;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
-    float4 y[3];
-    ln_row(X + (size_t)row * 768, g, b, lane, y);
+    typename LnMap<E>::Vec y[NV];
+    ln_row<E>(X + (size_t)row * E, g, b, lane, y);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        uint2 h, l;
-        split_bf16x4(y[i].x, y[i].y, y[i].z, y[i].w, h, l);
-        *reinterpret_cast<uint2*>(Y + (size_t)row * 1536 + i * 256 + lane * 4) = h;
-        *reinterpret_cast<uint2*>(Y + (size_t)row * 1536 + 768 + i * 256 + lane * 4) = l;
-    }
+    for (int i = 0; i < NV; ++i) vstore_split(Y + (size_t)row * (2 * E) + i * 64 * W + lane * W, E, y[i]);
 }
 
 // Final norm + CricaVPR heads.  get_intermediate_layers strips CLS (token 0) and the
 // CricaVPR code drops the first patch (token 1): tokens 2..T-1 are the local features
-// [B, T-2, 768] (f32, extract_local_features) and GeM pools over exactly those.
+// [B, T-2, E] (f32, extract_local_features) and GeM pools over exactly those.
 // Block (b, chunk) normalises GEM_CHUNK tokens and writes per-chunk sums of
 // clamp(x, 1e-6)^3; k_gem_finish reduces the chunks in a fixed order.
 constexpr int GEM_CHUNKS = 8;
 
+template <int E>
 __global__ __launch_bounds__(256) void k_final_norm_gem(const float* __restrict__ X, const float* __restrict__ g,
                                                         const float* __restrict__ bt, float* __restrict__ local,
                                                         float* __restrict__ partial, int T, int mean_pool) {
-    __shared__ float red[4][768];
+    using Vec = typename LnMap<E>::Vec;
+    constexpr int W = LnMap<E>::W, NV = LnMap<E>::NV;
+    __shared__ float red[4][E];
     const int b = blockIdx.x, chunk = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int L = T - 2, per = (L + GEM_CHUNKS - 1) / GEM_CHUNKS;
     const int t0 = chunk * per, t1 = min(L, t0 + per);
-    float acc[12];
+    float acc[W * NV];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+    for (int i = 0; i < W * NV; ++i) acc[i] = 0.f;
     for (int t = t0 + wave; t < t1; t += 4) {
-        float4 y[3];
-        ln_row(X + ((size_t)b * T + 2 + t) * 768, g, bt, lane, y);
-        float* dst = local ? local + ((size_t)b * L + t) * 768 : nullptr;
+        Vec y[NV];
+        ln_row<E>(X + ((size_t)b * T + 2 + t) * E, g, bt, lane, y);
+        float* dst = local ? local + ((size_t)b * L + t) * E : nullptr;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (dst) *reinterpret_cast<float4*>(dst + i * 256 + lane * 4) = y[i];
-            if (mean_pool) {  // AnyLoc: patch_features.mean(dim=1)
-                acc[4 * i + 0] += y[i].x;
-                acc[4 * i + 1] += y[i].y;
-                acc[4 * i + 2] += y[i].z;
-                acc[4 * i + 3] += y[i].w;
-            } else {  // CricaVPR GeM p = 3: clamp(min=1e-6)^3
-                const float c0 = fmaxf(y[i].x, 1e-6f), c1 = fmaxf(y[i].y, 1e-6f);
-                const float c2 = fmaxf(y[i].z, 1e-6f), c3 = fmaxf(y[i].w, 1e-6f);
-                acc[4 * i + 0] += c0 * c0 * c0;
-                acc[4 * i + 1] += c1 * c1 * c1;
-                acc[4 * i + 2] += c2 * c2 * c2;
-                acc[4 * i + 3] += c3 * c3 * c3;
-            }
+        for (int i = 0; i < NV; ++i) {
+            if (dst) *reinterpret_cast<Vec*>(dst + i * 64 * W + lane * W) = y[i];
+            if (mean_pool) vacc_mean(acc + W * i, y[i]);  // AnyLoc: patch_features.mean(dim=1)
+            else vacc_gem(acc + W * i, y[i]);             // CricaVPR GeM p = 3
         }
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NV; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) red[wave][i * 256 + lane * 4 + j] = acc[4 * i + j];
+        for (int j = 0; j < W; ++j) red[wave][i * 64 * W + lane * W + j] = acc[W * i + j];
     __syncthreads();
-    for (int c = threadIdx.x; c < 768; c += 256)
-        partial[((size_t)b * GEM_CHUNKS + chunk) * 768 + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    for (int c = threadIdx.x; c < E; c += 256)
+        partial[((size_t)b * GEM_CHUNKS + chunk) * E + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
 
+template <int E>
 __global__ void k_gem_finish(const float* __restrict__ partial, float* __restrict__ desc, int L, int mean_pool) {
     const int b = blockIdx.x;
-    for (int c = threadIdx.x; c < 768; c += blockDim.x) {
+    for (int c = threadIdx.x; c < E; c += blockDim.x) {
         float s = 0.f;
-        for (int k = 0; k < GEM_CHUNKS; ++k) s += partial[((size_t)b * GEM_CHUNKS + k) * 768 + c];
-        desc[(size_t)b * 768 + c] = mean_pool ? s / (float)L : powf(s / (float)L, 1.0f / 3.0f);
+        for (int k = 0; k < GEM_CHUNKS; ++k) s += partial[((size_t)b * GEM_CHUNKS + k) * E + c];
+        desc[(size_t)b * E + c] = mean_pool ? s / (float)L : powf(s / (float)L, 1.0f / 3.0f);
+    }
+}
+
+// Run f(std::integral_constant<int, E>) for a supported width; false otherwise.
+template <class F>
+bool for_width(int E, F f) {
+    switch (E) {
+        case 384: f(std::integral_constant<int, 384>{}); return true;
+        case 768: f(std::integral_constant<int, 768>{}); return true;
+        case 1024: f(std::integral_constant<int, 1024>{}); return true;
+        default: return false;
     }
 }
 
@@ -208,34 +292,49 @@ int mlg_preprocess_patches(const uint8_t* img, int B, int H, int W, int C, long 
     return MLG_OK;
 }
 
-int mlg_cls_rows(float* X, const float* cls, const float* pos, int B, int T, hipStream_t s) {
-    hipLaunchKernelGGL(k_cls_rows, dim3(B), dim3(256), 0, s, X, cls, pos, T);
+int mlg_cls_rows(float* X, const float* cls, const float* pos, int B, int T, hipStream_t s, int E) {
+    if (!for_width(E, [&](auto e) {
+            hipLaunchKernelGGL(k_cls_rows<decltype(e)::value>, dim3(B), dim3(256), 0, s, X, cls, pos, T);
+        }))
+        return MLG_EINVAL;
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
 
-int mlg_layernorm_bf16(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s) {
+int mlg_layernorm_bf16(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s, int E) {
     if (M <= 0) return MLG_EINVAL;
-    hipLaunchKernelGGL(k_layernorm_bf16, dim3((M + 3) / 4), dim3(256), 0, s, X, g, b, Y, M);
+    if (!for_width(E, [&](auto e) {
+            hipLaunchKernelGGL(k_layernorm_bf16<decltype(e)::value>, dim3((M + 3) / 4), dim3(256), 0, s, X, g, b, Y, M);
+        }))
+        return MLG_EINVAL;
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
 
-int mlg_layernorm_split(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s) {
+int mlg_layernorm_split(const float* X, const float* g, const float* b, bf16_t* Y, int M, hipStream_t s, int E) {
     if (M <= 0) return MLG_EINVAL;
-    hipLaunchKernelGGL(k_layernorm_split, dim3((M + 3) / 4), dim3(256), 0, s, X, g, b, Y, M);
+    if (!for_width(E, [&](auto e) {
+            hipLaunchKernelGGL(k_layernorm_split<decltype(e)::value>, dim3((M + 3) / 4), dim3(256), 0, s, X, g, b, Y, M);
+        }))
+        return MLG_EINVAL;
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
 
 int mlg_final_norm_gem(const float* X, const float* g, const float* b, float* local, float* partial, float* desc,
-                       int B, int T, int mean_pool, hipStream_t s) {
+                       int B, int T, int mean_pool, hipStream_t s, int E) {
     if (B <= 0 || T < 3) return MLG_EINVAL;
-    hipLaunchKernelGGL(k_final_norm_gem, dim3(B, GEM_CHUNKS), dim3(256), 0, s, X, g, b, local, partial, T, mean_pool);
+    if (!for_width(E, [&](auto e) {
+            hipLaunchKernelGGL(k_final_norm_gem<decltype(e)::value>, dim3(B, GEM_CHUNKS), dim3(256), 0, s, X, g, b,
+                               local, partial, T, mean_pool);
+        }))
+        return MLG_EINVAL;
     MLG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gem_finish, dim3(B), dim3(256), 0, s, partial, desc, T - 2, mean_pool);
+    for_width(E, [&](auto e) {
+        hipLaunchKernelGGL(k_gem_finish<decltype(e)::value>, dim3(B), dim3(256), 0, s, partial, desc, T - 2, mean_pool);
+    });
     MLG_LAUNCH_CHECK();
     return MLG_OK;
 }
 
-size_t mlg_gem_partial_bytes(int B) { return (size_t)B * GEM_CHUNKS * 768 * sizeof(float); }
+size_t mlg_gem_partial_bytes(int B, int E) { return (size_t)B * GEM_CHUNKS * E * sizeof(float); }

@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -130,6 +131,52 @@ inline const Table& vit_table(bool split, int64_t tokens) {
         }
         WT_FIELD(t, 0, "", W, norm_w, F32, E);
         WT_FIELD(t, 0, "", W, norm_b, F32, E);
+    });
+}
+
+// mlg_dino_weights with the block array it points to behind it, so that one table addresses
+// both; after wt::fill, set w.blocks = blocks
+struct DinoFlat {
+    mlg_dino_weights w;
+    mlg_vit_block blocks[MLG_DINO_MAX_DEPTH];
+};
+
+// rows of a split-packed GEMM weight with n output rows: the split GEMM's 256-column tile
+// (mlgate.h: zero rows up to the next multiple of 256; only ViT-S has such weights)
+inline int64_t split_rows(int64_t n) { return (n + 255) / 256 * 256; }
+
+// vit_table for a network of width `embed` and `depth` blocks, over DinoFlat
+inline const Table& dino_table(bool split, int64_t tokens, int64_t embed, int depth) {
+    return built_once_per(std::make_tuple(split, tokens, embed, depth), [=](Table& t) {
+        using W = mlg_dino_weights;
+        using B = mlg_vit_block;
+        const int64_t m = split ? 2 : 1, E = embed;
+        const auto rows = [=](int64_t n) { return split ? split_rows(n) : n; };
+        const size_t w0 = offsetof(DinoFlat, w);
+        WT_FIELD(t, w0, "", W, patch_w, BF16, rows(E) * MLG_VIT_PATCH_K * m);
+        WT_FIELD(t, w0, "", W, patch_b, F32, E);
+        WT_FIELD(t, w0, "", W, cls, F32, E);
+        WT_FIELD(t, w0, "", W, pos, F32, tokens * E);
+        for (int i = 0; i < depth && i < MLG_DINO_MAX_DEPTH; ++i) {
+            const size_t o = offsetof(DinoFlat, blocks) + i * sizeof(B);
+            const std::string p = at("blocks", i) + ".";
+            WT_FIELD(t, o, p, B, norm1_w, F32, E);
+            WT_FIELD(t, o, p, B, norm1_b, F32, E);
+            WT_FIELD(t, o, p, B, qkv_w, BF16, rows(3 * E) * E * m);
+            WT_FIELD(t, o, p, B, qkv_b, F32, 3 * E);
+            WT_FIELD(t, o, p, B, proj_w, BF16, rows(E) * E * m);
+            WT_FIELD(t, o, p, B, proj_b, F32, E);
+            WT_FIELD(t, o, p, B, ls1, F32, E);
+            WT_FIELD(t, o, p, B, norm2_w, F32, E);
+            WT_FIELD(t, o, p, B, norm2_b, F32, E);
+            WT_FIELD(t, o, p, B, fc1_w, BF16, rows(4 * E) * E * m);
+            WT_FIELD(t, o, p, B, fc1_b, F32, 4 * E);
+            WT_FIELD(t, o, p, B, fc2_w, BF16, rows(E) * 4 * E * m);
+            WT_FIELD(t, o, p, B, fc2_b, F32, E);
+            WT_FIELD(t, o, p, B, ls2, F32, E);
+        }
+        WT_FIELD(t, w0, "", W, norm_w, F32, E);
+        WT_FIELD(t, w0, "", W, norm_b, F32, E);
     });
 }
 

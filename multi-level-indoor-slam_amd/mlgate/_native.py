@@ -16,7 +16,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmlgate.so")
 TORCH_LIB_PATH = os.path.join(_HERE, "libmlgate_torch.so")
-OPS = ("vit_forward_into", "salad_forward", "knn_gate", "knn_query", "row_normalize", "similarity", "xcorr_score", "xcorr_batch",
+OPS = ("vit_forward_into", "dino_forward_into", "dino_weights_check", "salad_forward", "knn_gate", "knn_query", "row_normalize", "similarity", "xcorr_score", "xcorr_batch",
        "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
        "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess", "vlad", "anyloc_forward", "kmeans_step",
@@ -32,6 +32,9 @@ EXPORTS = {
     "mlg_strerror": (ctypes.c_char_p, [c_int]),
     "mlg_vit_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mlg_vit_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_void_p,
+                                c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mlg_dino_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mlg_dino_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_void_p,
                                 c_size_t, c_void_p, c_void_p, c_void_p]),
     "mlg_salad_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mlg_salad_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int,

@@ -91,8 +91,10 @@ class FullSemanticGate:
                  similarity_threshold: float = 0.5, min_time_gap: float = 10.0, k: int = 10, min_inliers: int = 20,
                  min_inlier_ratio: float = 0.25, strict_mode: bool = True, retrieval_floor_gating: bool = True,
                  verifier_floor_gating: bool = True, verify_rejected: bool = False, start_floor: int = 5,
-                 imu_detector_kwargs: Optional[Dict] = None):
+                 imu_detector_kwargs: Optional[Dict] = None, backbone: str = 'dinov2_vitb14'):
         self.vpr_method, self.matcher_type, self.device = vpr_method, matcher_type, device
+        # the DINOv2 backbone of the 'cricavpr' / 'anyloc' methods (dinov2_vits14 / b14 / l14)
+        self.backbone = backbone
         self.similarity_threshold, self.min_time_gap, self.k = similarity_threshold, min_time_gap, k
         self.min_inliers, self.min_inlier_ratio, self.strict_mode = min_inliers, min_inlier_ratio, strict_mode
         self.retrieval_floor_gating = retrieval_floor_gating
@@ -117,6 +119,12 @@ class FullSemanticGate:
         floor_labels = np.asarray(floor_labels)
         self.spr = SemanticPlaceRecognition(self.vpr_method, self.device, self.similarity_threshold,
                                             self.min_time_gap)
+        if self.backbone != 'dinov2_vitb14':
+            from .weights import backbone_config
+            if not hasattr(self.spr.vpr, 'backbone_name'):
+                raise ValueError(f"backbone = {self.backbone}: the {self.vpr_method} method has no DINOv2 backbone")
+            self.spr.vpr.backbone_name = self.backbone
+            self.spr.vpr.descriptor_dim = backbone_config(self.backbone)[0]
         if isinstance(images, torch.Tensor):
             frames = images
         else:
@@ -163,14 +171,17 @@ class DeviceGate:
                  verifier_floor_gating=True, verify=True, K=None, min_inliers=20, min_inlier_ratio=0.25,
                  vit_batch=123, sp_batch=64, lg_chunk=1024, max_keypoints=2048, vit_state_dict=None, record=False,
                  vit_precise=True, matcher='lightglue', loftr_chunk=256, max_pairs=None, lg_tail=0,
-                 local_features=True):
+                 local_features=True, backbone='dinov2_vitb14'):
         import torch
         from . import distributed as mdist
         from .lightglue import LightGlueGPU
         from .superpoint import SuperPointGPU
-        from .vit import VitB14
-        from .weights import EMBED, synthetic_state_dict
+        from .vit import DinoVit, VitB14
+        from .weights import backbone_config, synthetic_state_dict
         self.torch, self.mdist = torch, mdist
+        # the DINOv2 backbone: its width sizes the gather, descriptor and local-feature buffers
+        self.backbone = backbone
+        EMBED = backbone_config(backbone)[0]
         self.dev = torch.device(device)
         self.world, self.rank = world, rank
         N = self.N = len(timestamps)
@@ -200,15 +211,17 @@ class DeviceGate:
         self.hf_all = torch.as_tensor(has, dtype=torch.uint8, device=self.dev)
         num = np.array([np.nan if v is None else float(v) for v in lab], np.float64)
         self.f_num = torch.as_tensor(num, device=self.dev)
-        sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0)
+        sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
         # vit_precise: the split-bf16 ViT (MLG_VIT_SPLIT), whose descriptors follow the fp32
         # network closely enough that the kNN ranks near-ties as the fp32 reference does
-        self.eng = VitB14(sd, device=self.dev, max_batch=vit_batch, precise=vit_precise)
+        self.eng = (VitB14(sd, device=self.dev, max_batch=vit_batch, precise=vit_precise)
+                    if backbone == 'dinov2_vitb14' else
+                    DinoVit(sd, backbone=backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise))
         self.gather = mdist.RowGather(N, EMBED, world, self.dev)
         self.desc_loc = (self.gather.out[self.lo:self.hi] if world == 1
                          else torch.empty(self.n_local, EMBED, device=self.dev))
         # CricaVPR's per-keyframe local features (place_recognition.py:645-667, the input of
-        # rerank_candidates), written by the same ViT forward: [N, 528, 768] f32, 1.6 MB per
+        # rerank_candidates), written by the same ViT forward: [N, 528, 768] f32 at ViT-B, 1.6 MB per
         # keyframe.  local_features=False leaves them unmaterialised (the gate itself never
         # reads them): the N = 19,163 sequence then fits one GPU with its LightGlue workspace
         self.local_feats = (torch.empty(self.n_local, self.eng.n_local, EMBED, dtype=torch.float32, device=self.dev)

@@ -1,4 +1,4 @@
-"""DINOv2 ViT-B/14 + GeM descriptor engine (CricaVPR path) on the mlgate HIP kernels.
+"""DINOv2 ViT-S/B/L-14 + GeM descriptor engine (CricaVPR path) on the mlgate HIP kernels.
 
 Device-resident replacement for what CricaVPR does per keyframe
 (place_recognition.py:613-667, 759-803): preprocessing, the hub
@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native
-from .weights import DEPTH, EMBED, PATCH
+from .weights import DEFAULT_BACKBONE, EMBED, PATCH, backbone_config, check_state_dict
 
 PATCH_K = 768  # 3*14*14 = 588 patch inputs zero-padded to 12 K-tiles of 64 (include/mlgate.h)
 BLOCK_ORDER = ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "norm2_w", "norm2_b", "fc1_w",
@@ -48,11 +48,14 @@ def split_weight(w):
     return torch.cat([hi, lo], dim=1).contiguous()
 
 
-def pack_weights(sd, device, grid, precise):
-    """The torch.ops.mlgate.vit_forward_into weight list on ``device``: patch_w, patch_b, cls,
-    pos (resampled to ``grid`` x ``grid`` patches), DEPTH x BLOCK_ORDER, norm_w, norm_b; the
-    GEMM weights bf16, [W_hi | W_lo] with ``precise``."""
+def pack_weights(sd, device, grid, precise, backbone=DEFAULT_BACKBONE):
+    """The torch.ops.mlgate.vit_forward_into / dino_forward_into weight list on ``device``:
+    patch_w, patch_b, cls, pos (resampled to ``grid`` x ``grid`` patches), depth x BLOCK_ORDER,
+    norm_w, norm_b; the GEMM weights bf16, [W_hi | W_lo] with ``precise``.  The split GEMM
+    runs 256-column tiles, so with ``precise`` a GEMM weight whose row count is no multiple of
+    256 (ViT-S: patch, qkv, proj, fc2) gets zero rows up to the next one (include/mlgate.h)."""
     f32, bf = torch.float32, torch.bfloat16
+    embed, depth = backbone_config(backbone)[:2]
 
     def dev(a, dtype):
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
@@ -61,18 +64,20 @@ def pack_weights(sd, device, grid, precise):
     def gemm_w(a):  # a GEMM weight in the layout of this forward
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         t = t.to(device, torch.float32)
-        return split_weight(t) if precise else t.to(bf).contiguous()
+        if not precise:
+            return t.to(bf).contiguous()
+        return split_weight(F.pad(t, (0, 0, 0, -t.shape[0] % 256)))
 
-    pw = torch.as_tensor(np.asarray(sd["patch_embed.proj.weight"], np.float32)).reshape(EMBED, -1)
+    pw = torch.as_tensor(np.asarray(sd["patch_embed.proj.weight"], np.float32)).reshape(embed, -1)
     pos = torch.as_tensor(np.asarray(sd["pos_embed"], np.float32)).to(device)
     w = [gemm_w(F.pad(pw, (0, PATCH_K - pw.shape[1]))), dev(sd["patch_embed.proj.bias"], f32),
-         dev(np.asarray(sd["cls_token"], np.float32).reshape(EMBED), f32),
-         dev(resample_pos_embed(pos, grid).reshape(-1, EMBED), f32)]
+         dev(np.asarray(sd["cls_token"], np.float32).reshape(embed), f32),
+         dev(resample_pos_embed(pos, grid).reshape(-1, embed), f32)]
     names = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "qkv_w": "attn.qkv.weight",
              "qkv_b": "attn.qkv.bias", "proj_w": "attn.proj.weight", "proj_b": "attn.proj.bias",
              "ls1": "ls1.gamma", "norm2_w": "norm2.weight", "norm2_b": "norm2.bias", "fc1_w": "mlp.fc1.weight",
              "fc1_b": "mlp.fc1.bias", "fc2_w": "mlp.fc2.weight", "fc2_b": "mlp.fc2.bias", "ls2": "ls2.gamma"}
-    for i in range(DEPTH):
+    for i in range(depth):
         for f in BLOCK_ORDER:
             v = sd[f"blocks.{i}." + names[f]]
             w.append(gemm_w(v) if f in BF16_FIELDS else dev(v, f32))
@@ -120,10 +125,39 @@ class VitB14:
         _native.ops().vit_forward_into(frames.contiguous(), self._w, self.image_size, self.flags, self.max_batch,
                                        desc_out, local_out)
 
+    embed = EMBED  # DinoVit: the backbone's
+
     def forward(self, frames, with_local=False):
         B = frames.shape[0]
-        desc = torch.empty(B, EMBED, dtype=torch.float32, device=self.device)
-        local = (torch.empty(B, self.n_local, EMBED, dtype=torch.float32, device=self.device)
+        desc = torch.empty(B, self.embed, dtype=torch.float32, device=self.device)
+        local = (torch.empty(B, self.n_local, self.embed, dtype=torch.float32, device=self.device)
                  if with_local else None)
         self.forward_into(frames, desc, local)
         return (desc, local) if with_local else desc
+
+
+class DinoVit(VitB14):
+    """VitB14 for any of the three hub backbones (weights.BACKBONES): dinov2_vits14 (384 wide),
+    dinov2_vitb14 (768) or dinov2_vitl14 (1024, 24 blocks), through mlg_dino_forward.  Same
+    arguments, flags and outputs with 768 read as ``embed``; ``state_dict`` must be that
+    backbone's (a checkpoint of another width is refused, naming the first tensor that
+    disagrees).  At dinov2_vitb14 it launches the kernels VitB14 launches: the same bits."""
+
+    def __init__(self, state_dict, backbone=DEFAULT_BACKBONE, **kwargs):
+        self.backbone = backbone
+        self.embed, self.depth, self.heads, _ = backbone_config(backbone)
+        check_state_dict(state_dict, backbone)
+        super().__init__(state_dict, **kwargs)
+
+    def _pack(self, sd):
+        return pack_weights(sd, self.device, self.grid, self.precise, self.backbone)
+
+    def forward_into(self, frames, desc_out, local_out=None):
+        """VitB14.forward_into with descriptors [B, embed] and local features [B, n_local, embed];
+        torch.ops.mlgate.dino_forward_into on the current stream."""
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(-1)
+        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
+            raise TypeError("frames must be a uint8 tensor on the HIP device")
+        _native.ops().dino_forward_into(frames.contiguous(), self._w, self.embed, self.image_size, self.flags,
+                                        self.max_batch, desc_out, local_out)

@@ -329,7 +329,9 @@ class SALAD(_ResNetFallback):
 
 
 class _DinoEngineMixin:
-    """Lazy ViT-B/14 engine construction shared by CricaVPR and AnyLoc."""
+    """Lazy DINOv2 engine construction shared by CricaVPR and AnyLoc: ``backbone`` is one of
+    dinov2_vits14 / dinov2_vitb14 / dinov2_vitl14 (feat_dim 384 / 768 / 1024,
+    place_recognition.py:594-602)."""
 
     _image_size = 322
     _pool = "gem"
@@ -337,20 +339,21 @@ class _DinoEngineMixin:
 
     def _engine(self):
         if getattr(self, '_vit', None) is None:
-            if self.backbone_name != 'dinov2_vitb14':
-                raise ValueError(f"{self.backbone_name}: only the dinov2_vitb14 backbone has MI355X kernels")
-            from .vit import VitB14
-            from .weights import resolve_state_dict
-            sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None))
+            from .vit import DinoVit, VitB14
+            from .weights import backbone_config, resolve_state_dict
+            embed = backbone_config(self.backbone_name)[0]  # ValueError lists the supported names
+            sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None), backbone=self.backbone_name)
             if source.startswith('synthetic'):
                 warnings.warn("DINOv2 hub weights are not available offline; using seeded synthetic "
-                              "dinov2_vitb14 weights (set pretrained_path or MLGATE_DINOV2_WEIGHTS to a local "
+                              f"{self.backbone_name} weights (set pretrained_path or MLGATE_DINOV2_WEIGHTS to a local "
                               "hub checkpoint for real descriptors).")
             # the split-bf16 forward (VitB14's default): descriptors within ~1e-11 of fp32,
             # so retrieval ranks as the fp32 reference does
-            self._vit = VitB14(sd, device=self.device, image_size=self._image_size, pool=self._pool,
-                               swap_rb=self._swap_rb, precise=True)
-            self.feat_dim = 768
+            kw = dict(device=self.device, image_size=self._image_size, pool=self._pool, swap_rb=self._swap_rb,
+                      precise=True)
+            self._vit = (VitB14(sd, **kw) if self.backbone_name == 'dinov2_vitb14'
+                         else DinoVit(sd, backbone=self.backbone_name, **kw))
+            self.feat_dim = embed
             self._model_loaded = True
         return self._vit
 
@@ -396,7 +399,8 @@ class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
     def _build_engine(self, vocabulary):
         self._check_native_dims()
         if self.backbone_name != 'dinov2_vitb14':
-            raise ValueError(f"{self.backbone_name}: only the dinov2_vitb14 backbone has MI355X kernels")
+            raise ValueError(f"{self.backbone_name}: the native branch's head is 768 wide, only the dinov2_vitb14 "
+                             "backbone has MI355X kernels for it")
         from .anyloc import AnyLocGPU
         from .weights import resolve_state_dict
         sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None))
@@ -468,7 +472,7 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
         self.use_reranking = use_reranking
         self._model_loaded = False
         self._vit = None
-        self._feature_cache = {}  # idx -> device float32 [1, 528, 768]
+        self._feature_cache = {}  # idx -> device float32 [1, 528, feat_dim]
         self.native = None  # None: MLGATE_CRICAVPR_NATIVE decides; True / False force it
         self.cross_image_group = 1  # images of a call that attend to each other (native branch)
         self._crica = None
@@ -485,7 +489,8 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
                 raise ValueError(f"native CricaVPR produces 14 x 768 = 10752-dim descriptors, not "
                                  f"{self.descriptor_dim}")
             if self.backbone_name != 'dinov2_vitb14':
-                raise ValueError(f"{self.backbone_name}: only the dinov2_vitb14 backbone has MI355X kernels")
+                raise ValueError(f"{self.backbone_name}: the native branch's head is 768 wide, only the "
+                                 "dinov2_vitb14 backbone has MI355X kernels for it")
             from .crica import CricaGPU, check_group
             from .weights import resolve_crica_state_dict
             group = check_group(self.cross_image_group)

@@ -1,4 +1,4 @@
-"""DINOv2 ViT-B/14 weights for the CricaVPR descriptor path.
+"""DINOv2 ViT-S/B/L-14 weights for the CricaVPR / AnyLoc descriptor paths.
 
 The reference fetches ``torch.hub.load('facebookresearch/dinov2', 'dinov2_vitb14')``
 (place_recognition.py:586-590).  There is no network here or on the GPU box, so:
@@ -17,11 +17,28 @@ import numpy as np
 
 EMBED, DEPTH, HEADS, MLP, PATCH, POS_GRID = 768, 12, 12, 3072, 14, 37
 
+# The hub networks the reference's ``backbone`` argument names (place_recognition.py:536, :594-602):
+# name -> (embed, depth, heads, mlp); heads of 64, mlp = 4 * embed.  EMBED .. MLP above are ViT-B's row.
+BACKBONES = {
+    "dinov2_vits14": (384, 12, 6, 1536),
+    "dinov2_vitb14": (EMBED, DEPTH, HEADS, MLP),
+    "dinov2_vitl14": (1024, 24, 16, 4096),
+}
+DEFAULT_BACKBONE = "dinov2_vitb14"
 
-def hub_keys():
+
+def backbone_config(backbone=DEFAULT_BACKBONE):
+    """(embed, depth, heads, mlp) of a supported hub backbone; ValueError names the three."""
+    if backbone not in BACKBONES:
+        raise ValueError(f"{backbone}: unsupported backbone; the MI355X kernels cover {', '.join(BACKBONES)}")
+    return BACKBONES[backbone]
+
+
+def hub_keys(backbone=DEFAULT_BACKBONE):
+    depth = backbone_config(backbone)[1]
     keys = ["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias",
             "norm.weight", "norm.bias"]
-    for i in range(DEPTH):
+    for i in range(depth):
         p = f"blocks.{i}."
         keys += [p + s for s in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias",
                                  "attn.proj.weight", "attn.proj.bias", "ls1.gamma", "norm2.weight",
@@ -30,8 +47,43 @@ def hub_keys():
     return keys
 
 
-def synthetic_state_dict(seed=0):
-    """Seeded float32 weights with the hub dinov2_vitb14 key names and shapes."""
+def hub_shapes(backbone=DEFAULT_BACKBONE):
+    """{key: shape} of the hub state dict of ``backbone``."""
+    E, depth, _, mlp = backbone_config(backbone)
+    shapes = {"cls_token": (1, 1, E), "pos_embed": (1, 1 + POS_GRID * POS_GRID, E),
+              "patch_embed.proj.weight": (E, 3, PATCH, PATCH), "patch_embed.proj.bias": (E,),
+              "norm.weight": (E,), "norm.bias": (E,)}
+    block = {"norm1.weight": (E,), "norm1.bias": (E,), "attn.qkv.weight": (3 * E, E), "attn.qkv.bias": (3 * E,),
+             "attn.proj.weight": (E, E), "attn.proj.bias": (E,), "ls1.gamma": (E,), "norm2.weight": (E,),
+             "norm2.bias": (E,), "mlp.fc1.weight": (mlp, E), "mlp.fc1.bias": (mlp,), "mlp.fc2.weight": (E, mlp),
+             "mlp.fc2.bias": (E,), "ls2.gamma": (E,)}
+    for i in range(depth):
+        shapes.update({f"blocks.{i}.{k}": v for k, v in block.items()})
+    return shapes
+
+
+def check_state_dict(sd, backbone=DEFAULT_BACKBONE, where="state dict"):
+    """Raise unless ``sd`` holds every hub tensor of ``backbone`` in its shape: KeyError for a
+    missing key, ValueError naming the backbone asked for and the first tensor that disagrees
+    (a checkpoint of another width or depth)."""
+    shapes = hub_shapes(backbone)
+    for k in hub_keys(backbone):  # the width first: a ViT-B file asked for as ViT-L also lacks blocks
+        got = tuple(sd[k].shape) if k in sd else shapes[k]
+        if got != shapes[k]:
+            raise ValueError(f"{where} is not a {backbone} checkpoint: {k} has shape {got}, "
+                             f"{backbone} has {shapes[k]}")
+    missing = [k for k in hub_keys(backbone) if k not in sd]
+    if missing:
+        raise KeyError(f"{where} lacks {backbone} keys, e.g. {missing[:3]}")
+    extra = [k for k in sd if k.startswith("blocks.") and k not in shapes]
+    if extra:
+        raise ValueError(f"{where} is not a {backbone} checkpoint: it has {extra[0]}, beyond the "
+                         f"{backbone_config(backbone)[1]} blocks of {backbone}")
+
+
+def synthetic_state_dict(seed=0, backbone=DEFAULT_BACKBONE):
+    """Seeded float32 weights with the hub key names and shapes of ``backbone``."""
+    E, depth, _, mlp = backbone_config(backbone)
     rng = np.random.default_rng(seed)
 
     def normal(shape, std, mean=0.0):
@@ -39,50 +91,50 @@ def synthetic_state_dict(seed=0):
         return a + np.float32(mean) if mean else a
 
     sd = {
-        "cls_token": normal((1, 1, EMBED), 0.02),
-        "pos_embed": normal((1, 1 + POS_GRID * POS_GRID, EMBED), 0.02),
-        "patch_embed.proj.weight": normal((EMBED, 3, PATCH, PATCH), 0.02),
-        "patch_embed.proj.bias": normal((EMBED,), 0.02),
-        "norm.weight": normal((EMBED,), 0.1, 1.0),
-        "norm.bias": normal((EMBED,), 0.05),
+        "cls_token": normal((1, 1, E), 0.02),
+        "pos_embed": normal((1, 1 + POS_GRID * POS_GRID, E), 0.02),
+        "patch_embed.proj.weight": normal((E, 3, PATCH, PATCH), 0.02),
+        "patch_embed.proj.bias": normal((E,), 0.02),
+        "norm.weight": normal((E,), 0.1, 1.0),
+        "norm.bias": normal((E,), 0.05),
     }
-    for i in range(DEPTH):
+    for i in range(depth):
         p = f"blocks.{i}."
-        sd[p + "norm1.weight"] = normal((EMBED,), 0.1, 1.0)
-        sd[p + "norm1.bias"] = normal((EMBED,), 0.05)
-        sd[p + "attn.qkv.weight"] = normal((3 * EMBED, EMBED), 0.05)
-        sd[p + "attn.qkv.bias"] = normal((3 * EMBED,), 0.02)
-        sd[p + "attn.proj.weight"] = normal((EMBED, EMBED), 0.03)
-        sd[p + "attn.proj.bias"] = normal((EMBED,), 0.02)
-        sd[p + "ls1.gamma"] = rng.uniform(0.05, 0.6, EMBED).astype(np.float32)
-        sd[p + "norm2.weight"] = normal((EMBED,), 0.1, 1.0)
-        sd[p + "norm2.bias"] = normal((EMBED,), 0.05)
-        sd[p + "mlp.fc1.weight"] = normal((MLP, EMBED), 0.03)
-        sd[p + "mlp.fc1.bias"] = normal((MLP,), 0.02)
-        sd[p + "mlp.fc2.weight"] = normal((EMBED, MLP), 0.02)
-        sd[p + "mlp.fc2.bias"] = normal((EMBED,), 0.02)
-        sd[p + "ls2.gamma"] = rng.uniform(0.05, 0.6, EMBED).astype(np.float32)
+        sd[p + "norm1.weight"] = normal((E,), 0.1, 1.0)
+        sd[p + "norm1.bias"] = normal((E,), 0.05)
+        sd[p + "attn.qkv.weight"] = normal((3 * E, E), 0.05)
+        sd[p + "attn.qkv.bias"] = normal((3 * E,), 0.02)
+        sd[p + "attn.proj.weight"] = normal((E, E), 0.03)
+        sd[p + "attn.proj.bias"] = normal((E,), 0.02)
+        sd[p + "ls1.gamma"] = rng.uniform(0.05, 0.6, E).astype(np.float32)
+        sd[p + "norm2.weight"] = normal((E,), 0.1, 1.0)
+        sd[p + "norm2.bias"] = normal((E,), 0.05)
+        sd[p + "mlp.fc1.weight"] = normal((mlp, E), 0.03)
+        sd[p + "mlp.fc1.bias"] = normal((mlp,), 0.02)
+        sd[p + "mlp.fc2.weight"] = normal((E, mlp), 0.02)
+        sd[p + "mlp.fc2.bias"] = normal((E,), 0.02)
+        sd[p + "ls2.gamma"] = rng.uniform(0.05, 0.6, E).astype(np.float32)
     return sd
 
 
-def load_hub_state_dict(path):
-    """Hub-format dinov2_vitb14 checkpoint from a local file (no code executed from it)."""
+def load_hub_state_dict(path, backbone=DEFAULT_BACKBONE):
+    """Hub-format checkpoint of ``backbone`` from a local file (no code executed from it); a
+    checkpoint of another width or depth is refused (check_state_dict)."""
     import torch
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if "model" in sd and isinstance(sd["model"], dict):
         sd = sd["model"]
-    missing = [k for k in hub_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks dinov2_vitb14 keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in hub_keys()}
+    check_state_dict(sd, backbone, f"checkpoint {path}")
+    return {k: sd[k].float().cpu().numpy() for k in hub_keys(backbone)}
 
 
-def resolve_state_dict(pretrained_path=None, seed=0):
+def resolve_state_dict(pretrained_path=None, seed=0, backbone=DEFAULT_BACKBONE):
     """(state_dict, source) -- local checkpoint if given/configured, else synthetic."""
+    backbone_config(backbone)
     path = pretrained_path or os.environ.get("MLGATE_DINOV2_WEIGHTS")
     if path:
-        return load_hub_state_dict(path), path
-    return synthetic_state_dict(seed), f"synthetic(seed={seed})"
+        return load_hub_state_dict(path, backbone), path
+    return synthetic_state_dict(seed, backbone), f"synthetic(seed={seed})"
 
 
 # ----------------------------------------------------------------- SuperPoint
