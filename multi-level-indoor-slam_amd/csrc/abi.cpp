@@ -242,17 +242,16 @@ size_t mlg_vit_workspace_bytes(int batch, int image_size) {
 }  // extern "C"
 
 // Preprocess + patch embedding + the blocks; leaves the residual stream in ws->x.
-// split: the MLG_VIT_SPLIT forward (weights packed [W_hi | W_lo], 2x the reduction dimension).
+// flags: MLG_VIT_KEEP_CHANNELS, and MLG_VIT_SPLIT for the split forward (weights packed
+// [W_hi | W_lo], 2x the reduction dimension); each step picks its split or plain launcher.
 static int vit_trunk(const VitNet& w, const uint8_t* frames, const VitGeom& g, int H, int W, int C,
-                     long frame_stride, int swap_rb, const VitWorkspace& ws, hipStream_t s, int split = 0) {
+                     long frame_stride, int flags, const VitWorkspace& ws, hipStream_t s) {
     const int M = g.B * g.T, E = g.E, F = 4 * g.E;
+    const int swap_rb = (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, split = (flags & MLG_VIT_SPLIT) ? 1 : 0;
     MLG_TRY(mlg_preprocess_patches(frames, g.B, H, W, C, frame_stride, g.S, MLG_VIT_PATCH_K, swap_rb, ws.patches, s,
                                    split));
-    if (split)
-        MLG_TRY(mlg_gemm_patch_split(ws.patches, w.patch_w, w.patch_b, w.pos, ws.x, g.B * g.P, g.P,
-                                     MLG_VIT_PATCH_K, s, E));
-    else
-        MLG_TRY(mlg_gemm_patch(ws.patches, w.patch_w, w.patch_b, w.pos, ws.x, g.B * g.P, g.P, MLG_VIT_PATCH_K, s, E));
+    MLG_TRY((split ? mlg_gemm_patch_split : mlg_gemm_patch)(ws.patches, w.patch_w, w.patch_b, w.pos, ws.x, g.B * g.P,
+                                                            g.P, MLG_VIT_PATCH_K, s, E));
     MLG_TRY(mlg_cls_rows(ws.x, w.cls, w.pos, g.B, g.T, s, E));
     // padded key columns of V^T must be finite (masked keys multiply them by p = 0); padded
     // query rows are never stored but are zeroed too, so no lane computes on stale bits
@@ -260,55 +259,37 @@ static int vit_trunk(const VitNet& w, const uint8_t* frames, const VitGeom& g, i
     if (hipMemsetAsync(ws.q, 0, ws.q_bytes, s) != hipSuccess) return MLG_EHIP;
 
     const double mul = split ? 3.0 : 1.0;  // MFMA products per algorithmic product
-    for (int l = 0; l < w.depth && split; ++l) {
+    const auto ln = [&](const float* gamma, const float* beta) {
+        return (split ? mlg_layernorm_split : mlg_layernorm_bf16)(ws.x, gamma, beta, ws.xn, M, s, E);
+    };
+    // x += ls * (a W^T + b), a [M, K]: the projection (slot 3) and fc2 (slot 1)
+    const auto residual = [&](int slot, const bf16_t* a, const bf16_t* wt, const float* b, const float* ls, int K) {
+        MlgProfScope p(slot, s, mul * 2.0 * M * (double)E * K);
+        return (split ? mlg_gemm_residual_split : mlg_gemm_residual)(a, wt, b, ls, ws.x, M, E, K, s);
+    };
+    for (int l = 0; l < w.depth; ++l) {
         const mlg_vit_block& bl = w.blocks[l];
-        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s, E));
+        MLG_TRY(ln(bl.norm1_w, bl.norm1_b));
         {
             MlgProfScope p(2, s, mul * 2.0 * M * (3.0 * E) * E);
-            MLG_TRY(mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems, s, E));
+            MLG_TRY(split ? mlg_gemm_qkv_split(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, ws.lo_elems,
+                                               s, E)
+                          : mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s, E));
         }
         {
             MlgProfScope p(4, s, mul * 4.0 * g.B * g.heads * (double)g.T * g.T * 64);
-            MLG_TRY(mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s, g.heads));
+            MLG_TRY(split ? mlg_attention_split(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.lo_elems, ws.tasks, s,
+                                                g.heads)
+                          : mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s, g.heads));
         }
-        {
-            MlgProfScope p(3, s, mul * 2.0 * M * (double)E * E);
-            MLG_TRY(mlg_gemm_residual_split(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, E, E, s));
-        }
-        MLG_TRY(mlg_layernorm_split(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s, E));
+        MLG_TRY(residual(3, ws.o, bl.proj_w, bl.proj_b, bl.ls1, E));
+        MLG_TRY(ln(bl.norm2_w, bl.norm2_b));
         {
             MlgProfScope p(0, s, mul * 2.0 * M * (double)F * E);
-            MLG_TRY(mlg_gemm_bias_gelu_split(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, F, E, s));
+            MLG_TRY((split ? mlg_gemm_bias_gelu_split : mlg_gemm_bias_gelu_bf16)(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, F, E,
+                                                                                  s));
         }
-        {
-            MlgProfScope p(1, s, mul * 2.0 * M * (double)E * F);
-            MLG_TRY(mlg_gemm_residual_split(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, E, F, s));
-        }
-    }
-    for (int l = 0; l < w.depth && !split; ++l) {
-        const mlg_vit_block& bl = w.blocks[l];
-        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm1_w, bl.norm1_b, ws.xn, M, s, E));
-        {
-            MlgProfScope p(2, s, 2.0 * M * (3.0 * E) * E);
-            MLG_TRY(mlg_gemm_qkv(ws.xn, bl.qkv_w, bl.qkv_b, ws.q, ws.k, ws.vt, M, g.T, g.Tpad, s, E));
-        }
-        {
-            MlgProfScope p(4, s, 4.0 * g.B * g.heads * (double)g.T * g.T * 64);
-            MLG_TRY(mlg_attention(ws.q, ws.k, ws.vt, ws.o, g.B, g.T, g.Tpad, ws.tasks, s, g.heads));
-        }
-        {
-            MlgProfScope p(3, s, 2.0 * M * (double)E * E);
-            MLG_TRY(mlg_gemm_residual(ws.o, bl.proj_w, bl.proj_b, bl.ls1, ws.x, M, E, E, s));
-        }
-        MLG_TRY(mlg_layernorm_bf16(ws.x, bl.norm2_w, bl.norm2_b, ws.xn, M, s, E));
-        {
-            MlgProfScope p(0, s, 2.0 * M * (double)F * E);
-            MLG_TRY(mlg_gemm_bias_gelu_bf16(ws.xn, bl.fc1_w, bl.fc1_b, ws.h, M, F, E, s));
-        }
-        {
-            MlgProfScope p(1, s, 2.0 * M * (double)E * F);
-            MLG_TRY(mlg_gemm_residual(ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, ws.x, M, E, F, s));
-        }
+        MLG_TRY(residual(1, ws.h, bl.fc2_w, bl.fc2_b, bl.ls2, F));
     }
     return MLG_OK;
 }
@@ -322,9 +303,8 @@ static int vit_forward_run(const VitNet& net, int packing, const VitGeom& g, con
     VitWorkspace ws;
     if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    const int swap_rb = (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1;
     const int mean_pool = (flags & MLG_VIT_POOL_MEAN) ? 1 : 0;
-    MLG_TRY(vit_trunk(net, frames, g, H, W, C, frame_stride, swap_rb, ws, s, (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    MLG_TRY(vit_trunk(net, frames, g, H, W, C, frame_stride, flags, ws, s));
     MLG_TRY(mlg_final_norm_gem(ws.x, net.norm_w, net.norm_b, local_out, ws.partial, desc_out, g.B, g.T, mean_pool, s,
                                g.E));
     return MLG_OK;
@@ -378,7 +358,7 @@ int mlg_salad_forward(const mlg_vit_weights* w, const mlg_salad_weights* sw, con
     hipStream_t s = (hipStream_t)stream;
     const int M = g.B * g.T;
     // SALAD._preprocess keeps the stored channel order (place_recognition.py:395-397)
-    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, /*swap_rb=*/0, ws, s));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, MLG_VIT_KEEP_CHANNELS, ws, s));
     MLG_TRY(mlg_layernorm_bf16(ws.x, w->norm_w, w->norm_b, ws.xn, M, s));  // backbone norm_layer, all tokens
     MLG_TRY(mlg_gemm_bias_relu_bf16(ws.xn, 768, sw->w1, sw->b1, ws.h, 1024, 1024, M, 1024, 768, s));
     float* y = ws.x;  // [M, 256]
@@ -412,8 +392,7 @@ int mlg_anyloc_forward(const mlg_vit_weights* w, const mlg_vlad_vocab* vocab, co
     AnylocBufs b;
     if (anyloc_carve(g, vocab->num_clusters, workspace, &b) > workspace_bytes) return MLG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s,
-                      (flags & MLG_VIT_SPLIT) ? 1 : 0));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, flags, b.vit, s));
     MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, b.tokens, b.vit.partial, b.pooled, g.B, g.T,
                                /*mean_pool=*/1, s));
     return mlg_vlad_run(vocab->centers, vocab->num_clusters, b.tokens, B, g.T - 2, b.head, b.head_bytes, desc, nullptr,
@@ -451,7 +430,7 @@ int mlg_crica_forward(const mlg_vit_weights* w, const mlg_crica_weights* cw, con
     if (!need) return MLG_EINVAL;
     if (need > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, b.vit, s, 1));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, flags, b.vit, s));  // MLG_VIT_SPLIT: checked above
     MLG_TRY(mlg_crica_pool_run(b.vit.x, w->norm_w, w->norm_b, g.B, g.grid, cw->gem_p, b.pooled, s));
     if (local_out_or_null)  // the rerank cache: mlg_vit_forward's local features from this forward
         MLG_TRY(mlg_final_norm_gem(b.vit.x, w->norm_w, w->norm_b, local_out_or_null, b.vit.partial, b.gem, g.B, g.T,
@@ -467,7 +446,7 @@ int mlg_op_vit_trunk(const mlg_vit_weights* w, const uint8_t* frames, int B, int
     VitWorkspace ws;
     if (carve(g, workspace, &ws) > workspace_bytes) return MLG_ENOMEM;
     hipStream_t s = (hipStream_t)stream;
-    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, (flags & MLG_VIT_KEEP_CHANNELS) ? 0 : 1, ws, s, 1));
+    MLG_TRY(vit_trunk(net_of(w), frames, g, H, W, C, frame_stride, flags, ws, s));  // MLG_VIT_SPLIT: checked above
     if (hipMemcpyAsync(tokens_prenorm, ws.x, (size_t)g.B * g.T * 768 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
         hipSuccess)
         return MLG_EHIP;

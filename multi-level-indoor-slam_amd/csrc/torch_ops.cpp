@@ -63,6 +63,27 @@ Tensor workspace(size_t bytes, const Tensor& like) {
     return t;
 }
 
+// ------------------------------------------------------------ frame batches
+// frames uint8 [B, H, W, C], contiguous, on the device; stride: bytes from one frame to the next
+struct Frames {
+    const uint8_t* p;
+    int64_t B;
+    int H, W, C;
+    long stride;
+};
+Frames frames_of(const Tensor& frames) {
+    want(frames, at::kByte, "frames");
+    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    const int64_t H = frames.size(1), W = frames.size(2), C = frames.size(3);
+    return {cp<uint8_t>(frames), frames.size(0), (int)H, (int)W, (int)C, (long)(H * W * C)};
+}
+
+// call(b0, nb), an ABI call `what` on frames [b0, b0 + nb), for each run of at most `step` of B frames
+template <class Call>
+void for_chunks(int64_t B, int64_t step, const char* what, Call call) {
+    for (int64_t b0 = 0; b0 < B; b0 += step) check_rc(call(b0, (int)std::min(step, B - b0)), what);
+}
+
 // ------------------------------------------------------------ weight lists
 // Fill the pointer fields of *strukt from the list through its table (weight_tables.h).
 // dev: the device the op launches on (the list must live there); none: any one device.
@@ -85,6 +106,9 @@ void fill_weights(const wt::Table& table, const char* model, at::TensorList w, v
     TORCH_CHECK(!dev.has_value() || (!w.empty() && w[0].device() == *dev), model, " weights must be on ", *dev);
 }
 
+// tokens of a ViT list of width `embed`, from the list's own `pos` (the ops take it from image_size)
+int64_t tokens_of(at::TensorList w, int64_t embed) { return w.size() > 3 && w[3].defined() ? w[3].numel() / embed : 0; }
+
 // ------------------------------------------------------------------ ViT-B/14
 // split: weights packed for MLG_VIT_SPLIT ([W_hi | W_lo], 2x the reduction dim)
 mlg_vit_weights vit_weights(at::TensorList w, bool split, int64_t image_size, c10::Device dev) {
@@ -95,35 +119,44 @@ mlg_vit_weights vit_weights(at::TensorList w, bool split, int64_t image_size, c1
     return s;
 }
 
+// What vit_forward_into and dino_forward_into share once their weight struct is filled: desc
+// f32 [B, embed] and local f32 [B, n_local, embed] (or none) are checked and written in calls
+// of at most max_batch frames.  ws_bytes(nb): the workspace of nb frames; forward(frames, nb,
+// ws, desc, local): the ABI call on one chunk.
+template <class WsBytes, class Forward>
+void forward_into(const Tensor& frames, const Frames& f, int64_t embed, int64_t image_size, int64_t max_batch,
+                  const Tensor& desc, const c10::optional<Tensor>& local, const char* what, WsBytes ws_bytes,
+                  Forward forward) {
+    want(desc, at::kFloat, "desc");
+    TORCH_CHECK(desc.dim() == 2 && desc.size(0) == f.B && desc.size(1) == embed, "desc must be [B, ", embed, "]");
+    const int64_t grid = image_size / 14, n_local = grid * grid - 1;
+    const bool has_local = local.has_value() && local->defined();
+    if (has_local) {
+        want(*local, at::kFloat, "local");
+        TORCH_CHECK(local->dim() == 3 && local->size(0) == f.B && local->size(1) == n_local &&
+                        local->size(2) == embed, "local must be [B, (S/14)^2 - 1, ", embed, "]");
+    }
+    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    c10::DeviceGuard g(frames.device());
+    const Tensor ws = workspace(ws_bytes((int)std::min(f.B, max_batch)), frames);
+    for_chunks(f.B, max_batch, what, [&](int64_t b0, int nb) {
+        return forward(f.p + b0 * f.stride, nb, ws, mp<float>(desc) + b0 * embed,
+                       has_local ? mp<float>(*local) + b0 * n_local * embed : nullptr);
+    });
+}
+
 // frames uint8 [B, H, W, C]; writes desc f32 [B, 768] and local f32 [B, n_local, 768]
 void vit_forward_into(const Tensor& frames, at::TensorList w, int64_t image_size, int64_t flags, int64_t max_batch,
                       const Tensor& desc, const c10::optional<Tensor>& local) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    want(desc, at::kFloat, "desc");
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
-    TORCH_CHECK(desc.dim() == 2 && desc.size(0) == B && desc.size(1) == MLG_VIT_EMBED, "desc must be [B, 768]");
-    const int64_t grid = image_size / 14, n_local = grid * grid - 1;
-    if (local.has_value() && local->defined()) {
-        want(*local, at::kFloat, "local");
-        TORCH_CHECK(local->dim() == 3 && local->size(0) == B && local->size(1) == n_local &&
-                        local->size(2) == MLG_VIT_EMBED, "local must be [B, (S/14)^2 - 1, 768]");
-    }
-    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
+    const Frames f = frames_of(frames);
     const mlg_vit_weights s = vit_weights(w, (flags & MLG_VIT_SPLIT) != 0, image_size, frames.device());
-    c10::DeviceGuard g(frames.device());
-    const int64_t nb_max = std::min(B, max_batch);
-    Tensor ws = workspace(mlg_vit_workspace_bytes((int)nb_max, (int)image_size), frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        float* lo = (local.has_value() && local->defined()) ? mp<float>(*local) + b0 * n_local * MLG_VIT_EMBED
-                                                           : nullptr;
-        check_rc(mlg_vit_forward(&s, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                 (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
-                                 mp<float>(desc) + b0 * MLG_VIT_EMBED, lo, stream_of(frames)),
-                 "mlg_vit_forward");
-    }
+    forward_into(
+        frames, f, MLG_VIT_EMBED, image_size, max_batch, desc, local, "mlg_vit_forward",
+        [&](int nb) { return mlg_vit_workspace_bytes(nb, (int)image_size); },
+        [&](const uint8_t* fr, int nb, const Tensor& ws, float* d, float* lo) {
+            return mlg_vit_forward(&s, fr, nb, f.H, f.W, f.C, f.stride, (int)image_size, (int)flags, ws.data_ptr(),
+                                   (size_t)ws.numel(), d, lo, stream_of(frames));
+        });
 }
 
 // ------------------------------------------------------- DINOv2 ViT-S / B / L-14
@@ -149,67 +182,43 @@ void dino_weights(wt::DinoFlat& f, at::TensorList w, bool split, int64_t tokens,
 // [B, n_local, embed]
 void dino_forward_into(const Tensor& frames, at::TensorList w, int64_t embed, int64_t image_size, int64_t flags,
                        int64_t max_batch, const Tensor& desc, const c10::optional<Tensor>& local) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
-    want(desc, at::kFloat, "desc");
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
-    dino_depth(embed);
-    TORCH_CHECK(desc.dim() == 2 && desc.size(0) == B && desc.size(1) == embed, "desc must be [B, ", embed, "]");
-    const int64_t grid = image_size / 14, n_local = grid * grid - 1;
-    if (local.has_value() && local->defined()) {
-        want(*local, at::kFloat, "local");
-        TORCH_CHECK(local->dim() == 3 && local->size(0) == B && local->size(1) == n_local && local->size(2) == embed,
-                    "local must be [B, (S/14)^2 - 1, ", embed, "]");
-    }
-    TORCH_CHECK(max_batch > 0, "max_batch must be positive");
-    wt::DinoFlat f;
-    dino_weights(f, w, (flags & MLG_VIT_SPLIT) != 0, 1 + grid * grid, embed, frames.device());
-    c10::DeviceGuard g(frames.device());
-    const int64_t nb_max = std::min(B, max_batch);
-    Tensor ws = workspace(mlg_dino_workspace_bytes((int)embed, (int)nb_max, (int)image_size), frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        float* lo = (local.has_value() && local->defined()) ? mp<float>(*local) + b0 * n_local * embed : nullptr;
-        check_rc(mlg_dino_forward(&f.w, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                  (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
-                                  mp<float>(desc) + b0 * embed, lo, stream_of(frames)),
-                 "mlg_dino_forward");
-    }
+    const Frames f = frames_of(frames);
+    const int64_t grid = image_size / 14;
+    wt::DinoFlat d;
+    dino_weights(d, w, (flags & MLG_VIT_SPLIT) != 0, 1 + grid * grid, embed, frames.device());
+    forward_into(
+        frames, f, embed, image_size, max_batch, desc, local, "mlg_dino_forward",
+        [&](int nb) { return mlg_dino_workspace_bytes((int)embed, nb, (int)image_size); },
+        [&](const uint8_t* fr, int nb, const Tensor& ws, float* out, float* lo) {
+            return mlg_dino_forward(&d.w, fr, nb, f.H, f.W, f.C, f.stride, (int)image_size, (int)flags, ws.data_ptr(),
+                                    (size_t)ws.numel(), out, lo, stream_of(frames));
+        });
 }
 
-// weights_check for a dino list (any one device, host included); the token count comes from
-// the list's own `pos`
+// weights_check for a dino list (any one device, host included)
 void dino_weights_check(at::TensorList w, int64_t embed, bool split) {
     dino_depth(embed);
-    const int64_t tokens = w.size() > 3 && w[3].defined() ? w[3].numel() / embed : 0;
     wt::DinoFlat f;
-    dino_weights(f, w, split, tokens, embed, c10::nullopt);
+    dino_weights(f, w, split, tokens_of(w, embed), embed, c10::nullopt);
 }
 
 // SALAD: frames uint8 [B, H, W, C] -> desc f32 [B, 8448]
 Tensor salad_forward(const Tensor& frames, at::TensorList w, at::TensorList salad, double dust_bin,
                      int64_t image_size, int64_t max_batch) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    const Frames f = frames_of(frames);
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const mlg_vit_weights s = vit_weights(w, false, image_size, frames.device());
     mlg_salad_weights sw = MLG_STRUCT_INIT(mlg_salad_weights);
     fill_weights(wt::salad_table(), "salad", salad, &sw, frames.device());
     sw.dust_bin = (float)dust_bin;
     c10::DeviceGuard g(frames.device());
-    Tensor desc = at::empty({B, MLG_SALAD_DIM}, frames.options().dtype(at::kFloat));
-    const int64_t nb_max = std::min(B, max_batch);
-    Tensor ws = workspace(mlg_salad_workspace_bytes((int)nb_max, (int)image_size), frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        check_rc(mlg_salad_forward(&s, &sw, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                   (int)image_size, ws.data_ptr(), (size_t)ws.numel(),
-                                   mp<float>(desc) + b0 * MLG_SALAD_DIM, stream_of(frames)),
-                 "mlg_salad_forward");
-    }
+    Tensor desc = at::empty({f.B, MLG_SALAD_DIM}, frames.options().dtype(at::kFloat));
+    Tensor ws = workspace(mlg_salad_workspace_bytes((int)std::min(f.B, max_batch), (int)image_size), frames);
+    for_chunks(f.B, max_batch, "mlg_salad_forward", [&](int64_t b0, int nb) {
+        return mlg_salad_forward(&s, &sw, f.p + b0 * f.stride, nb, f.H, f.W, f.C, f.stride, (int)image_size,
+                                 ws.data_ptr(), (size_t)ws.numel(), mp<float>(desc) + b0 * MLG_SALAD_DIM,
+                                 stream_of(frames));
+    });
     return desc;
 }
 
@@ -611,25 +620,18 @@ Tensor pillow_resize_224(const Tensor& frames) {
 // ------------------------------------------------------------------ MixVPR
 // frames uint8 [B, H, W, C] -> desc f32 [B, 4096]
 Tensor mixvpr_forward(const Tensor& frames, at::TensorList trunk, at::TensorList head, int64_t max_batch) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4, "frames must be [B, H, W, C]");
+    const Frames f = frames_of(frames);
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
     mlg_mixvpr_weights s = MLG_STRUCT_INIT(mlg_mixvpr_weights);
     fill_weights(wt::mixvpr_trunk_table(), "mixvpr trunk", trunk, &s, frames.device());
     fill_weights(wt::mixvpr_head_table(), "mixvpr head", head, &s, frames.device());
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     c10::DeviceGuard g(frames.device());
-    Tensor desc = at::empty({B, MLG_MIXVPR_DIM}, frames.options().dtype(at::kFloat));
-    const int64_t nb_max = std::min(B, max_batch);
-    Tensor ws = workspace(mlg_mixvpr_workspace_bytes((int)nb_max, (int)H, (int)W), frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        check_rc(mlg_mixvpr_forward(&s, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                    ws.data_ptr(), (size_t)ws.numel(), mp<float>(desc) + b0 * MLG_MIXVPR_DIM,
-                                    stream_of(frames)),
-                 "mlg_mixvpr_forward");
-    }
+    Tensor desc = at::empty({f.B, MLG_MIXVPR_DIM}, frames.options().dtype(at::kFloat));
+    Tensor ws = workspace(mlg_mixvpr_workspace_bytes((int)std::min(f.B, max_batch), f.H, f.W), frames);
+    for_chunks(f.B, max_batch, "mlg_mixvpr_forward", [&](int64_t b0, int nb) {
+        return mlg_mixvpr_forward(&s, f.p + b0 * f.stride, nb, f.H, f.W, f.C, f.stride, ws.data_ptr(),
+                                  (size_t)ws.numel(), mp<float>(desc) + b0 * MLG_MIXVPR_DIM, stream_of(frames));
+    });
     return desc;
 }
 
@@ -695,28 +697,23 @@ std::tuple<Tensor, Tensor> vlad(const Tensor& tokens, const Tensor& centers) {
 // frames uint8 [B, H, W, C] -> desc f32 [B, K * 768]
 Tensor anyloc_forward(const Tensor& frames, at::TensorList w, const Tensor& centers, int64_t image_size,
                       int64_t flags, int64_t max_batch) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    const Frames f = frames_of(frames);
+    TORCH_CHECK(f.B > 0, "frames must be [B, H, W, C]");
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
     const mlg_vit_weights s = vit_weights(w, (flags & MLG_VIT_SPLIT) != 0, image_size, frames.device());
     const mlg_vlad_vocab v = vlad_vocab(centers);
     TORCH_CHECK(centers.device() == frames.device(), "centers and frames must be on one device");
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const int64_t D = centers.size(0) * MLG_VIT_EMBED;
     c10::DeviceGuard g(frames.device());
-    Tensor desc = at::empty({B, D}, frames.options().dtype(at::kFloat));
-    const int64_t nb_max = std::min(B, max_batch);
-    const size_t nbytes = mlg_anyloc_workspace_bytes((int)nb_max, (int)image_size, v.num_clusters);
+    Tensor desc = at::empty({f.B, D}, frames.options().dtype(at::kFloat));
+    const size_t nbytes = mlg_anyloc_workspace_bytes((int)std::min(f.B, max_batch), (int)image_size, v.num_clusters);
     TORCH_CHECK(nbytes > 0, "anyloc_forward: unsupported image_size / batch");
     Tensor ws = workspace(nbytes, frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        check_rc(mlg_anyloc_forward(&s, &v, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                    (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
-                                    mp<float>(desc) + b0 * D, stream_of(frames)),
-                 "mlg_anyloc_forward");
-    }
+    for_chunks(f.B, max_batch, "mlg_anyloc_forward", [&](int64_t b0, int nb) {
+        return mlg_anyloc_forward(&s, &v, f.p + b0 * f.stride, nb, f.H, f.W, f.C, f.stride, (int)image_size,
+                                  (int)flags, ws.data_ptr(), (size_t)ws.numel(), mp<float>(desc) + b0 * D,
+                                  stream_of(frames));
+    });
     return desc;
 }
 
@@ -758,57 +755,49 @@ mlg_crica_weights crica_weights(at::TensorList head, double gem_p, c10::Device d
 std::tuple<Tensor, Tensor> crica_forward(const Tensor& frames, at::TensorList w, at::TensorList head, double gem_p,
                                          int64_t image_size, int64_t flags, int64_t group, int64_t max_batch,
                                          bool with_local) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    const Frames f = frames_of(frames);
+    TORCH_CHECK(f.B > 0, "frames must be [B, H, W, C]");
     TORCH_CHECK(group >= 1 && group <= MLG_CRICA_MAX_GROUP, "group must be in 1 .. ", MLG_CRICA_MAX_GROUP);
     TORCH_CHECK(max_batch >= group, "max_batch must hold one group");
     TORCH_CHECK(flags & MLG_VIT_SPLIT, "crica_forward runs the split-bf16 trunk (MLG_VIT_SPLIT)");
     const mlg_vit_weights s = vit_weights(w, true, image_size, frames.device());
     const mlg_crica_weights cw = crica_weights(head, gem_p, frames.device());
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const int64_t grid = image_size / 14, n_local = grid * grid - 1;
     const int64_t step = std::min<int64_t>(max_batch / group * group, MLG_CRICA_MAX_BATCH / group * group);
     c10::DeviceGuard g(frames.device());
-    Tensor desc = at::empty({B, MLG_CRICA_DIM}, frames.options().dtype(at::kFloat));
-    Tensor local = at::empty({with_local ? B : 0, n_local, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
-    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(B, step), (int)image_size);
+    Tensor desc = at::empty({f.B, MLG_CRICA_DIM}, frames.options().dtype(at::kFloat));
+    Tensor local = at::empty({with_local ? f.B : 0, n_local, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
+    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(f.B, step), (int)image_size);
     TORCH_CHECK(nbytes > 0, "crica_forward: unsupported image_size / batch");
     Tensor ws = workspace(nbytes, frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += step) {
-        const int nb = (int)std::min(step, B - b0);
-        check_rc(mlg_crica_forward(&s, &cw, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                   (int)image_size, (int)flags, (int)group, ws.data_ptr(), (size_t)ws.numel(),
-                                   mp<float>(desc) + b0 * MLG_CRICA_DIM,
-                                   with_local ? mp<float>(local) + b0 * n_local * MLG_VIT_EMBED : nullptr,
-                                   stream_of(frames)),
-                 "mlg_crica_forward");
-    }
+    for_chunks(f.B, step, "mlg_crica_forward", [&](int64_t b0, int nb) {
+        return mlg_crica_forward(&s, &cw, f.p + b0 * f.stride, nb, f.H, f.W, f.C, f.stride, (int)image_size,
+                                 (int)flags, (int)group, ws.data_ptr(), (size_t)ws.numel(),
+                                 mp<float>(desc) + b0 * MLG_CRICA_DIM,
+                                 with_local ? mp<float>(local) + b0 * n_local * MLG_VIT_EMBED : nullptr,
+                                 stream_of(frames));
+    });
     return {desc, local};
 }
 
 // The trunk's residual stream before the final LayerNorm: f32 [B, 1 + (S/14)^2, 768]
 Tensor vit_trunk(const Tensor& frames, at::TensorList w, int64_t image_size, int64_t flags, int64_t max_batch) {
-    want(frames, at::kByte, "frames");
-    TORCH_CHECK(frames.dim() == 4 && frames.size(0) > 0, "frames must be [B, H, W, C]");
+    const Frames f = frames_of(frames);
+    TORCH_CHECK(f.B > 0, "frames must be [B, H, W, C]");
     TORCH_CHECK(max_batch > 0, "max_batch must be positive");
     TORCH_CHECK(flags & MLG_VIT_SPLIT, "vit_trunk runs the split-bf16 trunk (MLG_VIT_SPLIT)");
     const mlg_vit_weights s = vit_weights(w, true, image_size, frames.device());
-    const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2), C = frames.size(3);
     const int64_t grid = image_size / 14, T = grid * grid + 1;
     c10::DeviceGuard g(frames.device());
-    Tensor tokens = at::empty({B, T, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
-    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(B, max_batch), (int)image_size);
+    Tensor tokens = at::empty({f.B, T, MLG_VIT_EMBED}, frames.options().dtype(at::kFloat));
+    const size_t nbytes = mlg_vit_workspace_bytes((int)std::min(f.B, max_batch), (int)image_size);
     TORCH_CHECK(nbytes > 0, "vit_trunk: unsupported image_size / batch");
     Tensor ws = workspace(nbytes, frames);
-    const long stride = (long)(H * W * C);
-    for (int64_t b0 = 0; b0 < B; b0 += max_batch) {
-        const int nb = (int)std::min(max_batch, B - b0);
-        check_rc(mlg_op_vit_trunk(&s, cp<uint8_t>(frames) + b0 * stride, nb, (int)H, (int)W, (int)C, stride,
-                                  (int)image_size, (int)flags, ws.data_ptr(), (size_t)ws.numel(),
-                                  mp<float>(tokens) + b0 * T * MLG_VIT_EMBED, stream_of(frames)),
-                 "mlg_op_vit_trunk");
-    }
+    for_chunks(f.B, max_batch, "mlg_op_vit_trunk", [&](int64_t b0, int nb) {
+        return mlg_op_vit_trunk(&s, f.p + b0 * f.stride, nb, f.H, f.W, f.C, f.stride, (int)image_size, (int)flags,
+                                ws.data_ptr(), (size_t)ws.numel(), mp<float>(tokens) + b0 * T * MLG_VIT_EMBED,
+                                stream_of(frames));
+    });
     return tokens;
 }
 
@@ -931,10 +920,8 @@ void weights_check(std::string model, at::TensorList w) {
                  {"mixvpr_head", "mixvpr head", wt::mixvpr_head_table}};
     for (const auto& f : fixed)
         if (model == f.model) return fill_weights(f.table(), f.what, w, &s, any);
-    if (model == "vit" || model == "vit_split") {
-        const int64_t tokens = w.size() > 3 && w[3].defined() ? w[3].numel() / MLG_VIT_EMBED : 0;
-        return fill_weights(wt::vit_table(model == "vit_split", tokens), "vit", w, &s, any);
-    }
+    if (model == "vit" || model == "vit_split")
+        return fill_weights(wt::vit_table(model == "vit_split", tokens_of(w, MLG_VIT_EMBED)), "vit", w, &s, any);
     TORCH_CHECK(model == "loftr", "weights_check: unknown model '", model, "'");
     loftr_weights(w, any);
 }

@@ -2,6 +2,8 @@
 // operators of torch_ops.cpp take for it, and the one function that fills a struct from such a
 // list.  The table is the list order: entry i names the field tensor i lands in, its element
 // kind and the element count of the layout documented beside the field in mlgate.h.
+// The DINOv2 ViT list is described once (add_vit); ViT-B's vit_table is that description at
+// (768, 12) over mlg_vit_weights, dino_table the same over mlg_dino_weights at any hub width.
 // Plain C++17 over mlgate.h, model_shapes.h and the standard library (no torch, no HIP), so
 // tests/native/weight_tables_test.cpp checks it stand-alone.
 #pragma once
@@ -101,36 +103,50 @@ inline const Table& built_once_per(const Key& key, F build) {
     return it->second;
 }
 
-// split: MLG_VIT_SPLIT packing ([W_hi | W_lo]: 2x the GEMM weights); tokens = 1 + (S/14)^2
+// rows of a split-packed GEMM weight with n output rows: the split GEMM's 256-column tile
+// (mlgate.h: zero rows up to the next multiple of 256; only ViT-S has such weights)
+inline int64_t split_rows(int64_t n) { return (n + 255) / 256 * 256; }
+
+// The one description of a DINOv2 ViT list: patch_w, patch_b, cls, pos, `depth` x the fourteen
+// fields of mlg_vit_block, norm_w, norm_b, for a network of width E.  W holds the six net-level
+// fields (mlg_vit_weights or mlg_dino_weights) and lies at byte `base`; block 0 lies at byte
+// `blocks`.  split: MLG_VIT_SPLIT packing ([W_hi | W_lo]: 2x the GEMM weights, rows padded to
+// split_rows); tokens = 1 + (S/14)^2
+template <class W>
+inline void add_vit(Table& t, size_t base, size_t blocks, bool split, int64_t tokens, int64_t E, int depth) {
+    using B = mlg_vit_block;
+    const int64_t m = split ? 2 : 1;
+    const auto rows = [=](int64_t n) { return split ? split_rows(n) : n; };
+    WT_FIELD(t, base, "", W, patch_w, BF16, rows(E) * MLG_VIT_PATCH_K * m);
+    WT_FIELD(t, base, "", W, patch_b, F32, E);
+    WT_FIELD(t, base, "", W, cls, F32, E);
+    WT_FIELD(t, base, "", W, pos, F32, tokens * E);
+    for (int i = 0; i < depth; ++i) {
+        const size_t o = blocks + i * sizeof(B);
+        const std::string p = at("blocks", i) + ".";
+        WT_FIELD(t, o, p, B, norm1_w, F32, E);
+        WT_FIELD(t, o, p, B, norm1_b, F32, E);
+        WT_FIELD(t, o, p, B, qkv_w, BF16, rows(3 * E) * E * m);
+        WT_FIELD(t, o, p, B, qkv_b, F32, 3 * E);
+        WT_FIELD(t, o, p, B, proj_w, BF16, rows(E) * E * m);
+        WT_FIELD(t, o, p, B, proj_b, F32, E);
+        WT_FIELD(t, o, p, B, ls1, F32, E);
+        WT_FIELD(t, o, p, B, norm2_w, F32, E);
+        WT_FIELD(t, o, p, B, norm2_b, F32, E);
+        WT_FIELD(t, o, p, B, fc1_w, BF16, rows(4 * E) * E * m);
+        WT_FIELD(t, o, p, B, fc1_b, F32, 4 * E);
+        WT_FIELD(t, o, p, B, fc2_w, BF16, rows(E) * 4 * E * m);
+        WT_FIELD(t, o, p, B, fc2_b, F32, E);
+        WT_FIELD(t, o, p, B, ls2, F32, E);
+    }
+    WT_FIELD(t, base, "", W, norm_w, F32, E);
+    WT_FIELD(t, base, "", W, norm_b, F32, E);
+}
+
+// ViT-B/14 over mlg_vit_weights: the general description at (768, 12), its blocks inline
 inline const Table& vit_table(bool split, int64_t tokens) {
     return built_once_per(std::make_pair(split, tokens), [=](Table& t) {
-        using W = mlg_vit_weights;
-        using B = mlg_vit_block;
-        const int64_t m = split ? 2 : 1, E = MLG_VIT_EMBED;
-        WT_FIELD(t, 0, "", W, patch_w, BF16, E * MLG_VIT_PATCH_K * m);
-        WT_FIELD(t, 0, "", W, patch_b, F32, E);
-        WT_FIELD(t, 0, "", W, cls, F32, E);
-        WT_FIELD(t, 0, "", W, pos, F32, tokens * E);
-        for (int i = 0; i < MLG_VIT_DEPTH; ++i) {
-            const size_t o = offsetof(W, blocks) + i * sizeof(B);
-            const std::string p = at("blocks", i) + ".";
-            WT_FIELD(t, o, p, B, norm1_w, F32, E);
-            WT_FIELD(t, o, p, B, norm1_b, F32, E);
-            WT_FIELD(t, o, p, B, qkv_w, BF16, 3 * E * E * m);
-            WT_FIELD(t, o, p, B, qkv_b, F32, 3 * E);
-            WT_FIELD(t, o, p, B, proj_w, BF16, E * E * m);
-            WT_FIELD(t, o, p, B, proj_b, F32, E);
-            WT_FIELD(t, o, p, B, ls1, F32, E);
-            WT_FIELD(t, o, p, B, norm2_w, F32, E);
-            WT_FIELD(t, o, p, B, norm2_b, F32, E);
-            WT_FIELD(t, o, p, B, fc1_w, BF16, 4 * E * E * m);
-            WT_FIELD(t, o, p, B, fc1_b, F32, 4 * E);
-            WT_FIELD(t, o, p, B, fc2_w, BF16, E * 4 * E * m);
-            WT_FIELD(t, o, p, B, fc2_b, F32, E);
-            WT_FIELD(t, o, p, B, ls2, F32, E);
-        }
-        WT_FIELD(t, 0, "", W, norm_w, F32, E);
-        WT_FIELD(t, 0, "", W, norm_b, F32, E);
+        add_vit<mlg_vit_weights>(t, 0, offsetof(mlg_vit_weights, blocks), split, tokens, MLG_VIT_EMBED, MLG_VIT_DEPTH);
     });
 }
 
@@ -141,42 +157,11 @@ struct DinoFlat {
     mlg_vit_block blocks[MLG_DINO_MAX_DEPTH];
 };
 
-// rows of a split-packed GEMM weight with n output rows: the split GEMM's 256-column tile
-// (mlgate.h: zero rows up to the next multiple of 256; only ViT-S has such weights)
-inline int64_t split_rows(int64_t n) { return (n + 255) / 256 * 256; }
-
-// vit_table for a network of width `embed` and `depth` blocks, over DinoFlat
+// the network of width `embed` and `depth` blocks, over DinoFlat
 inline const Table& dino_table(bool split, int64_t tokens, int64_t embed, int depth) {
     return built_once_per(std::make_tuple(split, tokens, embed, depth), [=](Table& t) {
-        using W = mlg_dino_weights;
-        using B = mlg_vit_block;
-        const int64_t m = split ? 2 : 1, E = embed;
-        const auto rows = [=](int64_t n) { return split ? split_rows(n) : n; };
-        const size_t w0 = offsetof(DinoFlat, w);
-        WT_FIELD(t, w0, "", W, patch_w, BF16, rows(E) * MLG_VIT_PATCH_K * m);
-        WT_FIELD(t, w0, "", W, patch_b, F32, E);
-        WT_FIELD(t, w0, "", W, cls, F32, E);
-        WT_FIELD(t, w0, "", W, pos, F32, tokens * E);
-        for (int i = 0; i < depth && i < MLG_DINO_MAX_DEPTH; ++i) {
-            const size_t o = offsetof(DinoFlat, blocks) + i * sizeof(B);
-            const std::string p = at("blocks", i) + ".";
-            WT_FIELD(t, o, p, B, norm1_w, F32, E);
-            WT_FIELD(t, o, p, B, norm1_b, F32, E);
-            WT_FIELD(t, o, p, B, qkv_w, BF16, rows(3 * E) * E * m);
-            WT_FIELD(t, o, p, B, qkv_b, F32, 3 * E);
-            WT_FIELD(t, o, p, B, proj_w, BF16, rows(E) * E * m);
-            WT_FIELD(t, o, p, B, proj_b, F32, E);
-            WT_FIELD(t, o, p, B, ls1, F32, E);
-            WT_FIELD(t, o, p, B, norm2_w, F32, E);
-            WT_FIELD(t, o, p, B, norm2_b, F32, E);
-            WT_FIELD(t, o, p, B, fc1_w, BF16, rows(4 * E) * E * m);
-            WT_FIELD(t, o, p, B, fc1_b, F32, 4 * E);
-            WT_FIELD(t, o, p, B, fc2_w, BF16, rows(E) * 4 * E * m);
-            WT_FIELD(t, o, p, B, fc2_b, F32, E);
-            WT_FIELD(t, o, p, B, ls2, F32, E);
-        }
-        WT_FIELD(t, w0, "", W, norm_w, F32, E);
-        WT_FIELD(t, w0, "", W, norm_b, F32, E);
+        add_vit<mlg_dino_weights>(t, offsetof(DinoFlat, w), offsetof(DinoFlat, blocks), split, tokens, embed,
+                                  depth < MLG_DINO_MAX_DEPTH ? depth : MLG_DINO_MAX_DEPTH);
     });
 }
 

@@ -176,7 +176,7 @@ class DeviceGate:
         from . import distributed as mdist
         from .lightglue import LightGlueGPU
         from .superpoint import SuperPointGPU
-        from .vit import DinoVit, VitB14
+        from .vit import engine_for
         from .weights import backbone_config, synthetic_state_dict
         self.torch, self.mdist = torch, mdist
         # the DINOv2 backbone: its width sizes the gather, descriptor and local-feature buffers
@@ -214,9 +214,7 @@ class DeviceGate:
         sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
         # vit_precise: the split-bf16 ViT (MLG_VIT_SPLIT), whose descriptors follow the fp32
         # network closely enough that the kNN ranks near-ties as the fp32 reference does
-        self.eng = (VitB14(sd, device=self.dev, max_batch=vit_batch, precise=vit_precise)
-                    if backbone == 'dinov2_vitb14' else
-                    DinoVit(sd, backbone=backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise))
+        self.eng = engine_for(sd, backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise)
         self.gather = mdist.RowGather(N, EMBED, world, self.dev)
         self.desc_loc = (self.gather.out[self.lo:self.hi] if world == 1
                          else torch.empty(self.n_local, EMBED, device=self.dev))

@@ -96,6 +96,8 @@ class VitB14:
     retrieval (DeviceGate, the CricaVPR / AnyLoc drop-ins); precise=False keeps the plain
     bf16 forward (3x fewer MFMA products; SALAD's trunk, A/B tools)."""
 
+    backbone, embed = DEFAULT_BACKBONE, EMBED  # DinoVit: the instance's
+
     def __init__(self, state_dict, device="cuda", image_size=322, max_batch=64, pool="gem", swap_rb=True,
                  precise=True):
         self.device = _native.require_device(device)
@@ -108,24 +110,22 @@ class VitB14:
         self.precise = bool(precise)
         self.flags = ((1 if pool == "mean" else 0) | (0 if swap_rb else 2)  # MLG_VIT_POOL_MEAN / KEEP_CHANNELS
                       | (MLG_VIT_SPLIT if self.precise else 0))
-        self._w = self._pack(state_dict)
+        self._w = pack_weights(state_dict, self.device, self.grid, self.precise, self.backbone)
 
-    def _pack(self, sd):
-        return pack_weights(sd, self.device, self.grid, self.precise)
+    def _op(self, frames, *rest):
+        """The forward operator on this engine's weights: all a subclass chooses."""
+        _native.ops().vit_forward_into(frames, self._w, *rest)
 
     # ------------------------------------------------------------ forward
     def forward_into(self, frames, desc_out, local_out=None):
         """frames: uint8 [B, H, W, C] device tensor (C = 1, 3 BGR or 4 BGRA; or [B, H, W]).
-        Writes float32 descriptors [B, 768] (and local features [B, n_local, 768]);
-        torch.ops.mlgate.vit_forward_into on the current stream."""
+        Writes float32 descriptors [B, embed] (and local features [B, n_local, embed]) on the
+        current stream: torch.ops.mlgate.vit_forward_into (DinoVit: dino_forward_into)."""
         if frames.dim() == 3:
             frames = frames.unsqueeze(-1)
         if frames.dtype != torch.uint8 or frames.device.type != "cuda":
             raise TypeError("frames must be a uint8 tensor on the HIP device")
-        _native.ops().vit_forward_into(frames.contiguous(), self._w, self.image_size, self.flags, self.max_batch,
-                                       desc_out, local_out)
-
-    embed = EMBED  # DinoVit: the backbone's
+        self._op(frames.contiguous(), self.image_size, self.flags, self.max_batch, desc_out, local_out)
 
     def forward(self, frames, with_local=False):
         B = frames.shape[0]
@@ -149,15 +149,16 @@ class DinoVit(VitB14):
         check_state_dict(state_dict, backbone)
         super().__init__(state_dict, **kwargs)
 
-    def _pack(self, sd):
-        return pack_weights(sd, self.device, self.grid, self.precise, self.backbone)
+    def _op(self, frames, *rest):
+        _native.ops().dino_forward_into(frames, self._w, self.embed, *rest)
 
-    def forward_into(self, frames, desc_out, local_out=None):
-        """VitB14.forward_into with descriptors [B, embed] and local features [B, n_local, embed];
-        torch.ops.mlgate.dino_forward_into on the current stream."""
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        _native.ops().dino_forward_into(frames.contiguous(), self._w, self.embed, self.image_size, self.flags,
-                                        self.max_batch, desc_out, local_out)
+
+def engine_for(state_dict, backbone=DEFAULT_BACKBONE, **kwargs):
+    """The engine of ``backbone``: VitB14 for dinov2_vitb14, DinoVit otherwise.  DinoVit at
+    dinov2_vitb14 gives the same bits, but ViT-B keeps its own entry point (vit_forward_into,
+    mlg_vit_forward over the inline mlg_vit_weights): it is the ABI that existing callers link
+    against, and tests/test_dino_backbones_gpu.py compares the two entry points bit for bit,
+    so the default pipeline must go on running the first."""
+    if backbone == DEFAULT_BACKBONE:
+        return VitB14(state_dict, **kwargs)
+    return DinoVit(state_dict, backbone=backbone, **kwargs)

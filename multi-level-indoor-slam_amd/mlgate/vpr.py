@@ -339,7 +339,7 @@ class _DinoEngineMixin:
 
     def _engine(self):
         if getattr(self, '_vit', None) is None:
-            from .vit import DinoVit, VitB14
+            from .vit import engine_for
             from .weights import backbone_config, resolve_state_dict
             embed = backbone_config(self.backbone_name)[0]  # ValueError lists the supported names
             sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None), backbone=self.backbone_name)
@@ -349,10 +349,8 @@ class _DinoEngineMixin:
                               "hub checkpoint for real descriptors).")
             # the split-bf16 forward (VitB14's default): descriptors within ~1e-11 of fp32,
             # so retrieval ranks as the fp32 reference does
-            kw = dict(device=self.device, image_size=self._image_size, pool=self._pool, swap_rb=self._swap_rb,
-                      precise=True)
-            self._vit = (VitB14(sd, **kw) if self.backbone_name == 'dinov2_vitb14'
-                         else DinoVit(sd, backbone=self.backbone_name, **kw))
+            self._vit = engine_for(sd, self.backbone_name, device=self.device, image_size=self._image_size,
+                                   pool=self._pool, swap_rb=self._swap_rb, precise=True)
             self.feat_dim = embed
             self._model_loaded = True
         return self._vit

@@ -99,11 +99,19 @@ int main() {
     const wt::Table &vit = wt::vit_table(false, 530), &vits = wt::vit_table(true, 1370);
     const wt::Table &loftr = wt::loftr_table(0), &loftr_t = wt::loftr_table(123456);
     CHECK(&wt::vit_table(false, 530) == &vit && &wt::loftr_table(0) == &loftr);  // built once per parameter value
+    // the three hub networks over wt::DinoFlat: ViT-S split and plain, ViT-B, ViT-L
+    const wt::Table &dss = wt::dino_table(true, 530, 384, 12), &dsp = wt::dino_table(false, 530, 384, 12),
+                    &dbs = wt::dino_table(true, 530, 768, 12), &dls = wt::dino_table(true, 530, 1024, 24);
+    CHECK(&wt::dino_table(true, 530, 1024, 24) == &dls && &dss != &dsp);
+    const wt::Table& crica = wt::crica_table();
     const wt::Table &salad = wt::salad_table(), &sp = wt::sp_table(), &lg = wt::lg_table(), &sg = wt::sg_table(),
                     &rn = wt::rn_table(), &mxt = wt::mixvpr_trunk_table(), &mxh = wt::mixvpr_head_table();
 
     // ---- lengths: the list lengths of the operators
     CHECK(vit.size() == 174 && vits.size() == 174);
+    CHECK(dss.size() == 174 && dsp.size() == 174 && dbs.size() == 174 && wt::dino_table(false, 530, 768, 12).size() == 174);
+    CHECK(dls.size() == 342 && wt::dino_table(false, 530, 1024, 24).size() == 342);  // 4 + 14 x 24 + 2
+    CHECK(crica.size() == 24);
     CHECK(salad.size() == 8);
     CHECK(sp.size() == 24);
     CHECK(lg.size() == 234);  // 1 + 2 x 9 x 10 + 4 x 9 + 2 x 8 + 1
@@ -115,6 +123,24 @@ int main() {
     // ---- tiling
     check_tiling("vit", {&vit}, sizeof(mlg_vit_weights), {HEAD, TAIL_FROM(mlg_vit_weights, packing)});
     check_tiling("vit split", {&vits}, sizeof(mlg_vit_weights), {HEAD, TAIL_FROM(mlg_vit_weights, packing)});
+    {
+        // DinoFlat: mlg_dino_weights, whose `blocks` pointer is set after the fill, then the block array
+        using D = wt::DinoFlat;
+        using W = mlg_dino_weights;
+        static_assert(offsetof(D, w) == 0 && offsetof(D, blocks) == sizeof(W), "no padding between the two");
+        const std::vector<Span> others{HEAD, Span{offsetof(W, embed), offsetof(W, patch_w) - offsetof(W, embed)},
+                                       Span{offsetof(W, blocks), sizeof(void*)}, TAIL_FROM(W, packing)};
+        std::vector<Span> others12 = others;  // depth 12 leaves the upper twelve blocks alone
+        others12.push_back({offsetof(D, blocks) + 12 * sizeof(mlg_vit_block), 12 * sizeof(mlg_vit_block)});
+        static_assert(MLG_DINO_MAX_DEPTH == 24, "the unused blocks above");
+        check_tiling("dino ViT-S split", {&dss}, sizeof(D), others12);
+        check_tiling("dino ViT-S", {&dsp}, sizeof(D), others12);
+        check_tiling("dino ViT-B split", {&dbs}, sizeof(D), others12);
+        check_tiling("dino ViT-L split", {&dls}, sizeof(D), others);
+    }
+    check_tiling("crica", {&crica}, sizeof(mlg_crica_weights),
+                 {HEAD, Span{offsetof(mlg_crica_weights, gem_p),
+                             offsetof(mlg_crica_weights, layers) - offsetof(mlg_crica_weights, gem_p)}});
     check_tiling("salad", {&salad}, sizeof(mlg_salad_weights), {HEAD, TAIL_FROM(mlg_salad_weights, dust_bin)});
     check_tiling("superpoint", {&sp}, sizeof(mlg_sp_weights), {HEAD});
     check_tiling("lightglue", {&lg}, sizeof(mlg_lg_weights), {HEAD});
@@ -137,6 +163,38 @@ int main() {
     CHECK(vit[find(vit, "pos")].numel == 530 * 768 && vits[find(vits, "pos")].numel == 1370 * 768);
     CHECK(vit[find(vit, "blocks[0].qkv_w")].numel == 2304 * 768 && vits[find(vits, "blocks[0].qkv_w")].numel == 2 * 2304 * 768);
     CHECK(vits[find(vits, "patch_w")].numel == 2 * 768 * 768 && vits[find(vits, "blocks[11].fc2_b")].numel == 768);
+    // ViT-S split: GEMM weight rows padded to the split GEMM's 256-row tile, [W_hi | W_lo]; biases keep their count
+    CHECK(dss[find(dss, "patch_w")].numel == 512 * 768 * 2 && dss[find(dss, "blocks[0].qkv_w")].numel == 1280 * 384 * 2);
+    CHECK(dss[find(dss, "blocks[0].proj_w")].numel == 512 * 384 * 2 && dss[find(dss, "blocks[0].fc1_w")].numel == 1536 * 384 * 2);
+    CHECK(dss[find(dss, "blocks[0].fc2_w")].numel == 512 * 1536 * 2 && dss[find(dss, "blocks[0].qkv_b")].numel == 1152);
+    CHECK(dsp[find(dsp, "patch_w")].numel == 384 * 768 && dsp[find(dsp, "blocks[0].qkv_w")].numel == 1152 * 384);  // plain: none
+    CHECK(crica[find(crica, "layers[1].fc2_w")].numel == 768 * 2 * 2048);
+    // ViT-B's table is the general one at (768, 12): entry for entry the dino table, each field at its place
+    // in mlg_dino_weights (net level) or in the block array
+    for (const bool split : {false, true})
+        for (const int64_t tokens : {530, 1370}) {
+            const wt::Table &v = wt::vit_table(split, tokens), &d = wt::dino_table(split, tokens, 768, 12);
+            CHECK(v.size() == d.size());
+            const struct { const char* name; size_t off; } net[] = {
+                {"patch_w", offsetof(mlg_dino_weights, patch_w)}, {"patch_b", offsetof(mlg_dino_weights, patch_b)},
+                {"cls", offsetof(mlg_dino_weights, cls)},         {"pos", offsetof(mlg_dino_weights, pos)},
+                {"norm_w", offsetof(mlg_dino_weights, norm_w)},   {"norm_b", offsetof(mlg_dino_weights, norm_b)}};
+            size_t n_net = 0;
+            for (size_t i = 0; i < v.size() && i < d.size(); ++i) {
+                CHECK(!strcmp(v[i].name, d[i].name) && v[i].kind == d[i].kind && v[i].numel == d[i].numel &&
+                      v[i].optional == d[i].optional);
+                if (!strncmp(d[i].name, "blocks[", 7)) {
+                    CHECK(d[i].offset - offsetof(wt::DinoFlat, blocks) == v[i].offset - offsetof(mlg_vit_weights, blocks));
+                    continue;
+                }
+                for (const auto& f : net)
+                    if (!strcmp(d[i].name, f.name)) {
+                        CHECK(d[i].offset - offsetof(wt::DinoFlat, w) == f.off);
+                        ++n_net;
+                    }
+            }
+            CHECK(n_net == 6);
+        }
     CHECK(sp[find(sp, "w[8]")].numel == 128 * 256 && sp[find(sp, "b[8]")].numel == 128);
     CHECK(sp[find(sp, "w[3]")].numel == 128 * 9 * 64);
     CHECK(rn[find(rn, "blocks[0].w1")].numel == 128 * 64 && rn[find(rn, "blocks[0].wd")].numel == 256 * 64);
@@ -158,6 +216,26 @@ int main() {
         AT(vit, s, blocks[11].ls2, "blocks[11].ls2");
         AT(vit, s, norm_b, "norm_b");
         CHECK(s.patch_w == tag(0) && s.blocks[0].norm1_w == tag(4) && s.norm_b == tag(173));
+    }
+    {
+        const wt::DinoFlat s = filled<wt::DinoFlat>(dls);
+        AT(dls, s, w.patch_w, "patch_w");
+        AT(dls, s, w.pos, "pos");
+        AT(dls, s, blocks[0].norm1_w, "blocks[0].norm1_w");
+        AT(dls, s, blocks[12].qkv_w, "blocks[12].qkv_w");
+        AT(dls, s, blocks[23].ls2, "blocks[23].ls2");
+        AT(dls, s, w.norm_w, "norm_w");
+        CHECK(s.w.patch_w == tag(0) && s.blocks[23].ls2 == tag(339) && s.w.norm_b == tag(341));
+        CHECK(s.w.blocks == nullptr && s.w.embed == 0 && s.w.packing == 0);  // the caller's: left alone
+        const wt::DinoFlat s12 = filled<wt::DinoFlat>(dss);
+        CHECK(s12.blocks[11].ls2 == tag(171) && s12.blocks[12].norm1_w == nullptr && s12.w.norm_b == tag(173));
+    }
+    {
+        const mlg_crica_weights s = filled<mlg_crica_weights>(crica);
+        AT(crica, s, layers[0].in_w, "layers[0].in_w");
+        AT(crica, s, layers[0].ln2_b, "layers[0].ln2_b");
+        AT(crica, s, layers[1].fc2_w, "layers[1].fc2_w");
+        CHECK(s.layers[0].in_w == tag(0) && s.layers[1].in_w == tag(12) && s.layers[1].ln2_b == tag(23));
     }
     {
         const mlg_salad_weights s = filled<mlg_salad_weights>(salad);
@@ -309,6 +387,18 @@ int main() {
             mlg_lg_weights s;
             CHECK(wt::fill(lg, "test", d.data(), d.size(), &s).empty());
         }
+    }
+    {
+        // the ViT-L table: a list one block short, and a wrong count in the last block
+        static_assert(sizeof(wt::DinoFlat) <= 4096, "refuse() hands the filler 4096 bytes");
+        std::vector<wt::Desc> d = good(dls);
+        d.erase(d.begin() + 4 + 23 * 14, d.begin() + 4 + 24 * 14);
+        refuse(dls, d, -1, "expected 342 tensors, got 328");
+        const int i = find(dls, "blocks[23].fc2_w");
+        CHECK(i == 4 + 23 * 14 + 11);
+        d = good(dls);
+        d[i].numel = 768 * 3072 * 2;  // ViT-B's
+        refuse(dls, d, i, "with 8388608 elements, contiguous, on device 0 as weights[0]; got 4718592 elements");
     }
     {
         // ResNet's downsample slots: required in a stage's first block, empty = NULL elsewhere
