@@ -228,6 +228,17 @@ def require_device(device="cuda"):
     return dev
 
 
+def device_frames(frames):
+    """The frames argument of every descriptor engine: uint8 [B, H, W, C] (or [B, H, W], which
+    gets a channel axis) on the HIP device, made contiguous; TypeError otherwise."""
+    import torch
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(-1)
+    if frames.dtype != torch.uint8 or frames.device.type != "cuda":
+        raise TypeError("frames must be a uint8 tensor on the HIP device")
+    return frames.contiguous()
+
+
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 

@@ -48,21 +48,14 @@ class AnyLocGPU:
         self.num_clusters = c.shape[0]
         self.descriptor_dim = c.shape[0] * EMBED
 
-    def _frames(self, frames):
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        return frames.contiguous()
-
     def forward(self, frames):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, K * 768]."""
-        return _native.ops().anyloc_forward(self._frames(frames), self._vit._w, self.centers, self.image_size,
-                                            self._vit.flags, self.max_batch)
+        return _native.ops().anyloc_forward(_native.device_frames(frames), self._vit._w, self.centers,
+                                            self.image_size, self._vit.flags, self.max_batch)
 
     def tokens(self, frames):
         """The tokens VLAD aggregates: float32 [B, n_tokens, 768]."""
-        return self._vit.forward(self._frames(frames), with_local=True)[1]
+        return self._vit.forward(_native.device_frames(frames), with_local=True)[1]
 
     def vlad(self, tokens, with_labels=False):
         """The head alone: float32 [B, P, 768] device tokens -> [B, K * 768] (and int32 labels [B, P])."""

@@ -24,7 +24,7 @@ import torch
 
 from . import _native
 from .vit import VitB14, split_weight
-from .weights import CRICA_DIM, CRICA_LAYERS, CRICA_ROWS, EMBED, resolve_crica_state_dict
+from .weights import CRICA_DIM, CRICA_LAYERS, CRICA_ROWS, EMBED, given_or_resolved, sub_state_dict
 
 IMAGE_SIZE = 322
 MAX_GROUP = 32  # include/mlgate.h MLG_CRICA_MAX_GROUP
@@ -60,16 +60,12 @@ class CricaGPU:
 
     def __init__(self, state_dict=None, device="cuda", image_size=IMAGE_SIZE, max_batch=64, group=1,
                  pretrained_path=None):
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_crica_state_dict(pretrained_path)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("crica", state_dict, pretrained_path)
         self.group = check_group(group)
         if max_batch < self.group:
             raise ValueError(f"max_batch = {max_batch} does not hold one group of {self.group}")
-        backbone = {k[len("backbone."):]: v for k, v in state_dict.items() if k.startswith("backbone.")}
-        self._vit = VitB14(backbone, device=device, image_size=image_size, max_batch=max_batch, pool="gem",
-                           swap_rb=True, precise=True)
+        self._vit = VitB14(sub_state_dict(state_dict, "backbone."), device=device, image_size=image_size,
+                           max_batch=max_batch, pool="gem", swap_rb=True, precise=True)
         if self._vit.grid < 12:
             raise ValueError("image_size must be at least 168 (a 12 x 12 patch grid)")
         self.device = self._vit.device
@@ -78,25 +74,18 @@ class CricaGPU:
         self.descriptor_dim = CRICA_DIM
         self._head, self.gem_p = pack_head(state_dict, self.device)
 
-    def _frames(self, frames):
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        return frames.contiguous()
-
     def forward(self, frames, with_local=False):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, 10752]
         (and, from the same forward, the local features [B, n_local, 768] that
         ``VitB14.forward(frames, with_local=True)`` returns)."""
-        desc, local = _native.ops().crica_forward(self._frames(frames), self._vit._w, self._head, self.gem_p,
+        desc, local = _native.ops().crica_forward(_native.device_frames(frames), self._vit._w, self._head, self.gem_p,
                                                   self.image_size, self._vit.flags, self.group, self.max_batch,
                                                   bool(with_local))
         return (desc, local) if with_local else desc
 
     def trunk(self, frames):
         """The trunk's residual stream before the final LayerNorm: float32 [B, 1 + g^2, 768]."""
-        return _native.ops().vit_trunk(self._frames(frames), self._vit._w, self.image_size, self._vit.flags,
+        return _native.ops().vit_trunk(_native.device_frames(frames), self._vit._w, self.image_size, self._vit.flags,
                                        self.max_batch)
 
     def pool(self, tokens_prenorm):

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .weights import LG_LAYERS, resolve_lightglue_state_dict
+from .weights import LG_LAYERS, given_or_resolved
 
 PRUNING_MIN_KPTS_CUDA = 1536  # LightGlue.pruning_keypoint_thresholds['flash'] (CUDA + SDPA)
 BLOCK_ORDER = ("Wqkv", "bqkv", "Wout", "bout", "Wf1", "bf1", "ln_g", "ln_b", "Wf2", "bf2")  # mlg_lg_block
@@ -91,10 +91,7 @@ class LightGlueGPU:
     def __init__(self, state_dict=None, device="cuda", depth_confidence=0.95, width_confidence=0.99,
                  filter_threshold=0.1, pruning_min_kpts=PRUNING_MIN_KPTS_CUDA, weights_path=None, seed=0):
         self.device = _native.require_device(device)
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_lightglue_state_dict(weights_path, seed)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("lightglue", state_dict, weights_path, seed)
         self.depth_confidence = float(depth_confidence)
         self.width_confidence = float(width_confidence)
         self.filter_threshold = float(filter_threshold)

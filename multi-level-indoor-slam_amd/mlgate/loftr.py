@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .weights import resolve_loftr_state_dict
+from .weights import given_or_resolved
 
 D_C = 256
 # (name, BatchNorm prefix or None, cin, cout) in mlg_loftr_weights.conv_w order
@@ -119,10 +119,7 @@ class LoFTRGPU:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _native.MlgateError("LoFTR runs on the HIP device only (no CPU path)")
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_loftr_state_dict(seed=seed)
-        else:
-            self.weights_source = "caller"
+        state_dict, self.weights_source = given_or_resolved("loftr", state_dict, seed=seed, given="caller")
         self.ops = _native.ops()
         self.weights = weight_list(state_dict, self.device)
         # the fused coarse layer tails read their weights k-step packed: pack once here

@@ -19,7 +19,8 @@ import torch
 from . import _native
 from .lightglue import pack_kstep
 from .resnet import pack_trunk
-from .weights import MIXVPR_CHANNELS, MIXVPR_DEPTH, MIXVPR_HW, MIXVPR_ROWS, MIXVPR_STAGES, resolve_mixvpr_state_dict
+from .weights import (MIXVPR_CHANNELS, MIXVPR_DEPTH, MIXVPR_HW, MIXVPR_ROWS, MIXVPR_STAGES, given_or_resolved,
+                      sub_state_dict)
 
 IMAGE_SIZE = 320
 DESC_DIM = MIXVPR_CHANNELS * MIXVPR_ROWS
@@ -64,22 +65,14 @@ class MixVprGPU:
 
     def __init__(self, state_dict=None, device="cuda", max_batch=32, pretrained_path=None, seed=0):
         self.device = _native.require_device(device)
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_mixvpr_state_dict(pretrained_path, seed)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("mixvpr", state_dict, pretrained_path, seed)
         self.max_batch = max_batch
-        backbone = {k[len("backbone.model."):]: v for k, v in state_dict.items() if k.startswith("backbone.model.")}
-        self._trunk = pack_trunk(backbone, self.device, MIXVPR_STAGES)
+        self._trunk = pack_trunk(sub_state_dict(state_dict, "backbone.model."), self.device, MIXVPR_STAGES)
         self._head = head_list(state_dict, self.device)
 
     def forward(self, frames):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, 4096]."""
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        return _native.ops().mixvpr_forward(frames.contiguous(), self._trunk, self._head, self.max_batch)
+        return _native.ops().mixvpr_forward(_native.device_frames(frames), self._trunk, self._head, self.max_batch)
 
     def head(self, features):
         """features: float32 [B, 400, 1024] device tensor (layer3 output, NHWC) -> float32 [B, 4096]."""

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .weights import RESNET_STAGES, resolve_resnet50_state_dict
+from .weights import RESNET_STAGES, given_or_resolved
 
 BN_EPS = 1e-5
 
@@ -64,10 +64,7 @@ class ResNet50GPU:
 
     def __init__(self, state_dict=None, device="cuda", weights_path=None, seed=0):
         self.device = _native.require_device(device)
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_resnet50_state_dict(weights_path, seed)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("resnet50", state_dict, weights_path, seed)
         self._w = self._pack(state_dict)
 
     def _pack(self, sd):

@@ -18,7 +18,7 @@ import torch
 
 from . import _native
 from .vit import VitB14
-from .weights import SALAD_CLUSTER_DIM, SALAD_CLUSTERS, resolve_salad_state_dict
+from .weights import SALAD_CLUSTER_DIM, SALAD_CLUSTERS, given_or_resolved, sub_state_dict
 
 IMAGE_SIZE = 322  # SALAD's evaluation size; the hub PatchEmbed needs multiples of 14
 DESC_DIM = SALAD_CLUSTERS * SALAD_CLUSTER_DIM + 256
@@ -53,22 +53,15 @@ class SaladGPU:
     """Packed device weights for batched SALAD descriptor extraction."""
 
     def __init__(self, state_dict=None, device="cuda", max_batch=64, pretrained_path=None):
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_salad_state_dict(pretrained_path)
-        else:
-            self.weights_source = "given"
-        backbone = {k[len("backbone.model."):]: v for k, v in state_dict.items() if k.startswith("backbone.model.")}
-        self._vit = VitB14(backbone, device=device, image_size=IMAGE_SIZE, max_batch=max_batch, pool="gem",
-                           swap_rb=False, precise=False)  # mlg_salad_forward runs the plain bf16 trunk
+        state_dict, self.weights_source = given_or_resolved("salad", state_dict, pretrained_path)
+        self._vit = VitB14(sub_state_dict(state_dict, "backbone.model."), device=device, image_size=IMAGE_SIZE,
+                           max_batch=max_batch, pool="gem", swap_rb=False,
+                           precise=False)  # mlg_salad_forward runs the plain bf16 trunk
         self.device = self._vit.device
         self.max_batch = max_batch
         self._agg, self.dust_bin = aggregator_list(state_dict, self.device)
 
     def forward(self, frames):
         """frames: uint8 [B, H, W, C] (or [B, H, W]) device tensor -> float32 [B, 8448]."""
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        return _native.ops().salad_forward(frames.contiguous(), self._vit._w, self._agg, self.dust_bin, IMAGE_SIZE,
-                                           self.max_batch)
+        return _native.ops().salad_forward(_native.device_frames(frames), self._vit._w, self._agg, self.dust_bin,
+                                           IMAGE_SIZE, self.max_batch)

@@ -16,7 +16,7 @@ import torch
 
 from . import _native
 from .lightglue import pack_kstep
-from .weights import SG_KENC, SG_LAYERS, resolve_superglue_state_dict
+from .weights import SG_KENC, SG_LAYERS, given_or_resolved
 
 SINKHORN_ITERATIONS = 20
 MATCH_THRESHOLD = 0.2
@@ -70,10 +70,7 @@ class SuperGlueGPU:
     def __init__(self, state_dict=None, device="cuda", sinkhorn_iterations=SINKHORN_ITERATIONS,
                  match_threshold=MATCH_THRESHOLD, weights_path=None, seed=0):
         self.device = _native.require_device(device)
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_superglue_state_dict(weights_path, seed)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("superglue", state_dict, weights_path, seed)
         self.iters = int(sinkhorn_iterations)
         self.threshold = float(match_threshold)
         self.bin_score = float(np.asarray(state_dict["bin_score"], np.float32))

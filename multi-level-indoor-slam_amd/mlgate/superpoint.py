@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .weights import SUPERPOINT_LAYERS, resolve_superpoint_state_dict
+from .weights import SUPERPOINT_LAYERS, given_or_resolved
 
 DESC_DIM = 256
 _ORDER = ["conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa",
@@ -45,10 +45,7 @@ class SuperPointGPU:
     def __init__(self, state_dict=None, device="cuda", max_num_keypoints=2048, detection_threshold=0.001,
                  nms_radius=4, remove_borders=4, weights_path=None, seed=0):
         self.device = _native.require_device(device)
-        if state_dict is None:
-            state_dict, self.weights_source = resolve_superpoint_state_dict(weights_path, seed)
-        else:
-            self.weights_source = "given"
+        state_dict, self.weights_source = given_or_resolved("superpoint", state_dict, weights_path, seed)
         self.max_kp = int(max_num_keypoints)
         self.det_thr = float(detection_threshold)
         self.nms_radius = int(nms_radius)

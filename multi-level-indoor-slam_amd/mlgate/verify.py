@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import geometry
+from .vpr import _NativeSwitch
 
 
 @dataclass
@@ -47,6 +48,23 @@ def _rejected(query_idx, match_idx):
     return MatchResult(query_idx=query_idx, match_idx=match_idx, num_keypoints_query=0, num_keypoints_match=0,
                        num_matches=0, num_inliers=0, inlier_ratio=0.0, relative_pose=None, essential_matrix=None,
                        confidence=0.0, is_valid=False)
+
+
+def _warn_unconfigured(engines, settings):
+    """Warn which of ``engines`` ((name, engine), ...) run on seeded weights; ``settings`` names
+    what would configure them."""
+    synth = [n for n, m in engines if m.weights_source.startswith("synthetic")]
+    if synth:
+        warnings.warn(f"{' and '.join(synth)} weights not configured ({settings}); using seeded synthetic weights",
+                      stacklevel=2)
+
+
+def _used_frames(frames, pairs):
+    """(pos, sel) for a pair list: sel = the frames some pair names, gathered once in index
+    order (``frames`` itself when that is all of them), pos[f] = the row of frame f in sel."""
+    used = sorted({i for p in pairs for i in p})
+    sel = frames[torch.as_tensor(used, device=frames.device)] if len(used) < frames.shape[0] else frames
+    return {f: j for j, f in enumerate(used)}, sel
 
 
 class BaseFeatureMatcher:
@@ -110,11 +128,8 @@ class LightGlue(BaseFeatureMatcher):
         self.extractor = SuperPointGPU(device=self.device, max_num_keypoints=self.max_keypoints,
                                        detection_threshold=self.detection_threshold)
         self.matcher = LightGlueGPU(device=self.device)
-        synth = [n for n, m in (("SuperPoint", self.extractor), ("LightGlue", self.matcher))
-                 if m.weights_source.startswith("synthetic")]
-        if synth:
-            warnings.warn(f"{' and '.join(synth)} weights not configured (MLGATE_SUPERPOINT_WEIGHTS / "
-                          "MLGATE_LIGHTGLUE_WEIGHTS); using seeded synthetic weights")
+        _warn_unconfigured((("SuperPoint", self.extractor), ("LightGlue", self.matcher)),
+                           "MLGATE_SUPERPOINT_WEIGHTS / MLGATE_LIGHTGLUE_WEIGHTS")
         self._model_loaded = True
         self._is_native = True
 
@@ -190,15 +205,10 @@ class LightGlue(BaseFeatureMatcher):
         pairs = list(pairs)
         if not pairs:
             return []
+        pos, sel = _used_frames(frames, pairs)
         if not getattr(self, "_is_native", False):  # ORB fallback: one detect over the used frames
-            used = sorted({i for p in pairs for i in p})
-            sel = frames[torch.as_tensor(used, device=frames.device)]
             kp, _, _, _, ds, cnt = self.orb.detect_device(sel)
-            feats = {f: (kp[j], ds[j], cnt[j]) for j, f in enumerate(used)}
-            return self._match_feats(feats, pairs)
-        used = sorted({i for p in pairs for i in p})
-        pos = {f: j for j, f in enumerate(used)}
-        sel = frames[torch.as_tensor(used, device=frames.device)] if len(used) < frames.shape[0] else frames
+            return self._match_feats({f: (kp[j], ds[j], cnt[j]) for f, j in pos.items()}, pairs)
         kp, _, ds, _, cnt = self.extractor.extract_device(sel)
         counts = cnt.cpu().numpy()
         m, sc, n, _ = self.matcher.match_device(kp, ds, counts, [pos[a] for a, _ in pairs],
@@ -211,7 +221,7 @@ class LightGlue(BaseFeatureMatcher):
         return out
 
 
-class SuperGlue(BaseFeatureMatcher):
+class SuperGlue(_NativeSwitch, BaseFeatureMatcher):
     """geometric_verification.py:353-421.  The reference's native branch never runs
     SuperGlue (:419-421 return the LightGlue fallback, and the magicleap package is
     absent), so by default this matcher IS the GPU LightGlue path, with the reference's
@@ -221,28 +231,25 @@ class SuperGlue(BaseFeatureMatcher):
     match_threshold 0.2) on the GPU (mlgate.superglue, csrc/superglue.hip); weights from
     MLGATE_SUPERGLUE_WEIGHTS, else seeded synthetic ones."""
 
+    _native_env = "MLGATE_SUPERGLUE_NATIVE"
+
     def __init__(self, device: str = 'cuda', max_keypoints: int = 2048, weights: str = 'indoor'):
         super().__init__(device)
         self.max_keypoints = max_keypoints
         self.weights = weights
-        self.native = None  # None: MLGATE_SUPERGLUE_NATIVE decides; True / False force it
         self._model_loaded = False
 
     def _load_model(self):
         if self._model_loaded:
             return
-        native = self.native if self.native is not None else os.environ.get("MLGATE_SUPERGLUE_NATIVE") == "1"
-        if native:
+        if self._native_selected():
             from .superglue import SuperGlueGPU
             from .superpoint import SuperPointGPU
             self.extractor = SuperPointGPU(device=self.device, max_num_keypoints=self.max_keypoints,
                                            detection_threshold=0.005, nms_radius=4)
             self.matcher = SuperGlueGPU(device=self.device)
-            synth = [n for n, m in (("SuperPoint", self.extractor), ("SuperGlue", self.matcher))
-                     if m.weights_source.startswith("synthetic")]
-            if synth:
-                warnings.warn(f"{' and '.join(synth)} weights not configured (MLGATE_SUPERPOINT_WEIGHTS / "
-                              "MLGATE_SUPERGLUE_WEIGHTS); using seeded synthetic weights")
+            _warn_unconfigured((("SuperPoint", self.extractor), ("SuperGlue", self.matcher)),
+                               "MLGATE_SUPERPOINT_WEIGHTS / MLGATE_SUPERGLUE_WEIGHTS")
             self._is_native = True
         else:
             warnings.warn("SuperGlue not installed. Using LightGlue fallback.")
@@ -271,9 +278,7 @@ class SuperGlue(BaseFeatureMatcher):
         pairs = list(pairs)
         if not pairs:
             return []
-        used = sorted({i for p in pairs for i in p})
-        pos = {f: j for j, f in enumerate(used)}
-        sel = frames[torch.as_tensor(used, device=frames.device)] if len(used) < frames.shape[0] else frames
+        pos, sel = _used_frames(frames, pairs)
         kp, sc, ds, _, cnt = self.extractor.extract_device(sel)
         m, s, n = self.matcher.match_device(kp, sc, ds, cnt.cpu().numpy(), [pos[a] for a, _ in pairs],
                                             [pos[b] for _, b in pairs], int(frames.shape[2]), int(frames.shape[1]))
@@ -281,7 +286,7 @@ class SuperGlue(BaseFeatureMatcher):
         return [(kp[pos[a]][m[p, :n[p], 0]], kp[pos[b]][m[p, :n[p], 1]], s[p, :n[p]]) for p, (a, b) in enumerate(pairs)]
 
 
-class LoFTR(BaseFeatureMatcher):
+class LoFTR(_NativeSwitch, BaseFeatureMatcher):
     """geometric_verification.py:424-526.  The reference runs kornia's LoFTR when kornia
     imports (pretrained `weights`) and otherwise warns and uses the LightGlue fallback
     (:447-467).  kornia and its checkpoints are absent here, so by default this class
@@ -294,21 +299,21 @@ class LoFTR(BaseFeatureMatcher):
     used).  The native kernels match frames of one shape; a pair of differently shaped
     frames is matched by the LightGlue fallback, with a warning."""
 
+    _native_env = "MLGATE_LOFTR_NATIVE"
+
     def __init__(self, device: str = 'cuda', weights: str = 'indoor'):
         super().__init__(device)
         self.weights = weights
-        self.native = None  # None: the environment decides (see the class docstring)
         self._model_loaded = False
 
-    def _want_native(self):
-        if self.native is not None:
-            return bool(self.native)
-        return os.environ.get("MLGATE_LOFTR_NATIVE") == "1" or bool(os.environ.get("MLGATE_LOFTR_WEIGHTS"))
+    def _native_selected(self):
+        """The shared rule, or (with ``.native`` unset) a configured checkpoint (see the class docstring)."""
+        return super()._native_selected() or (self.native is None and bool(os.environ.get("MLGATE_LOFTR_WEIGHTS")))
 
     def _load_model(self):
         if self._model_loaded:
             return
-        native = self._want_native()
+        native = self._native_selected()
         if native and self.weights != 'indoor' and not os.environ.get("MLGATE_LOFTR_WEIGHTS"):
             warnings.warn(f"LoFTR weights {self.weights!r}: no checkpoint in MLGATE_LOFTR_WEIGHTS; "
                           "using the LightGlue fallback")
@@ -316,8 +321,7 @@ class LoFTR(BaseFeatureMatcher):
         if native:
             from .loftr import LoFTRGPU
             self._matcher = LoFTRGPU(device=self.device)
-            if self._matcher.weights_source.startswith("synthetic"):
-                warnings.warn("LoFTR weights not configured (MLGATE_LOFTR_WEIGHTS); using seeded synthetic weights")
+            _warn_unconfigured((("LoFTR", self._matcher),), "MLGATE_LOFTR_WEIGHTS")
             self._is_native = True
         else:
             warnings.warn("LoFTR (kornia) not installed. Using LightGlue fallback. Install with: pip install kornia")

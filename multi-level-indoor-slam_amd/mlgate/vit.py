@@ -121,11 +121,7 @@ class VitB14:
         """frames: uint8 [B, H, W, C] device tensor (C = 1, 3 BGR or 4 BGRA; or [B, H, W]).
         Writes float32 descriptors [B, embed] (and local features [B, n_local, embed]) on the
         current stream: torch.ops.mlgate.vit_forward_into (DinoVit: dino_forward_into)."""
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(-1)
-        if frames.dtype != torch.uint8 or frames.device.type != "cuda":
-            raise TypeError("frames must be a uint8 tensor on the HIP device")
-        self._op(frames.contiguous(), self.image_size, self.flags, self.max_batch, desc_out, local_out)
+        self._op(_native.device_frames(frames), self.image_size, self.flags, self.max_batch, desc_out, local_out)
 
     def forward(self, frames, with_local=False):
         B = frames.shape[0]

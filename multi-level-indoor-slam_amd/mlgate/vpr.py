@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
-from . import _native
+from . import _native, weights
 
 
 @dataclass
@@ -52,6 +52,38 @@ class PlaceDescriptor:
     descriptor: np.ndarray
     image_path: Optional[str] = None
     floor_label: Optional[int] = None
+
+
+def _entries(descs, timestamps, floor_labels=None, image_paths=None):
+    """One PlaceDescriptor per row of ``descs``."""
+    return [PlaceDescriptor(timestamp=timestamps[i], descriptor=d,
+                            image_path=None if image_paths is None else image_paths[i],
+                            floor_label=None if floor_labels is None else floor_labels[i])
+            for i, d in enumerate(descs)]
+
+
+def _warn_synthetic(source, text):
+    """Warn with ``text``, at the caller's line, when a weights source says the weights are
+    seeded, not a checkpoint's."""
+    if source.startswith("synthetic"):
+        warnings.warn(text, stacklevel=2)
+
+
+def _check_vitb14_head(backbone):
+    if backbone != 'dinov2_vitb14':
+        raise ValueError(f"{backbone}: the native branch's head is 768 wide, only the dinov2_vitb14 backbone has "
+                         "MI355X kernels for it")
+
+
+class _NativeSwitch:
+    """The rule of every opt-in native branch: ``.native = None`` lets the environment variable
+    ``_native_env`` decide ("1" selects the branch); True / False force it."""
+
+    _native_env = None
+    native = None
+
+    def _native_selected(self):
+        return self.native if self.native is not None else os.environ.get(self._native_env) == "1"
 
 
 def _torch():
@@ -135,12 +167,7 @@ class BasePlaceRecognition:
 
     def add_images(self, images, timestamps, floor_labels=None, image_paths=None) -> List[PlaceDescriptor]:
         """Batched add_image (mlgate extension): one device batch instead of N calls."""
-        descs = self.extract_descriptors(images)
-        out = []
-        for i, d in enumerate(descs):
-            out.append(PlaceDescriptor(timestamp=timestamps[i], descriptor=d,
-                                       image_path=None if image_paths is None else image_paths[i],
-                                       floor_label=None if floor_labels is None else floor_labels[i]))
+        out = _entries(self.extract_descriptors(images), timestamps, floor_labels, image_paths)
         self.descriptors.extend(out)
         return out
 
@@ -219,32 +246,56 @@ class BasePlaceRecognition:
                            match_timestamp=self.descriptors[int(j)].timestamp) for j, s in zip(idx, sim)]
 
 
-class _ResNetFallback(BasePlaceRecognition):
+class _ResNetFallback(_NativeSwitch, BasePlaceRecognition):
     """MixVPR / SALAD: what the reference executes is a torchvision ResNet-50 GAP
     (place_recognition.py:248-306) -- the MixVPR / SALAD packages are never importable
     under the names it tries, so every call lands in ``_load_fallback_model``.  Here
-    that network runs on the GPU (mlgate.resnet, HIP kernels + bf16 MFMA GEMMs)."""
+    that network runs on the GPU (mlgate.resnet, HIP kernels + bf16 MFMA GEMMs).
+
+    A subclass names its opt-in native branch: ``_native_env``, the attribute that holds the
+    native engine (``_native_attr``), ``_build_native()`` (its dimension / backbone checks and
+    its engine constructor), the warning when that engine runs on seeded weights and, for
+    SALAD, the reference's warning before the fallback loads."""
+
+    _native_attr = None
+    _synthetic_warning = None
+    _fallback_warning = None
 
     def __init__(self, descriptor_dim, device, pretrained_path=None):
         super().__init__(descriptor_dim, device)
         self.pretrained_path = pretrained_path
         self._model_loaded = False
+        setattr(self, self._native_attr, None)
+
+    def _build_native(self):
+        raise NotImplementedError
 
     def _load_model(self):
         if self._model_loaded:
             return
-        from .resnet import ResNet50GPU
-        self._net = ResNet50GPU(device=self.device)
-        if self._net.weights_source.startswith("synthetic"):
-            warnings.warn("ImageNet ResNet-50 weights are not available offline; using seeded synthetic resnet50 "
-                          "weights (set MLGATE_RESNET50_WEIGHTS to a local torchvision checkpoint).")
+        native = self._native_selected()
+        if native:
+            engine = self._build_native()
+            setattr(self, self._native_attr, engine)
+            _warn_synthetic(engine.weights_source, self._synthetic_warning)
+        else:
+            if self._fallback_warning:
+                warnings.warn(self._fallback_warning)
+            from .resnet import ResNet50GPU
+            self._net = ResNet50GPU(device=self.device)
+            _warn_synthetic(self._net.weights_source,
+                            "ImageNet ResNet-50 weights are not available offline; using seeded synthetic resnet50 "
+                            "weights (set MLGATE_RESNET50_WEIGHTS to a local torchvision checkpoint).")
         self._model_loaded = True
-        self._is_fallback = True
+        self._is_fallback = not native
 
     def extract_descriptors(self, images) -> np.ndarray:
         self._load_model()
-        frames = _device_frames(images, self._net.device)
-        return self._net.forward_device(frames, self.descriptor_dim).cpu().numpy()
+        engine = getattr(self, self._native_attr)
+        if engine is None:
+            frames = _device_frames(images, self._net.device)
+            return self._net.forward_device(frames, self.descriptor_dim).cpu().numpy()
+        return engine.forward(_device_frames(images, engine.device)).cpu().numpy()
 
     def extract_descriptor(self, image: np.ndarray) -> np.ndarray:
         return self.extract_descriptors([image])[0]
@@ -258,36 +309,22 @@ class MixVPR(_ResNetFallback):
     + feature-mixer head at 320 x 320 on the GPU (mlgate.mixvpr, csrc/mixvpr.hip); weights
     from ``pretrained_path`` / MLGATE_MIXVPR_WEIGHTS, else seeded synthetic ones."""
 
+    _native_env, _native_attr = "MLGATE_MIXVPR_NATIVE", "_mix"
+    _synthetic_warning = ("MixVPR weights not configured (pretrained_path / MLGATE_MIXVPR_WEIGHTS); using seeded "
+                          "synthetic weights")
+
     def __init__(self, backbone: str = 'resnet50', descriptor_dim: int = 4096, device: str = 'cuda',
                  pretrained_path: Optional[str] = None):
         super().__init__(descriptor_dim, device, pretrained_path)
         self.backbone_name = backbone
-        self.native = None  # None: MLGATE_MIXVPR_NATIVE decides; True / False force it
-        self._mix = None
 
-    def _load_model(self):
-        if self._model_loaded:
-            return
-        native = self.native if self.native is not None else os.environ.get("MLGATE_MIXVPR_NATIVE") == "1"
-        if not native:
-            return super()._load_model()
+    def _build_native(self):
         from .mixvpr import DESC_DIM, MixVprGPU
         if self.backbone_name != 'resnet50':
             raise ValueError(f"native MixVPR: only the resnet50 backbone has MI355X kernels, not {self.backbone_name}")
         if self.descriptor_dim != DESC_DIM:
             raise ValueError(f"native MixVPR produces {DESC_DIM}-dim descriptors, not {self.descriptor_dim}")
-        self._mix = MixVprGPU(device=self.device, pretrained_path=self.pretrained_path)
-        if self._mix.weights_source.startswith("synthetic"):
-            warnings.warn("MixVPR weights not configured (pretrained_path / MLGATE_MIXVPR_WEIGHTS); using seeded "
-                          "synthetic weights")
-        self._model_loaded = True
-        self._is_fallback = False
-
-    def extract_descriptors(self, images) -> np.ndarray:
-        self._load_model()
-        if self._mix is None:
-            return super().extract_descriptors(images)
-        return self._mix.forward(_device_frames(images, self._mix.device)).cpu().numpy()
+        return MixVprGPU(device=self.device, pretrained_path=self.pretrained_path)
 
 
 class SALAD(_ResNetFallback):
@@ -299,36 +336,22 @@ class SALAD(_ResNetFallback):
     csrc/salad.hip); weights from ``pretrained_path`` / MLGATE_SALAD_WEIGHTS, else seeded
     synthetic ones."""
 
+    _native_env, _native_attr = "MLGATE_SALAD_NATIVE", "_salad"
+    _synthetic_warning = ("SALAD weights not configured (pretrained_path / MLGATE_SALAD_WEIGHTS); using seeded "
+                          "synthetic weights")
+    _fallback_warning = "SALAD not installed. Using MixVPR fallback. For SALAD: pip install salad-vpr"
+
     def __init__(self, descriptor_dim: int = 8448, device: str = 'cuda', pretrained_path: Optional[str] = None):
         super().__init__(descriptor_dim, device, pretrained_path)
-        self.native = None  # None: MLGATE_SALAD_NATIVE decides; True / False force it
-        self._salad = None
 
-    def _load_model(self):
-        if self._model_loaded:
-            return
-        native = self.native if self.native is not None else os.environ.get("MLGATE_SALAD_NATIVE") == "1"
-        if not native:
-            warnings.warn("SALAD not installed. Using MixVPR fallback. For SALAD: pip install salad-vpr")
-            return super()._load_model()
+    def _build_native(self):
         from .salad import DESC_DIM, SaladGPU
         if self.descriptor_dim != DESC_DIM:
             raise ValueError(f"native SALAD produces {DESC_DIM}-dim descriptors, not {self.descriptor_dim}")
-        self._salad = SaladGPU(device=self.device, pretrained_path=self.pretrained_path)
-        if self._salad.weights_source.startswith("synthetic"):
-            warnings.warn("SALAD weights not configured (pretrained_path / MLGATE_SALAD_WEIGHTS); using seeded "
-                          "synthetic weights")
-        self._model_loaded = True
-        self._is_fallback = False
-
-    def extract_descriptors(self, images) -> np.ndarray:
-        self._load_model()
-        if self._salad is None:
-            return super().extract_descriptors(images)
-        return self._salad.forward(_device_frames(images, self._salad.device)).cpu().numpy()
+        return SaladGPU(device=self.device, pretrained_path=self.pretrained_path)
 
 
-class _DinoEngineMixin:
+class _DinoEngineMixin(_NativeSwitch):
     """Lazy DINOv2 engine construction shared by CricaVPR and AnyLoc: ``backbone`` is one of
     dinov2_vits14 / dinov2_vitb14 / dinov2_vitl14 (feat_dim 384 / 768 / 1024,
     place_recognition.py:594-602)."""
@@ -337,16 +360,19 @@ class _DinoEngineMixin:
     _pool = "gem"
     _swap_rb = True
 
+    def _dino_state_dict(self, setting):
+        """The backbone's state dict; seeded weights come with a warning that names ``setting``."""
+        sd, source = weights.resolve_state_dict(getattr(self, 'pretrained_path', None), backbone=self.backbone_name)
+        _warn_synthetic(source, "DINOv2 hub weights are not available offline; using seeded synthetic "
+                                f"{self.backbone_name} weights (set {setting} to a local hub checkpoint for real "
+                                "descriptors).")
+        return sd
+
     def _engine(self):
         if getattr(self, '_vit', None) is None:
             from .vit import engine_for
-            from .weights import backbone_config, resolve_state_dict
-            embed = backbone_config(self.backbone_name)[0]  # ValueError lists the supported names
-            sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None), backbone=self.backbone_name)
-            if source.startswith('synthetic'):
-                warnings.warn("DINOv2 hub weights are not available offline; using seeded synthetic "
-                              f"{self.backbone_name} weights (set pretrained_path or MLGATE_DINOV2_WEIGHTS to a local "
-                              "hub checkpoint for real descriptors).")
+            embed = weights.backbone_config(self.backbone_name)[0]  # ValueError lists the supported names
+            sd = self._dino_state_dict("pretrained_path or MLGATE_DINOV2_WEIGHTS")
             # the split-bf16 forward (VitB14's default): descriptors within ~1e-11 of fp32,
             # so retrieval ranks as the fp32 reference does (DESIGN.md section 4)
             self._vit = engine_for(sd, self.backbone_name, device=self.device, image_size=self._image_size,
@@ -367,6 +393,7 @@ class _DinoEngineMixin:
 
 
 class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
+    _native_env = "MLGATE_ANYLOC_NATIVE"
     _image_size = 518
     _pool = "mean"
     _swap_rb = False
@@ -378,34 +405,23 @@ class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
         self.num_clusters = num_clusters
         self._model_loaded = False
         self._vit = None
-        self.native = None  # None: MLGATE_ANYLOC_NATIVE decides; True / False force it
         self._anyloc = None
         self._vocabulary = None
 
-    def _native_selected(self):
-        return self.native if self.native is not None else os.environ.get("MLGATE_ANYLOC_NATIVE") == "1"
-
     def _check_native_dims(self):
-        from .weights import VLAD_CLUSTERS, VLAD_DIM
-        if self.num_clusters not in VLAD_CLUSTERS:
+        if self.num_clusters not in weights.VLAD_CLUSTERS:
             raise ValueError(f"native AnyLoc: num_clusters = {self.num_clusters} is not a multiple of 16 in 16..128 "
                              f"(descriptor_dim = {self.descriptor_dim})")
-        if self.descriptor_dim != self.num_clusters * VLAD_DIM:
-            raise ValueError(f"native AnyLoc produces num_clusters x {VLAD_DIM} = {self.num_clusters * VLAD_DIM}-dim "
-                             f"descriptors (num_clusters = {self.num_clusters}), not {self.descriptor_dim}")
+        if self.descriptor_dim != self.num_clusters * weights.VLAD_DIM:
+            raise ValueError(f"native AnyLoc produces num_clusters x {weights.VLAD_DIM} = "
+                             f"{self.num_clusters * weights.VLAD_DIM}-dim descriptors (num_clusters = "
+                             f"{self.num_clusters}), not {self.descriptor_dim}")
 
     def _build_engine(self, vocabulary):
         self._check_native_dims()
-        if self.backbone_name != 'dinov2_vitb14':
-            raise ValueError(f"{self.backbone_name}: the native branch's head is 768 wide, only the dinov2_vitb14 "
-                             "backbone has MI355X kernels for it")
+        _check_vitb14_head(self.backbone_name)
         from .anyloc import AnyLocGPU
-        from .weights import resolve_state_dict
-        sd, source = resolve_state_dict(getattr(self, 'pretrained_path', None))
-        if source.startswith('synthetic'):
-            warnings.warn("DINOv2 hub weights are not available offline; using seeded synthetic "
-                          "dinov2_vitb14 weights (set MLGATE_DINOV2_WEIGHTS to a local hub checkpoint for "
-                          "real descriptors).")
+        sd = self._dino_state_dict("MLGATE_DINOV2_WEIGHTS")
         self.feat_dim = 768
         self._model_loaded = True
         return AnyLocGPU(sd, vocabulary, device=self.device, image_size=self._image_size)
@@ -418,21 +434,18 @@ class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
             self._check_native_dims()
             vocab = self._vocabulary
             if vocab is None:
-                from .weights import resolve_vocabulary
-                vocab, source = resolve_vocabulary(None, self.num_clusters)
-                if source.startswith('synthetic'):
-                    warnings.warn("AnyLoc vocabulary not configured (set_vocabulary / fit_vocabulary / "
-                                  "MLGATE_ANYLOC_VOCAB); using a seeded synthetic vocabulary")
+                vocab, source = weights.resolve_vocabulary(None, self.num_clusters)
+                _warn_synthetic(source, "AnyLoc vocabulary not configured (set_vocabulary / fit_vocabulary / "
+                                        "MLGATE_ANYLOC_VOCAB); using a seeded synthetic vocabulary")
                 self._vocabulary = vocab
             self._anyloc = self._build_engine(vocab)
         return self._anyloc
 
     def set_vocabulary(self, centers):
         """VLAD cluster centres [num_clusters, 768] for the native branch (mlgate extension)."""
-        from .weights import check_vocabulary
         if hasattr(centers, 'detach'):
             centers = centers.detach().float().cpu().numpy()
-        self._vocabulary = check_vocabulary(centers, self.num_clusters)
+        self._vocabulary = weights.check_vocabulary(centers, self.num_clusters)
         if self._anyloc is not None:
             self._anyloc.set_vocabulary(self._vocabulary)
 
@@ -448,20 +461,16 @@ class AnyLoc(_DinoEngineMixin, BasePlaceRecognition):
         self.set_vocabulary(centers)
         return centers
 
-    def extract_descriptors(self, images) -> np.ndarray:
+    def _forward(self, images, with_local=False):
         eng = self._native_engine()
         if eng is None:
-            return super().extract_descriptors(images)
-        return eng.forward(_device_frames(images, eng.device)).cpu().numpy()
-
-    def extract_descriptor(self, image: np.ndarray) -> np.ndarray:
-        eng = self._native_engine()
-        if eng is None:
-            return super().extract_descriptor(image)
-        return eng.forward(_device_frames([image], eng.device))[0].cpu().numpy().flatten()
+            return super()._forward(images, with_local)
+        return eng.forward(_device_frames(images, eng.device))
 
 
 class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
+    _native_env = "MLGATE_CRICAVPR_NATIVE"
+
     def __init__(self, backbone: str = 'dinov2_vitb14', descriptor_dim: int = 10752, device: str = 'cuda',
                  pretrained_path: Optional[str] = None, use_reranking: bool = True):
         super().__init__(descriptor_dim, device)
@@ -471,12 +480,8 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
         self._model_loaded = False
         self._vit = None
         self._feature_cache = {}  # idx -> device float32 [1, 528, feat_dim]
-        self.native = None  # None: MLGATE_CRICAVPR_NATIVE decides; True / False force it
         self.cross_image_group = 1  # images of a call that attend to each other (native branch)
         self._crica = None
-
-    def _native_selected(self):
-        return self.native if self.native is not None else os.environ.get("MLGATE_CRICAVPR_NATIVE") == "1"
 
     def _native_engine(self):
         """The CricaGPU engine when the native branch is selected, else None."""
@@ -486,20 +491,16 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
             if self.descriptor_dim != 10752:
                 raise ValueError(f"native CricaVPR produces 14 x 768 = 10752-dim descriptors, not "
                                  f"{self.descriptor_dim}")
-            if self.backbone_name != 'dinov2_vitb14':
-                raise ValueError(f"{self.backbone_name}: the native branch's head is 768 wide, only the "
-                                 "dinov2_vitb14 backbone has MI355X kernels for it")
+            _check_vitb14_head(self.backbone_name)
             from .crica import CricaGPU, check_group
-            from .weights import resolve_crica_state_dict
             group = check_group(self.cross_image_group)
             if self._crica is not None:  # the group changed: the packed weights stay
                 self._crica.group = group
                 return self._crica
-            sd, source = resolve_crica_state_dict(self.pretrained_path)
-            if source.startswith('synthetic'):
-                warnings.warn("CricaVPR weights are not available offline; using seeded synthetic weights (set "
-                              "pretrained_path or MLGATE_CRICAVPR_WEIGHTS to a local CricaVPRNet checkpoint for "
-                              "real descriptors).")
+            sd, source = weights.resolve_crica_state_dict(self.pretrained_path)
+            _warn_synthetic(source, "CricaVPR weights are not available offline; using seeded synthetic weights (set "
+                                    "pretrained_path or MLGATE_CRICAVPR_WEIGHTS to a local CricaVPRNet checkpoint "
+                                    "for real descriptors).")
             self._crica = CricaGPU(sd, device=self.device, image_size=self._image_size,
                                    max_batch=max(64, group), group=group)
             self.feat_dim = 768
@@ -570,15 +571,11 @@ class CricaVPR(_DinoEngineMixin, BasePlaceRecognition):
         return out
 
     def _append(self, descs, local, timestamps, floor_labels, image_paths):
-        out = []
-        for i in range(len(descs)):
-            entry = PlaceDescriptor(timestamp=timestamps[i], descriptor=descs[i],
-                                    image_path=None if image_paths is None else image_paths[i],
-                                    floor_label=None if floor_labels is None else floor_labels[i])
+        out = _entries(descs, timestamps, floor_labels, image_paths)
+        for i, entry in enumerate(out):
             self.descriptors.append(entry)
             if self.use_reranking:
                 self._feature_cache[len(self.descriptors) - 1] = local[i:i + 1]
-            out.append(entry)
         return out
 
     def add_image(self, image: np.ndarray, timestamp: float, floor_label: Optional[int] = None,

@@ -9,9 +9,17 @@ The reference fetches ``torch.hub.load('facebookresearch/dinov2', 'dinov2_vitb14
     the hub architecture and key names, so the full network runs with real shapes.
     Descriptors from synthetic weights are meaningful for throughput and parity
     testing only, not for place recognition.
+
+Every other network of the package (SuperPoint, LightGlue, ResNet-50, LoFTR, SuperGlue,
+SALAD, MixVPR, CricaVPR) follows the same rule -- a local file, else the model's
+``MLGATE_*_WEIGHTS`` variable, else seeded weights -- through one table: ``CHECKPOINTS``
+holds one record per model, ``load_checkpoint`` / ``resolve_checkpoint`` do the work, and
+the public ``load_*_state_dict`` / ``resolve_*_state_dict`` names are bindings of the two.
 """
+import collections
 import functools
 import os
+import re
 
 import numpy as np
 
@@ -117,24 +125,79 @@ def synthetic_state_dict(seed=0, backbone=DEFAULT_BACKBONE):
     return sd
 
 
-def load_hub_state_dict(path, backbone=DEFAULT_BACKBONE):
-    """Hub-format checkpoint of ``backbone`` from a local file (no code executed from it); a
-    checkpoint of another width or depth is refused (check_state_dict)."""
+# ----------------------------------------------------------------- checkpoints
+# Everything in which one model's checkpoint handling differs from another's: the environment
+# variable that names a file, keys(**kw) -> the key names in order, synthetic(seed, **kw) -> the
+# seeded weights, the word the KeyError uses, the keys a file may nest its state dict under (the
+# first that holds a dict is unwrapped), an optional rewrite of each key name, an optional
+# check(sd, path, **kw) of the unwrapped dict and an optional finish(out, path) of the result.
+# A new model adds its record to CHECKPOINTS and binds its two public names below it.
+Checkpoint = collections.namedtuple("Checkpoint", "env keys synthetic word nests rewrite check finish",
+                                    defaults=((), None, None, None))
+CHECKPOINTS = {}
+
+
+def load_checkpoint(model, path, **kw):
+    """{key: float32 array} over ``model``'s keys, in their order, from a local file
+    (torch.load, weights only: no code is executed from it); KeyError names the first three
+    keys the file lacks.  ``kw`` goes to the record's functions (DINOv2: backbone)."""
     import torch
+    c = CHECKPOINTS[model]
     sd = torch.load(path, map_location="cpu", weights_only=True)
-    if "model" in sd and isinstance(sd["model"], dict):
-        sd = sd["model"]
-    check_state_dict(sd, backbone, f"checkpoint {path}")
-    return {k: sd[k].float().cpu().numpy() for k in hub_keys(backbone)}
+    for nest in c.nests:
+        if nest in sd and isinstance(sd[nest], dict):
+            sd = sd[nest]
+            break
+    if c.rewrite:
+        sd = {c.rewrite(k): v for k, v in sd.items()}
+    if c.check:
+        c.check(sd, path, **kw)
+    keys = c.keys(**kw)
+    missing = [k for k in keys if k not in sd]
+    if missing:
+        raise KeyError(f"checkpoint {path} lacks {c.word} keys, e.g. {missing[:3]}")
+    out = {k: sd[k].float().cpu().numpy() for k in keys}
+    return c.finish(out, path) if c.finish else out
+
+
+def resolve_checkpoint(model, path=None, seed=0, **kw):
+    """(state_dict, source): the file at ``path``, else the one the model's environment
+    variable names, else seeded synthetic weights with the source 'synthetic(seed=N)'."""
+    c = CHECKPOINTS[model]
+    path = path or os.environ.get(c.env)
+    if path:
+        return load_checkpoint(model, path, **kw), path
+    return c.synthetic(seed, **kw), f"synthetic(seed={seed})"
+
+
+def given_or_resolved(model, state_dict, path=None, seed=0, given="given"):
+    """(state_dict, weights_source) of an engine constructor: the caller's dict under the label
+    ``given``, else resolve_checkpoint(model, path, seed)."""
+    if state_dict is None:
+        return resolve_checkpoint(model, path, seed)
+    return state_dict, given
+
+
+def sub_state_dict(sd, prefix):
+    """The entries of ``sd`` under ``prefix`` (a trunk inside a larger model), the prefix removed."""
+    return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+
+
+# Hub-format checkpoint, bare or under 'model'; one of another width or depth is refused, and a
+# missing key is reported, by check_state_dict, which names the backbone asked for.
+CHECKPOINTS["dinov2"] = Checkpoint(
+    "MLGATE_DINOV2_WEIGHTS", hub_keys, synthetic_state_dict, "DINOv2", ("model",),
+    check=lambda sd, path, backbone=DEFAULT_BACKBONE: check_state_dict(sd, backbone, f"checkpoint {path}"))
+
+
+def load_hub_state_dict(path, backbone=DEFAULT_BACKBONE):
+    return load_checkpoint("dinov2", path, backbone=backbone)
 
 
 def resolve_state_dict(pretrained_path=None, seed=0, backbone=DEFAULT_BACKBONE):
     """(state_dict, source) -- local checkpoint if given/configured, else synthetic."""
     backbone_config(backbone)
-    path = pretrained_path or os.environ.get("MLGATE_DINOV2_WEIGHTS")
-    if path:
-        return load_hub_state_dict(path, backbone), path
-    return synthetic_state_dict(seed, backbone), f"synthetic(seed={seed})"
+    return resolve_checkpoint("dinov2", pretrained_path, seed, backbone=backbone)
 
 
 # ----------------------------------------------------------------- SuperPoint
@@ -200,22 +263,15 @@ def _whitening_head(sd, seed, n_scenes=4, reg=1e-2):
     return Wh.astype(np.float32).reshape(256, 256, 1, 1), (-(Wh @ mu)).astype(np.float32)
 
 
-def load_superpoint_state_dict(path):
-    """LightGlue superpoint_v1.pth-style checkpoint from a local file (weights only)."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    keys = [f"{n}.{p}" for n, *_ in SUPERPOINT_LAYERS for p in ("weight", "bias")]
-    missing = [k for k in keys if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks SuperPoint keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in keys}
+def superpoint_keys():
+    return [f"{n}.{p}" for n, *_ in SUPERPOINT_LAYERS for p in ("weight", "bias")]
 
 
-def resolve_superpoint_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_SUPERPOINT_WEIGHTS")
-    if path:
-        return load_superpoint_state_dict(path), path
-    return superpoint_state_dict(seed), f"synthetic(seed={seed})"
+# LightGlue's superpoint_v1.pth
+CHECKPOINTS["superpoint"] = Checkpoint("MLGATE_SUPERPOINT_WEIGHTS", superpoint_keys, superpoint_state_dict,
+                                       "SuperPoint")
+load_superpoint_state_dict = functools.partial(load_checkpoint, "superpoint")
+resolve_superpoint_state_dict = functools.partial(resolve_checkpoint, "superpoint")
 
 
 # ----------------------------------------------------------------- LightGlue
@@ -277,25 +333,13 @@ def lightglue_state_dict(seed=0, res_gain=0.05, final_scale=16.0, match_gain=6.0
     return sd
 
 
-def load_lightglue_state_dict(path):
-    """LightGlue superpoint_lightglue.pth-style checkpoint from a local file (weights only)."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    import re
-    # older releases stored "self_attn.{i}.*" / "cross_attn.{i}.*" (LightGlue renames them on load)
-    sd = {re.sub(r"^(self_attn|cross_attn)\.(\d+)\.", r"transformers.\2.\1.", k.replace("matcher.", "")): v
-          for k, v in sd.items()}
-    missing = [k for k in lightglue_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks LightGlue keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in lightglue_keys()}
-
-
-def resolve_lightglue_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_LIGHTGLUE_WEIGHTS")
-    if path:
-        return load_lightglue_state_dict(path), path
-    return lightglue_state_dict(seed), f"synthetic(seed={seed})"
+# LightGlue's superpoint_lightglue.pth; older releases stored "self_attn.{i}.*" / "cross_attn.{i}.*"
+# under "matcher." (LightGlue renames them on load)
+CHECKPOINTS["lightglue"] = Checkpoint(
+    "MLGATE_LIGHTGLUE_WEIGHTS", lightglue_keys, lightglue_state_dict, "LightGlue",
+    rewrite=lambda k: re.sub(r"^(self_attn|cross_attn)\.(\d+)\.", r"transformers.\2.\1.", k.replace("matcher.", "")))
+load_lightglue_state_dict = functools.partial(load_checkpoint, "lightglue")
+resolve_lightglue_state_dict = functools.partial(resolve_checkpoint, "lightglue")
 
 
 # ----------------------------------------------------------------- ResNet-50 (MixVPR / SALAD fallback)
@@ -351,21 +395,10 @@ def resnet50_state_dict(seed=0):
     return sd
 
 
-def load_resnet50_state_dict(path):
-    """torchvision resnet50 checkpoint (e.g. resnet50-0676ba61.pth) from a local file."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    missing = [k for k in resnet50_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks resnet50 keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in resnet50_keys()}
-
-
-def resolve_resnet50_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_RESNET50_WEIGHTS")
-    if path:
-        return load_resnet50_state_dict(path), path
-    return resnet50_state_dict(seed), f"synthetic(seed={seed})"
+# torchvision's resnet50 checkpoint (e.g. resnet50-0676ba61.pth)
+CHECKPOINTS["resnet50"] = Checkpoint("MLGATE_RESNET50_WEIGHTS", resnet50_keys, resnet50_state_dict, "resnet50")
+load_resnet50_state_dict = functools.partial(load_checkpoint, "resnet50")
+resolve_resnet50_state_dict = functools.partial(resolve_checkpoint, "resnet50")
 
 
 # ----------------------------------------------------------------------------- LoFTR
@@ -511,22 +544,10 @@ def _loftr_whitening(sd, seed, n_scenes=3, reg=1e-2, h=240, w=320):
     return Wh.astype(np.float32).reshape(len(mu), len(mu), 1, 1)
 
 
-def load_loftr_state_dict(path):
-    """kornia LoFTR checkpoint (loftr_indoor.ckpt: {'state_dict': ...} or a bare state dict)."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    sd = sd.get("state_dict", sd)
-    missing = [k for k in loftr_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks LoFTR keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in loftr_keys()}
-
-
-def resolve_loftr_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_LOFTR_WEIGHTS")
-    if path:
-        return load_loftr_state_dict(path), path
-    return loftr_state_dict(seed), f"synthetic(seed={seed})"
+# kornia's LoFTR checkpoint (loftr_indoor.ckpt: {'state_dict': ...} or a bare state dict)
+CHECKPOINTS["loftr"] = Checkpoint("MLGATE_LOFTR_WEIGHTS", loftr_keys, loftr_state_dict, "LoFTR", ("state_dict",))
+load_loftr_state_dict = functools.partial(load_checkpoint, "loftr")
+resolve_loftr_state_dict = functools.partial(resolve_checkpoint, "loftr")
 
 
 # ----------------------------------------------------------------- SuperGlue (magicleap)
@@ -597,21 +618,10 @@ def superglue_state_dict(seed=0, res_gain=0.05, kenc_gain=0.05, final_scale=12.0
     return sd
 
 
-def load_superglue_state_dict(path):
-    """magicleap superglue_*.pth from a local file (weights only)."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    missing = [k for k in superglue_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks SuperGlue keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in superglue_keys()}
-
-
-def resolve_superglue_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_SUPERGLUE_WEIGHTS")
-    if path:
-        return load_superglue_state_dict(path), path
-    return superglue_state_dict(seed), f"synthetic(seed={seed})"
+# magicleap's superglue_{indoor,outdoor}.pth
+CHECKPOINTS["superglue"] = Checkpoint("MLGATE_SUPERGLUE_WEIGHTS", superglue_keys, superglue_state_dict, "SuperGlue")
+load_superglue_state_dict = functools.partial(load_checkpoint, "superglue")
+resolve_superglue_state_dict = functools.partial(resolve_checkpoint, "superglue")
 
 
 # ----------------------------------------------------------------- SALAD
@@ -657,24 +667,10 @@ def salad_state_dict(seed=0, score_gain=2.0):
     return sd
 
 
-def load_salad_state_dict(path):
-    """serizba/salad checkpoint (VPRModel state dict, optionally under 'state_dict') from a
-    local file, weights only."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
-        sd = sd["state_dict"]
-    missing = [k for k in salad_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks SALAD keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in salad_keys()}
-
-
-def resolve_salad_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_SALAD_WEIGHTS")
-    if path:
-        return load_salad_state_dict(path), path
-    return salad_state_dict(seed), f"synthetic(seed={seed})"
+# serizba/salad checkpoint: the VPRModel state dict, bare or under 'state_dict'
+CHECKPOINTS["salad"] = Checkpoint("MLGATE_SALAD_WEIGHTS", salad_keys, salad_state_dict, "SALAD", ("state_dict",))
+load_salad_state_dict = functools.partial(load_checkpoint, "salad")
+resolve_salad_state_dict = functools.partial(resolve_checkpoint, "salad")
 
 
 # ----------------------------------------------------------------- MixVPR
@@ -727,24 +723,11 @@ def mixvpr_state_dict(seed=0):
     return sd
 
 
-def load_mixvpr_state_dict(path):
-    """amaralibey/MixVPR checkpoint (a Lightning file: the state dict bare or under
-    'state_dict') from a local file, weights only; layer4 / fc keys are ignored."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
-        sd = sd["state_dict"]
-    missing = [k for k in mixvpr_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks MixVPR keys, e.g. {missing[:3]}")
-    return {k: sd[k].float().cpu().numpy() for k in mixvpr_keys()}
-
-
-def resolve_mixvpr_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_MIXVPR_WEIGHTS")
-    if path:
-        return load_mixvpr_state_dict(path), path
-    return mixvpr_state_dict(seed), f"synthetic(seed={seed})"
+# amaralibey/MixVPR checkpoint (a Lightning file: the state dict bare or under 'state_dict');
+# layer4 / fc keys are ignored
+CHECKPOINTS["mixvpr"] = Checkpoint("MLGATE_MIXVPR_WEIGHTS", mixvpr_keys, mixvpr_state_dict, "MixVPR", ("state_dict",))
+load_mixvpr_state_dict = functools.partial(load_checkpoint, "mixvpr")
+resolve_mixvpr_state_dict = functools.partial(resolve_checkpoint, "mixvpr")
 
 
 # ------------------------------------------------------------- AnyLoc vocabulary
@@ -856,37 +839,30 @@ def crica_state_dict(seed=0):
     return sd
 
 
-def load_crica_state_dict(path):
-    """CricaVPRNet checkpoint from a local file, weights only: a plain state dict or one under
-    'model_state_dict' / 'state_dict', with or without DataParallel's 'module.' prefix.
-    A backbone with tensors the hub ViT-B/14 does not have (upstream's per-block adapters,
+def _crica_refuse_foreign_backbone(sd, path):
+    """A backbone with tensors the hub ViT-B/14 does not have (upstream's per-block adapters,
     whose layout cannot be checked here) is refused by name, never silently dropped."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    for nest in ("model_state_dict", "state_dict"):
-        if nest in sd and isinstance(sd[nest], dict):
-            sd = sd[nest]
-            break
-    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
     known = {"backbone." + k for k in hub_keys()} | {"backbone." + k for k in CRICA_UNUSED_BACKBONE_KEYS}
     foreign = [k for k in sd if k.startswith("backbone.") and k not in known]
     if foreign:
         raise ValueError(f"checkpoint {path}: {len(foreign)} backbone tensors are not part of dinov2_vitb14, the "
                          f"first is '{foreign[0]}'; a backbone with adapters is not supported")
-    missing = [k for k in crica_keys() if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint {path} lacks CricaVPR keys, e.g. {missing[:3]}")
-    out = {"backbone." + k: sd["backbone." + k].float().cpu().numpy() for k in hub_keys()}
+
+
+def _crica_reshape_head(out, path):
+    """Every head tensor in the shape of crica_head_shapes (a checkpoint may store p as a scalar)."""
     for k, shp in crica_head_shapes().items():
-        a = sd[k].float().cpu().numpy()
-        if a.size != int(np.prod(shp)):
-            raise ValueError(f"checkpoint {path}: '{k}' has shape {tuple(a.shape)}, expected {shp}")
-        out[k] = a.reshape(shp)
+        if out[k].size != int(np.prod(shp)):
+            raise ValueError(f"checkpoint {path}: '{k}' has shape {tuple(out[k].shape)}, expected {shp}")
+        out[k] = out[k].reshape(shp)
     return out
 
 
-def resolve_crica_state_dict(path=None, seed=0):
-    path = path or os.environ.get("MLGATE_CRICAVPR_WEIGHTS")
-    if path:
-        return load_crica_state_dict(path), path
-    return crica_state_dict(seed), f"synthetic(seed={seed})"
+# CricaVPRNet checkpoint: a plain state dict or one under 'model_state_dict' / 'state_dict', with
+# or without DataParallel's 'module.' prefix
+CHECKPOINTS["crica"] = Checkpoint(
+    "MLGATE_CRICAVPR_WEIGHTS", crica_keys, crica_state_dict, "CricaVPR", ("model_state_dict", "state_dict"),
+    rewrite=lambda k: k[len("module."):] if k.startswith("module.") else k,
+    check=_crica_refuse_foreign_backbone, finish=_crica_reshape_head)
+load_crica_state_dict = functools.partial(load_checkpoint, "crica")
+resolve_crica_state_dict = functools.partial(resolve_checkpoint, "crica")
