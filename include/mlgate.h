@@ -365,6 +365,40 @@ size_t mlg_xcorr_batch_workspace_bytes(int F, int L, int D, int P);
 int mlg_xcorr_batch(const float* feats, int F, int L, int D, const int32_t* query, const int32_t* cand, int P,
                     void* workspace, size_t workspace_bytes, float* scores, void* stream);
 
+/* CricaVPR.rerank_candidates (place_recognition.py:714-757) for every query row of
+ * mlg_knn_gate's output, on the device: asynchronous on `stream`, no host synchronisation.
+ * feats: f32 [F, L, D] local features of the F bank frames (not normalised); query row i is
+ * frame q0 + i; idx / sim int32 / f32 [Q, k] and count int32 [Q] as mlg_knn_gate wrote them
+ * (count is clamped to [0, k]); mask_or_null uint8 [Q, k]: entries with a zero byte are not
+ * candidates (never scored; the caller keeps emitting and counting them), NULL = every
+ * emitted entry; cached_or_null uint8 [F]: frames whose features are cached, NULL = all.
+ * Per row, over its masked entries in emission order:
+ *   combined = 0.5 * float64(sim) + 0.5 * float64(cross), where cross is bit-identical to
+ *   mlg_xcorr_batch's score of (query = q0 + i, cand = idx) on the same bank, in either order
+ *   of the pair; a candidate that is not cached, or whose index lies outside [0, F) (never
+ *   read), scores combined = float64(sim);
+ *   stable descending sort by combined (equal scores keep emission order); the first top_k
+ *   are kept.  A query frame that is not cached keeps its first top_k candidates unchanged,
+ *   with score = float64(sim).
+ * Outputs, [Q, top_k] in re-ranked order: r_idx int32, r_sim f32 (the global similarity,
+ * carried on unchanged), r_cross f32 (NaN where the entry was not scored), r_score f64
+ * (combined); r_count int32 [Q] = min(candidates, top_k).  Slots past r_count hold idx -1,
+ * sim 0, cross NaN, score 0.  dropped_total_or_null: a device uint64 that the number of
+ * candidates not kept is added to.
+ * Refused before any HIP call: MLG_EINVAL for a null required pointer, a non-positive size,
+ * k outside [1, 64], top_k outside [1, k], D % 4 != 0, L > 4096, q0 < 0 or q0 + Q > F;
+ * MLG_ENOMEM for a workspace below mlg_rerank_workspace_bytes (0 for a bad shape).  The
+ * The workspace layout, every buffer rounded up to 256 bytes:
+ *   normalised bank f32 [F, L, D]   cross score per slot f32 [Q, k]
+ * (tests/test_rerank_cpu.py restates it; the sizes recorded in
+ * tests/golden/workspace_sizes.json are those of the earlier queries.) */
+extern size_t mlg_rerank_workspace_bytes(int F, int L, int D, int Q, int k);
+int mlg_rerank_gate(const float* feats, int F, int L, int D, int q0, int Q, int k, const int32_t* idx,
+                    const float* sim, const uint8_t* mask_or_null, const int32_t* count,
+                    const uint8_t* cached_or_null, int top_k, void* workspace, size_t workspace_bytes,
+                    int32_t* r_idx, float* r_sim, float* r_cross, double* r_score, int32_t* r_count,
+                    unsigned long long* dropped_total_or_null, void* stream);
+
 /* ----------------------------------------------------------- op-level access --
  * Individual kernels of the ViT path (parity tests against a float32 reference). */
 int mlg_op_gemm_f32out(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, void* stream);

@@ -723,6 +723,18 @@ int mlg_xcorr_batch(const float* feats, int F, int L, int D, const int32_t* quer
                                (hipStream_t)stream);
 }
 
+size_t mlg_rerank_workspace_bytes(int F, int L, int D, int Q, int k) { return mlg_rerank_ws_bytes(F, L, D, Q, k); }
+
+int mlg_rerank_gate(const float* feats, int F, int L, int D, int q0, int Q, int k, const int32_t* idx,
+                    const float* sim, const uint8_t* mask_or_null, const int32_t* count,
+                    const uint8_t* cached_or_null, int top_k, void* workspace, size_t workspace_bytes,
+                    int32_t* r_idx, float* r_sim, float* r_cross, double* r_score, int32_t* r_count,
+                    unsigned long long* dropped_total_or_null, void* stream) {
+    return mlg_rerank_run(feats, F, L, D, q0, Q, k, idx, sim, mask_or_null, count, cached_or_null, top_k, workspace,
+                          workspace_bytes, r_idx, r_sim, r_cross, r_score, r_count, dropped_total_or_null,
+                          (hipStream_t)stream);
+}
+
 int mlg_op_gemm_f32out(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, void* stream) {
     return mlg_gemm_f32out(A, W, C, M, N, K, (hipStream_t)stream);
 }

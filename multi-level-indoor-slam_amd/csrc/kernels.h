@@ -144,6 +144,13 @@ int mlg_knn_fused(const float* Xq, int Q, const float* Xd, int N, int D, const d
                   float thr, int k, int gating, void* ws, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
                   unsigned long long* totals, hipStream_t s);
 
+// rerank.hip -- CricaVPR.rerank_candidates over mlg_knn_gate's lists: fused cross-correlation + selection
+size_t mlg_rerank_ws_bytes(int F, int L, int D, int Q, int k);
+int mlg_rerank_run(const float* feats, int F, int L, int D, int q0, int Q, int k, const int32_t* idx,
+                   const float* sim, const uint8_t* mask, const int32_t* count, const uint8_t* cached, int top_k,
+                   void* ws, size_t ws_bytes, int32_t* r_idx, float* r_sim, float* r_cross, double* r_score,
+                   int32_t* r_count, unsigned long long* dropped, hipStream_t s);
+
 // proximity.hip -- trajectory-proximity candidates + floor gate
 bool mlg_proximity_shape_ok(int N, int row0, int nrows);
 size_t mlg_proximity_ws_bytes(int N, int nrows);

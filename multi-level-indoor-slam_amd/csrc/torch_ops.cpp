@@ -480,6 +480,58 @@ Tensor xcorr_batch(const Tensor& feats, const Tensor& query, const Tensor& cand)
     return out;
 }
 
+// CricaVPR.rerank_candidates over knn_gate's lists: feats f32 [F, L, D]; idx / sim / mask [Q, k], count [Q];
+// cached uint8 [F] or none; totals int64 [1] or none -> r_idx, r_sim, r_cross, r_score [Q, top_k], r_count [Q]
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rerank_gate(const Tensor& feats, const Tensor& idx,
+                                                               const Tensor& sim, const c10::optional<Tensor>& mask,
+                                                               const Tensor& count, int64_t top_k, int64_t q0,
+                                                               const c10::optional<Tensor>& cached,
+                                                               const c10::optional<Tensor>& totals) {
+    want(feats, at::kFloat, "feats");
+    want(idx, at::kInt, "idx");
+    want(sim, at::kFloat, "sim");
+    want(count, at::kInt, "count");
+    TORCH_CHECK(feats.dim() == 3 && feats.size(2) % 4 == 0, "feats [F, L, D] with D % 4 == 0");
+    TORCH_CHECK(idx.dim() == 2 && sim.sizes() == idx.sizes() && count.numel() == idx.size(0),
+                "idx / sim [Q, k], count [Q]");
+    const int64_t F = feats.size(0), L = feats.size(1), D = feats.size(2), Q = idx.size(0), k = idx.size(1);
+    TORCH_CHECK(k >= 1 && k <= 64, "rerank_gate: k must be in [1, 64]");
+    TORCH_CHECK(top_k >= 1 && top_k <= k, "rerank_gate: top_k must be in [1, k]");
+    TORCH_CHECK(q0 >= 0 && q0 + Q <= F, "query rows out of range");
+    const bool has_mask = mask.has_value() && mask->defined();
+    const bool has_cached = cached.has_value() && cached->defined();
+    const bool has_totals = totals.has_value() && totals->defined();
+    if (has_mask) {
+        want(*mask, at::kByte, "mask");
+        TORCH_CHECK(mask->sizes() == idx.sizes(), "mask must be uint8 [Q, k]");
+    }
+    if (has_cached) {
+        want(*cached, at::kByte, "cached");
+        TORCH_CHECK(cached->numel() == F, "cached must be uint8 [F]");
+    }
+    if (has_totals) {
+        want(*totals, at::kLong, "totals");
+        TORCH_CHECK(totals->numel() == 1, "totals must be int64 [1]");
+    }
+    c10::DeviceGuard g(feats.device());
+    auto o = feats.options();
+    Tensor r_idx = at::empty({Q, top_k}, o.dtype(at::kInt)), r_sim = at::empty({Q, top_k}, o.dtype(at::kFloat));
+    Tensor r_cross = at::empty({Q, top_k}, o.dtype(at::kFloat)), r_score = at::empty({Q, top_k}, o.dtype(at::kDouble));
+    Tensor r_count = at::empty({Q}, o.dtype(at::kInt));
+    if (Q == 0) return {r_idx, r_sim, r_cross, r_score, r_count};
+    const size_t nbytes = mlg_rerank_workspace_bytes((int)F, (int)L, (int)D, (int)Q, (int)k);
+    TORCH_CHECK(nbytes > 0, "rerank_gate: unsupported shape F=", F, " L=", L, " D=", D, " Q=", Q, " k=", k);
+    Tensor ws = workspace(nbytes, feats);
+    check_rc(mlg_rerank_gate(cp<float>(feats), (int)F, (int)L, (int)D, (int)q0, (int)Q, (int)k, cp<int32_t>(idx),
+                             cp<float>(sim), has_mask ? cp<uint8_t>(*mask) : nullptr, cp<int32_t>(count),
+                             has_cached ? cp<uint8_t>(*cached) : nullptr, (int)top_k, ws.data_ptr(),
+                             (size_t)ws.numel(), mp<int32_t>(r_idx), mp<float>(r_sim), mp<float>(r_cross),
+                             mp<double>(r_score), mp<int32_t>(r_count),
+                             has_totals ? mp<unsigned long long>(*totals) : nullptr, stream_of(feats)),
+             "mlg_rerank_gate");
+    return {r_idx, r_sim, r_cross, r_score, r_count};
+}
+
 // --------------------------------------------------------------- LightGlue
 std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const Tensor& desc, const Tensor& counts,
                                                      const Tensor& pair_a, const Tensor& pair_b, at::TensorList w,
@@ -1136,6 +1188,8 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("similarity(Tensor A, Tensor B) -> Tensor");
     m.def("xcorr_score(Tensor q, Tensor m) -> Tensor");
     m.def("xcorr_batch(Tensor feats, Tensor query, Tensor cand) -> Tensor");
+    m.def("rerank_gate(Tensor feats, Tensor idx, Tensor sim, Tensor? mask, Tensor count, int top_k, int q0, "
+          "Tensor? cached, Tensor(a!)? totals) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("superpoint(Tensor frames, Tensor[] weights, float detection_threshold, int max_keypoints, "
           "int nms_radius, int remove_borders, bool with_bf16) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("lightglue(Tensor kpts, Tensor desc, Tensor counts, Tensor pair_a, Tensor pair_b, Tensor[] weights, "
@@ -1197,6 +1251,7 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("similarity", &similarity);
     m.impl("xcorr_score", &xcorr_score);
     m.impl("xcorr_batch", &xcorr_batch);
+    m.impl("rerank_gate", &rerank_gate);
     m.impl("superpoint", &superpoint);
     m.impl("lightglue", &lightglue);
     m.impl("ransac_epipolar", &ransac_epipolar);

@@ -8,6 +8,8 @@ the reference's public APIs, and this module is that harness:
   2. descriptors   SemanticPlaceRecognition('cricavpr').add_image per keyframe
                    (place_recognition.py:843-849; here one batched add_images);
   3. retrieval     find_loop_closures(enable_floor_gating, k) (:851-911);
+  3b. re-ranking   (opt-in, rerank_top_k) CricaVPR.rerank_candidates (:714-757) over each
+                   query's valid matches: the first rerank_top_k go on to the verifier;
   4. verification  SemanticGeometricVerifier.verify_with_semantics on every retrieved
                    match with is_valid (geometric_verification.py:688-734; batched);
   5. gate          SemanticLoopClosureGate(floor_labels).gate_candidates on the
@@ -73,6 +75,8 @@ class GateReport:
     verifier_stats: Dict
     gate_stats: Dict
     rejections: RejectionCount = field(default_factory=RejectionCount)
+    # rerank_top_k: the matches the re-ranking stage did not keep (not a rejection term)
+    reranked_out: List[PlaceMatch] = field(default_factory=list)
 
 
 def floor_labels_from_imu(timestamps, imu, start_floor=5, detector_kwargs=None):
@@ -91,8 +95,20 @@ class FullSemanticGate:
                  similarity_threshold: float = 0.5, min_time_gap: float = 10.0, k: int = 10, min_inliers: int = 20,
                  min_inlier_ratio: float = 0.25, strict_mode: bool = True, retrieval_floor_gating: bool = True,
                  verifier_floor_gating: bool = True, verify_rejected: bool = False, start_floor: int = 5,
-                 imu_detector_kwargs: Optional[Dict] = None, backbone: str = 'dinov2_vitb14'):
+                 imu_detector_kwargs: Optional[Dict] = None, backbone: str = 'dinov2_vitb14',
+                 rerank_top_k: Optional[int] = None):
         self.vpr_method, self.matcher_type, self.device = vpr_method, matcher_type, device
+        # rerank_top_k: CricaVPR.rerank_candidates (place_recognition.py:714-757) between
+        # retrieval and verification, as DeviceGate(rerank_top_k=...) runs it; None: no such stage
+        if rerank_top_k is not None:
+            if vpr_method != 'cricavpr':
+                raise ValueError(f"rerank_top_k needs CricaVPR's cached local features; the {vpr_method} method "
+                                 "caches none")
+            if int(rerank_top_k) < 1:
+                raise ValueError(f"rerank_top_k must be >= 1 (got {rerank_top_k})")
+            if k > 64:
+                raise ValueError(f"rerank_top_k takes k <= 64 (got k = {k})")
+        self.rerank_top_k = None if rerank_top_k is None else int(rerank_top_k)
         # the DINOv2 backbone of the 'cricavpr' / 'anyloc' methods (dinov2_vits14 / b14 / l14)
         self.backbone = backbone
         self.similarity_threshold, self.min_time_gap, self.k = similarity_threshold, min_time_gap, k
@@ -134,6 +150,9 @@ class FullSemanticGate:
         self.spr.add_images(frames, timestamps.tolist(), labels)
         matches = self.spr.find_loop_closures(enable_floor_gating=self.retrieval_floor_gating, k=self.k)
         to_verify = [m for m in matches if m.is_valid or self.verify_rejected]
+        reranked_out = []
+        if self.rerank_top_k is not None:
+            to_verify, reranked_out = self._rerank(to_verify, len(timestamps))
         self.verifier = SemanticGeometricVerifier(self.matcher_type, self.device, self.min_inliers,
                                                   self.min_inlier_ratio, enable_floor_gating=self.verifier_floor_gating)
         pairs = [(m.query_idx, m.match_idx) for m in to_verify]
@@ -151,7 +170,46 @@ class FullSemanticGate:
         return GateReport(floor_labels=floor_labels, events=events, matches=matches, verified=to_verify,
                           results=results, accepted=accepted, rejected=rejected,
                           retrieval_stats=self.spr.get_statistics(matches), verifier_stats=vstats,
-                          gate_stats=gstats, rejections=counts)
+                          gate_stats=gstats, rejections=counts, reranked_out=reranked_out)
+
+    def _rerank(self, to_verify, n):
+        """(kept, dropped) of the matches bound for the verifier: each query's matches, in
+        emission order, through mlg_rerank_gate over the cached local features; the kept ones
+        row-major by query and in re-ranked order within a row, similarities unchanged."""
+        import torch
+        from . import retrieval
+        vpr = self.spr.vpr
+        rows = {}
+        for m in to_verify:
+            rows.setdefault(m.query_idx, []).append(m)
+        k = max([len(r) for r in rows.values()] + [1])
+        idx, sim = np.zeros((n, k), np.int32), np.zeros((n, k), np.float32)
+        count = np.zeros(n, np.int32)
+        for q, r in rows.items():
+            idx[q, :len(r)] = [m.match_idx for m in r]
+            sim[q, :len(r)] = [m.similarity for m in r]
+            count[q] = len(r)
+        cache = vpr._feature_cache if vpr.use_reranking else {}
+        cached = np.array([f in cache for f in range(n)], np.uint8)
+        some = next(iter(cache.values())) if cache else None
+        if some is None:  # nothing cached: every row keeps its first top_k
+            bank = torch.zeros(n, 1, 4, device=torch.device(self.device))
+        else:
+            some = vpr._to_device_feats(some)
+            bank = torch.zeros((n,) + tuple(some.shape), device=some.device)
+            for f, v in cache.items():
+                bank[f].copy_(vpr._to_device_feats(v))
+        dev = bank.device
+        r_idx, _, _, _, r_count = retrieval.rerank_gate(
+            bank, torch.from_numpy(idx).to(dev), torch.from_numpy(sim).to(dev), None, torch.from_numpy(count).to(dev),
+            min(self.rerank_top_k, k), cached=torch.from_numpy(cached).to(dev))
+        r_idx, r_count = r_idx.cpu().numpy(), r_count.cpu().numpy()
+        kept = []
+        for q in sorted(rows):
+            by_idx = {m.match_idx: m for m in rows[q]}
+            kept += [by_idx[int(j)] for j in r_idx[q, :r_count[q]]]
+        keep_ids = {id(m) for m in kept}
+        return kept, [m for m in to_verify if id(m) not in keep_ids]
 
 
 class DeviceGate:
@@ -171,7 +229,14 @@ class DeviceGate:
                  verifier_floor_gating=True, verify=True, K=None, min_inliers=20, min_inlier_ratio=0.25,
                  vit_batch=123, sp_batch=64, lg_chunk=1024, max_keypoints=2048, vit_state_dict=None, record=False,
                  vit_precise=True, matcher='lightglue', loftr_chunk=256, max_pairs=None, lg_tail=0,
-                 local_features=True, backbone='dinov2_vitb14'):
+                 local_features=True, backbone='dinov2_vitb14', rerank_top_k=None):
+        if rerank_top_k is not None:  # refused before anything is built
+            if not local_features:
+                raise ValueError("rerank_top_k needs the local features: local_features=True")
+            if int(rerank_top_k) < 1:
+                raise ValueError(f"rerank_top_k must be >= 1 (got {rerank_top_k})")
+            if int(k) > 64:
+                raise ValueError(f"rerank_top_k takes k <= 64 (got k = {k})")
         import torch
         from . import distributed as mdist
         from .lightglue import LightGlueGPU
@@ -220,11 +285,23 @@ class DeviceGate:
                          else torch.empty(self.n_local, EMBED, device=self.dev))
         # CricaVPR's per-keyframe local features (place_recognition.py:645-667, the input of
         # rerank_candidates), written by the same ViT forward: [N, 528, 768] f32 at ViT-B, 1.6 MB per
-        # keyframe.  local_features=False leaves them unmaterialised (the gate itself never
-        # reads them): the N = 19,163 sequence then fits one GPU with its LightGlue workspace
+        # keyframe.  local_features=False leaves them unmaterialised (the gate reads them only
+        # with rerank_top_k): the N = 19,163 sequence then fits one GPU with its LightGlue workspace
         self.local_feats = (torch.empty(self.n_local, self.eng.n_local, EMBED, dtype=torch.float32, device=self.dev)
                             if local_features else None)
         self.totals = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        # rerank_top_k: CricaVPR.rerank_candidates (place_recognition.py:714-757) between
+        # retrieval and verification -- the valid entries of each query row re-ranked by
+        # 0.5 global + 0.5 local cross-correlation, the first rerank_top_k handed to the
+        # verifier (mlg_rerank_gate).  None: the stage does not exist.  With several ranks the
+        # bank of local features is all-gathered: every rank then holds all N keyframes'
+        # [528, EMBED] f32 features (1.6 MB per keyframe at ViT-B)
+        self.rerank_top_k = None
+        if rerank_top_k is not None:
+            self.rerank_top_k = int(rerank_top_k)
+            self.feat_gather = (mdist.RowGather(N, self.eng.n_local * EMBED, world, self.dev) if world > 1
+                                else None)
+        self.last_rerank = None
         self.verify = verify
         # matcher: 'lightglue' (SuperPoint + LightGlue, the reference default) or 'loftr'
         # (GeometricVerifier('loftr'), geometric_verification.py:424-526; BASELINE configs[4])
@@ -319,7 +396,15 @@ class DeviceGate:
                                                     Q=self.n_local, totals=self.totals)
         # the retrieval lists come to the host once (Q x k entries): the pair list that
         # drives the verifier's chunks is built there, with no further device syncs
-        h_idx, h_valid, h_count = (x.cpu().numpy() for x in (idx, valid, count))
+        rr = ()
+        if self.rerank_top_k is not None:
+            bank = self.local_feats
+            if self.world > 1:  # every rank's keyframes' local features, in keyframe order
+                bank = self.feat_gather(self.local_feats.view(self.n_local, -1)).view(
+                    self.N, self.local_feats.shape[1], self.local_feats.shape[2])
+            rr = retrieval.rerank_gate(bank, idx, sim, valid, count, min(self.rerank_top_k, idx.shape[1]),
+                                       q0=self.lo)
+        h_idx, h_valid, h_count, *h_rr = (x.cpu().numpy() for x in (idx, valid, count) + tuple(rr))
         if self.record:  # this rank's query rows: idx / sim / valid [Q, k], count [Q] (host)
             self.last_retrieval = (h_idx, sim.cpu().numpy(), h_valid, h_count)
         k = idx.shape[1]
@@ -329,6 +414,19 @@ class DeviceGate:
                "accepted": 0}
         # PlaceMatch.is_valid == False: emitted but floor-rejected
         out["retrieval_floor_rejected"] = int((live & (h_valid == 0)).sum())
+        # matches handed to verify_with_semantics: the is_valid ones, row-major by query
+        qs, js = np.nonzero(live & (h_valid != 0))
+        pa_h, pb_h = (qs + self.lo).astype(np.int32), h_idx[qs, js].astype(np.int32)
+        if h_rr:
+            # re-ranking on: the kept entries instead, in re-ranked order within a row.
+            # reranked_out is not a rejection term (RejectionCount keeps its four)
+            r_idx, r_count = h_rr[0], h_rr[4]
+            if self.record:  # r_idx / r_sim / r_cross / r_score [Q, top_k], r_count [Q] (host)
+                self.last_rerank = tuple(h_rr)
+            out["rerank_candidates"] = len(qs)
+            qs, js = np.nonzero(np.arange(r_idx.shape[1])[None, :] < r_count[:, None])
+            pa_h, pb_h = (qs + self.lo).astype(np.int32), r_idx[qs, js].astype(np.int32)
+            out["reranked_out"] = out["rerank_candidates"] - len(qs)
         if not self.verify:
             return out
         # SuperPoint once per keyframe (the reference re-extracts per pair), cached in HBM.
@@ -345,9 +443,7 @@ class DeviceGate:
             torch.cuda.current_stream(self.dev).wait_event(sp_ev)
         elif self.matcher == 'lightglue' and not self._sp_overlap:
             self._extract_rows(np.arange(self.n_local))
-        # matches handed to verify_with_semantics (is_valid ones), skip rule on floors
-        qs, js = np.nonzero(live & (h_valid != 0))
-        pa_h, pb_h = (qs + self.lo).astype(np.int32), h_idx[qs, js].astype(np.int32)
+        # the verifier's skip rule on floors
         if self.verifier_floor_gating:
             # verify_with_semantics skips when floor1 != floor2 in Python
             # (geometric_verification.py:709-710): None == None only, NaN != NaN

@@ -56,6 +56,26 @@ def knn_query(db, qdesc, t_db, t_query, min_gap, k):
     return _native.ops().knn_query(db, qdesc, t_db, t_query, float(min_gap), int(k))
 
 
+def rerank_gate(feats, idx, sim, mask, count, top_k, q0=0, cached=None, totals=None):
+    """CricaVPR.rerank_candidates (place_recognition.py:714-757) for every query row of
+    knn_gate's output, on the device and asynchronous on the current stream
+    (mlg_rerank_gate).  feats f32 [F, L, D]: the local features of the bank frames, query
+    row i being frame q0 + i; idx / sim [Q, k], count [Q] as knn_gate returned them; mask
+    uint8 [Q, k] (or None: every emitted entry): the entries that are candidates; cached
+    uint8 [F] (or None: all) marks the frames whose features are cached; totals int64 [1]
+    (or None) is added the number of candidates that were not kept.
+
+    Returns device tensors r_idx int32, r_sim f32 (the global similarity), r_cross f32 (NaN
+    where the entry was not scored), r_score f64 -- all [Q, top_k], each row in re-ranked
+    order -- and r_count int32 [Q]."""
+    k = idx.shape[1]
+    if not 1 <= k <= 64:
+        raise ValueError(f"rerank_gate takes k in [1, 64] (got {k})")
+    if not 1 <= top_k <= k:
+        raise ValueError(f"top_k must be in [1, k = {k}] (got {top_k})")
+    return _native.ops().rerank_gate(feats, idx, sim, mask, count, int(top_k), int(q0), cached, totals)
+
+
 def xcorr_score(qf, mf):
     """CricaVPR.compute_cross_correlation_score on device float32 [n1, D] / [n2, D] -> device scalar."""
     return _native.ops().xcorr_score(qf.contiguous(), mf.contiguous())
