@@ -28,13 +28,13 @@ Two front ends run the same kernels:
     process per GPU, RCCL all-gathers; bench.py's step).  Its decisions and counts are
     those of FullSemanticGate (tests/test_pipeline_gpu.py).
 """
-import os
+import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import _native
+from . import _native, gate_plan
 
 from .floors import IMUFloorDetector
 from .gate import LoopClosureCandidate, SemanticLoopClosureGate
@@ -212,6 +212,23 @@ class FullSemanticGate:
         return kept, [m for m in to_verify if id(m) not in keep_ids]
 
 
+def decide_pairs(n, inl, ta, tb, f_num, limit, min_inliers, min_inlier_ratio, n_valid_t, gate_rej_t):
+    """The verifier's decision rule (geometric_verification.py:602-620) and the floor gate
+    (loop_closure_gate.py:91-98) for a chunk of pairs, on tensors of any one device: match
+    counts n and inlier counts inl [P], keyframe indices ta / tb [P] (int64) into the numeric
+    floor labels f_num.  Returns ok [P] and adds the geometrically valid pairs to n_valid_t,
+    those of them the floor gate rejects to gate_rej_t (0-d int64), with no host sync.
+    Deviation, by design: a None label is NaN in f_num and never rejects, where the
+    reference's host gate computes abs(None - None) and raises TypeError
+    (loop_closure_gate.py:89; the drop-in SemanticLoopClosureGate keeps that TypeError,
+    tests/test_api_cpu.py::test_gate_none_labels_raise_nan_labels_accept)."""
+    ratio = inl.double() / n.clamp(min=1).double()
+    ok = (n >= 5) & (inl >= min_inliers) & (ratio >= min_inlier_ratio)
+    n_valid_t += ok.sum()
+    gate_rej_t += (ok & ((f_num[ta] - f_num[tb]).abs() > limit)).sum()
+    return ok
+
+
 class DeviceGate:
     """The same chain on device arrays for a frame-sharded sequence: rank r of W owns
     keyframes [r N / W, (r + 1) N / W) -- its frames, ViT forwards and SuperPoint
@@ -229,7 +246,7 @@ class DeviceGate:
                  verifier_floor_gating=True, verify=True, K=None, min_inliers=20, min_inlier_ratio=0.25,
                  vit_batch=123, sp_batch=64, lg_chunk=1024, max_keypoints=2048, vit_state_dict=None, record=False,
                  vit_precise=True, matcher='lightglue', loftr_chunk=256, max_pairs=None, lg_tail=0,
-                 local_features=True, backbone='dinov2_vitb14', rerank_top_k=None):
+                 local_features=True, backbone='dinov2_vitb14', rerank_top_k=None, overlap=True, lg_dedup=True):
         if rerank_top_k is not None:  # refused before anything is built
             if not local_features:
                 raise ValueError("rerank_top_k needs the local features: local_features=True")
@@ -310,12 +327,13 @@ class DeviceGate:
         self.matcher = matcher
         self.loftr_chunk = int(loftr_chunk)
         self.max_pairs = max_pairs  # verify only the first max_pairs pairs of the global list (bench sub-runs)
+        if verify:
+            self.fx = mdist.FeatureExchange(N, world, rank) if world > 1 else None
+            self.K = (torch.from_numpy(np.asarray(K, np.float64).reshape(9).copy()).to(self.dev)
+                      if K is not None else None)
         if verify and matcher == 'loftr':
             from .loftr import LoFTRGPU
             self.lf = LoFTRGPU(device=self.dev, feature_batch=16)
-            self.fx = mdist.FeatureExchange(N, world, rank) if world > 1 else None
-            Kc = np.asarray(K if K is not None else np.eye(3), np.float64)
-            self.K = torch.from_numpy(Kc.reshape(9).copy()).to(self.dev) if K is not None else None
         elif verify:
             KP = max_keypoints
             self.sp = SuperPointGPU(device=self.dev, max_num_keypoints=KP)
@@ -324,12 +342,15 @@ class DeviceGate:
             # features of exactly the keyframes its verification slice touches
             self.kp_loc = torch.empty(self.n_local, KP * 2, device=self.dev)
             self.ds_loc = torch.empty(self.n_local, KP * 256, device=self.dev)
-            # zeros: with the SuperPoint overlap the first chunk's call sees rows not yet
-            # extracted this step, and mlg_lightglue range-checks every count
             self.cnt_loc = torch.zeros(self.n_local, 1, dtype=torch.int32, device=self.dev)
-            self.fx = mdist.FeatureExchange(N, world, rank) if world > 1 else None
-            Kc = np.asarray(K if K is not None else np.eye(3), np.float64)
-            self.K = torch.from_numpy(Kc.reshape(9).copy()).to(self.dev) if K is not None else None
+        # overlap=True: the step on a high-priority stream, SuperPoint on a side stream under
+        # the ViT and the kNN, each LightGlue chunk's RANSAC on a side stream under the next
+        # chunk (step, _step, _verify_lightglue).  overlap=False: everything on the caller's
+        # current stream at normal priority, in program order -- the same results (tests/
+        # test_pipeline_gpu.py::test_stream_overlap_changes_nothing) and serial stage times.
+        # lg_dedup=False: LightGlue on every ordered pair, not once per unordered pair.
+        self.overlap, self.lg_dedup = bool(overlap), bool(lg_dedup)
+        self._hi = self._sp_stream = self._side = None  # made by the first overlapped step
         self.last = {}
         # record=True: step() keeps every verified ordered pair's (a, b, matches, inliers,
         # is_valid) in self.last_pair_results (host arrays in verification order)
@@ -341,20 +362,6 @@ class DeviceGate:
         self.last_pair_results = None
         self.last_retrieval = None
 
-    def _dedup(self):
-        """Match each unordered pair once (MLGATE_LG_DEDUP=0: every ordered pair, for A/B)."""
-        import os
-        return os.environ.get("MLGATE_LG_DEDUP", "1") != "0"
-
-    def _side_stream(self):
-        """The RANSAC stream (MLGATE_RANSAC_SIDE=0: the main stream, for A/B runs)."""
-        if getattr(self, "_side", None) is None:
-            import os
-            same = os.environ.get("MLGATE_RANSAC_SIDE", "1") == "0"
-            self._side = (self.torch.cuda.current_stream(self.dev) if same
-                          else self.torch.cuda.Stream(device=self.dev))
-        return self._side
-
     def step(self):
         """Gate the sequence once.  Returns this rank's counts (dict of ints): matches,
         the four rejection terms, pairs verified, pairs geometrically valid, accepted.
@@ -362,13 +369,14 @@ class DeviceGate:
         workgroups ahead of the side streams' (RANSAC, SuperPoint): they fill the gaps and
         kernel tails instead of taking CUs from the LightGlue kernels (same-box A/B,
         profiles/r06p_ab_main_priority.txt: attention -2 % per launch, step time equal).
-        MLGATE_MAIN_PRIORITY=0: everything at normal priority (A/B)."""
-        import os
-        if os.environ.get("MLGATE_MAIN_PRIORITY", "1") != "1":
+        overlap=False: everything on the caller's stream, at normal priority."""
+        if not self.overlap:
             return self._step()
         torch = self.torch
-        if getattr(self, "_hi", None) is None:
+        if self._hi is None:
             self._hi = torch.cuda.Stream(device=self.dev, priority=-1)
+            if self.verify and self.matcher == 'lightglue':  # SuperPoint's and RANSAC's side streams
+                self._sp_stream, self._side = torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev)
         cur = torch.cuda.current_stream(self.dev)
         self._hi.wait_stream(cur)
         with torch.cuda.stream(self._hi):
@@ -378,15 +386,14 @@ class DeviceGate:
 
     def _step(self):
         torch = self.torch
-        from . import geometry, retrieval
+        from . import retrieval
+        lightglue = self.verify and self.matcher == 'lightglue'
         # SuperPoint of every local keyframe on its side stream (normal priority) while the
         # ViT and the kNN run on this one (high priority): it fills the ViT kernels' tails and
         # the CUs its LayerNorm / attention launches leave free (same-box ABAB, profiles/
         # r06u_ab_sp_under_vit.txt: -0.4 % step time, counts identical).  The LightGlue stage
-        # waits on its event.  MLGATE_SP_UNDER_VIT=0: SuperPoint after them on this stream.
-        sp_ev = None
-        if self.verify and self.matcher == 'lightglue' and os.environ.get("MLGATE_SP_UNDER_VIT", "1") == "1":
-            sp_ev = self._extract_side(np.arange(self.n_local))
+        # waits on its event.  overlap=False: SuperPoint after them on this stream.
+        sp_ev = self._extract_side(np.arange(self.n_local)) if lightglue and self.overlap else None
         self.eng.forward_into(self.frames, self.desc_loc, self.local_feats)
         if self.world > 1:
             self.gather(self.desc_loc)  # RCCL all-gather of the descriptors over xGMI
@@ -407,48 +414,27 @@ class DeviceGate:
         h_idx, h_valid, h_count, *h_rr = (x.cpu().numpy() for x in (idx, valid, count) + tuple(rr))
         if self.record:  # this rank's query rows: idx / sim / valid [Q, k], count [Q] (host)
             self.last_retrieval = (h_idx, sim.cpu().numpy(), h_valid, h_count)
-        k = idx.shape[1]
-        live = np.arange(k)[None, :] < h_count[:, None]
-        out = {"matches": int(h_count.sum()), "retrieval_floor_rejected": 0, "skipped_floor_mismatch": 0,
+        matches, floor_rej, pa_h, pb_h = gate_plan.pairs_from_retrieval(h_idx, h_valid, h_count, self.lo)
+        out = {"matches": matches, "retrieval_floor_rejected": floor_rej, "skipped_floor_mismatch": 0,
                "verifier_invalid": 0, "gate_rejected_cross_floor": 0, "pairs_verified": 0, "verified_valid": 0,
                "accepted": 0}
-        # PlaceMatch.is_valid == False: emitted but floor-rejected
-        out["retrieval_floor_rejected"] = int((live & (h_valid == 0)).sum())
-        # matches handed to verify_with_semantics: the is_valid ones, row-major by query
-        qs, js = np.nonzero(live & (h_valid != 0))
-        pa_h, pb_h = (qs + self.lo).astype(np.int32), h_idx[qs, js].astype(np.int32)
         if h_rr:
             # re-ranking on: the kept entries instead, in re-ranked order within a row.
             # reranked_out is not a rejection term (RejectionCount keeps its four)
-            r_idx, r_count = h_rr[0], h_rr[4]
             if self.record:  # r_idx / r_sim / r_cross / r_score [Q, top_k], r_count [Q] (host)
                 self.last_rerank = tuple(h_rr)
-            out["rerank_candidates"] = len(qs)
-            qs, js = np.nonzero(np.arange(r_idx.shape[1])[None, :] < r_count[:, None])
-            pa_h, pb_h = (qs + self.lo).astype(np.int32), r_idx[qs, js].astype(np.int32)
-            out["reranked_out"] = out["rerank_candidates"] - len(qs)
+            out["rerank_candidates"] = len(pa_h)
+            pa_h, pb_h = gate_plan.pairs_from_rerank(h_rr[0], h_rr[4], self.lo)
+            out["reranked_out"] = out["rerank_candidates"] - len(pa_h)
         if not self.verify:
             return out
-        # SuperPoint once per keyframe (the reference re-extracts per pair), cached in HBM.
-        # MLGATE_SP_OVERLAP=1 (one rank): only the keyframes of the first LightGlue chunk
-        # are extracted up front, the rest on a side stream under that chunk
-        # (_verify_lightglue).  Same results, +0.2 % on the bench -- the LightGlue tile
-        # leaves SuperPoint's convolutions little room on a CU -- while the bench's
-        # per-stage HIP-event table would then time SuperPoint's launches with the
-        # concurrent LightGlue in them (profiles/r05p_ab_superpoint_overlap.txt): off by
-        # default.  Several ranks: all keyframes first (FeatureExchange ships finished rows).
-        self._sp_overlap = (sp_ev is None and self.world == 1 and self.matcher == 'lightglue'
-                            and os.environ.get("MLGATE_SP_OVERLAP", "0") == "1")
+        # SuperPoint once per keyframe (the reference re-extracts per pair), cached in HBM
         if sp_ev is not None:
             torch.cuda.current_stream(self.dev).wait_event(sp_ev)
-        elif self.matcher == 'lightglue' and not self._sp_overlap:
+        elif lightglue:
             self._extract_rows(np.arange(self.n_local))
-        # the verifier's skip rule on floors
-        if self.verifier_floor_gating:
-            # verify_with_semantics skips when floor1 != floor2 in Python
-            # (geometric_verification.py:709-710): None == None only, NaN != NaN
-            ha, hb = self.h_has[pa_h] != 0, self.h_has[pb_h] != 0
-            same = (ha & hb & (self.h_codes[pa_h] == self.h_codes[pb_h])) | (~ha & ~hb)
+        if self.verifier_floor_gating:  # the verifier's skip rule on floors
+            same = gate_plan.same_floor(pa_h, pb_h, self.h_codes, self.h_has)
             out["skipped_floor_mismatch"] = int((~same).sum())
             pa_h, pb_h = pa_h[same], pb_h[same]
         pa_t, pb_t = torch.from_numpy(pa_h).to(self.dev), torch.from_numpy(pb_h).to(self.dev)
@@ -457,13 +443,12 @@ class DeviceGate:
         # pair-level load balance across ranks: the pairs are re-balanced first (the union
         # of the slices is the global pair list), then FeatureExchange delivers each rank
         # exactly the SuperPoint features its own slice touches
-        dedup = self._dedup()
         if self.world > 1:
-            pa_t, pb_t = self.mdist.balanced_pairs(pa_t, pb_t, self.world, self.rank, group_reverse=dedup)
+            pa_t, pb_t = self.mdist.balanced_pairs(pa_t, pb_t, self.world, self.rank, group_reverse=self.lg_dedup)
             pa, pb = pa_t.cpu().numpy(), pb_t.cpu().numpy()
         else:
             pa, pb = pa_h, pb_h
-        return self._verify_lightglue(pa, pb, dedup, out)
+        return self._verify_lightglue(pa, pb, out)
 
     def _extract_rows(self, rows):
         """SuperPoint of the local keyframes `rows` (host int array, any order) into the
@@ -487,81 +472,85 @@ class DeviceGate:
                 self.ds_loc.index_copy_(0, dst, ds.view(len(r), -1))
                 self.cnt_loc.index_copy_(0, dst, cnt.view(-1, 1).to(self.cnt_loc.dtype))
 
-    def _verify_lightglue(self, pa, pb, dedup, out):
+    def _verify_lightglue(self, pa, pb, out):
         """SuperPoint features (local table or need-driven exchange) -> LightGlue (once per
-        unordered pair when dedup) -> RANSAC + decision + floor gate per ordered pair, for
+        unordered pair with lg_dedup) -> RANSAC + decision + floor gate per ordered pair, for
         this rank's slice (pa, pb) of the pair list (host int32 arrays); fills `out`."""
+        torch = self.torch
+        dedup = self.lg_dedup
         self.last_pairs = (pa, pb)
         # features of the keyframes the pairs touch: the local table (world 1), or the
         # need-driven exchange (row k of the compact tables = keyframe need[k])
         if self.world > 1:
             need = np.unique(np.concatenate([pa, pb]).astype(np.int64))
-            kp_c, ds_c, cnt_c = self.fx(need, [self.kp_loc, self.ds_loc, self.cnt_loc])
+            kp_t, ds_t, cnt_t = self.fx(need, [self.kp_loc, self.ds_loc, self.cnt_loc])
             nf = len(need)
             local = lambda x: np.searchsorted(need, x).astype(np.int32)  # noqa: E731
             out["features_exchanged_bytes"] = self.fx.last_bytes
         else:
-            kp_c, ds_c, cnt_c, nf = self.kp_loc, self.ds_loc, self.cnt_loc, self.N
+            kp_t, ds_t, cnt_t, nf = self.kp_loc, self.ds_loc, self.cnt_loc, self.N
             local = lambda x: np.asarray(x, np.int32)  # noqa: E731
-        kp_all = kp_c.view(nf, self.kp, 2)
-        ds_all = ds_c.view(nf, self.kp, 256)
+        kp_all = kp_t.view(nf, self.kp, 2)
+        ds_all = ds_t.view(nf, self.kp, 256)
         # LightGlue once per UNORDERED pair: it is symmetric in its two images (shared
         # weights; self / cross blocks, dual-softmax assignment, early stopping and pruning
         # treat both alike), so (b, a) is (a, b) with the image roles exchanged and the
         # matches re-sorted by the new image0 index (mlg_lg_orient_matches).  Every ORDERED
         # pair still gets its own RANSAC on its own match order and its own decision, as
         # verify_with_semantics gives each (query, match) (geometric_verification.py:688-744).
-        if dedup:
-            key = np.minimum(pa, pb).astype(np.int64) * self.N + np.maximum(pa, pb)
-            ukey, inv = np.unique(key, return_inverse=True)
-            ua, ub = (ukey // self.N).astype(np.int32), (ukey % self.N).astype(np.int32)
-            swap_all = (pa > pb).astype(np.uint8)
-        else:
-            ua, ub, inv, swap_all = pa, pb, np.arange(len(pa)), np.zeros(len(pa), np.uint8)
-        order = np.argsort(inv, kind="stable")
-        # chunk starts: full chunks, then (lg_tail > 0) the remainder cut so the LAST chunk
-        # is 1 / lg_tail of it -- that chunk's RANSAC is the only one with no LightGlue to
-        # overlap (per-pair results do not depend on the chunking)
-        chunk = self._lg_chunk_for(len(ua))
-        self.last_lg_chunk = chunk
-        starts = list(range(0, len(ua), chunk))
-        rem = len(ua) - starts[-1] if starts else 0
-        if self.lg_tail > 0 and rem >= 1024:
-            starts.append(len(ua) - max(256, rem // self.lg_tail))
-        starts.append(len(ua))
-        bounds = np.searchsorted(inv[order], np.asarray(starts))
+        ua, ub, inv, swap_all, order = gate_plan.unordered_plan(pa, pb, self.N, dedup)
+        chunk = self.last_lg_chunk = self._lg_chunk_for(len(ua))
+        starts, bounds = gate_plan.chunk_starts(len(ua), chunk, self.lg_tail, inv[order])
         out["pairs_matched_lightglue"] = len(ua)
         ua, ub = local(ua), local(ub)  # LightGlue indexes the feature tables
-        sp_done = None
-        if getattr(self, "_sp_overlap", False):
-            # the first chunk's keyframes now, the rest on a side stream under that chunk;
-            # only the finished rows' counts are read here (ADVICE r05: the side stream is
-            # writing the others), the rest once the side stream's event has passed
-            first = np.unique(np.concatenate([ua[:starts[1]], ub[:starts[1]]])) if len(starts) > 1 else \
-                np.zeros(0, np.int64)
-            self._extract_rows(first)
-            counts = np.zeros(nf, np.int32)
-            if len(first):
-                fi = self.torch.from_numpy(first.astype(np.int64)).to(self.dev)
-                counts[first] = cnt_c.view(-1).index_select(0, fi).cpu().numpy()
-            rest = np.setdiff1d(np.arange(self.n_local), first, assume_unique=True)
-            sp_done = self._extract_side(rest)
-        else:
-            counts = cnt_c.view(-1).cpu().numpy()
+        counts = cnt_t.view(-1).cpu().numpy()
         # RANSAC of chunk c runs on a side stream while LightGlue matches chunk c + 1 on
         # this one (mlg_lightglue waits on its stream once per layer; the side stream
-        # fills those gaps and the CUs the small RANSAC / assignment grids leave idle)
-        n_valid_t, gate_rej_t, rec = self._verify_chunks(starts, bounds, order, inv, ua, ub, pa, pb, swap_all, dedup,
-                                                         kp_all, ds_all, counts, local, sp_done, cnt_c)
+        # fills those gaps and the CUs the small RANSAC / assignment grids leave idle).
+        # overlap=False: the side stream is this one
+        main = torch.cuda.current_stream(self.dev)
+        side = self._side if self.overlap else main
+        n_valid_t, gate_rej_t, rec = self._tallies()
+        for ci in range(len(starts) - 1):
+            c0, c1 = starts[ci], starts[ci + 1]
+            mu, su, nu, _ = self.lg.match_device(kp_all, ds_all, counts, ua[c0:c1], ub[c0:c1])
+            sel = order[bounds[ci]:bounds[ci + 1]]  # the ordered pairs of these unordered ones
+            ca, cb = pa[sel], pb[sel]
+            if dedup:
+                rows = torch.from_numpy((inv[sel] - c0).astype(np.int32)).to(self.dev)
+                sw = torch.from_numpy(swap_all[sel]).to(self.dev)
+                m, _, n = _native.ops().lg_orient(mu, su, nu, rows, sw)
+            else:
+                m, n = mu, nu
+            ready = torch.cuda.Event()
+            ready.record(main)
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                m.record_stream(side)
+                n.record_stream(side)
+                # (every host -> device copy before the RANSAC launch: a copy waits for its stream)
+                ta = torch.from_numpy(ca).to(self.dev).long()  # global keyframe indices
+                tb = torch.from_numpy(cb).to(self.dev).long()
+                inl = self._ransac_inliers(kp_all, m, n, local(ca), local(cb))
+                ok = decide_pairs(n, inl, ta, tb, self.f_num, self.limit, self.min_inliers, self.min_inlier_ratio,
+                                  n_valid_t, gate_rej_t)
+                if rec is not None:
+                    rec.append((sel, n, inl, ok))
+        main.wait_stream(side)
+        return self._finish(out, pa, pb, n_valid_t, gate_rej_t, rec)
+
+    def _tallies(self):
+        """(n_valid_t, gate_rej_t, rec): the two device tallies decide_pairs adds to and,
+        with record, the list of the chunks' (sel, n, inl, ok)."""
+        z = lambda: self.torch.zeros((), dtype=self.torch.int64, device=self.dev)  # noqa: E731
+        return z(), z(), [] if self.record else None
+
+    def _finish(self, out, pa, pb, n_valid_t, gate_rej_t, rec):
+        """The verification's one device sync, then last_pair_results (record) and the counts."""
         n_valid, gate_rej = int(n_valid_t), int(gate_rej_t)
         if rec is not None:
-            r = {"a": pa, "b": pb, "matches": np.zeros(len(pa), np.int32), "inliers": np.zeros(len(pa), np.int32),
-                 "is_valid": np.zeros(len(pa), bool)}
-            for sel, n, inl, ok in rec:
-                r["matches"][sel] = n.cpu().numpy()
-                r["inliers"][sel] = inl.cpu().numpy()
-                r["is_valid"][sel] = ok.cpu().numpy()
-            self.last_pair_results = r
+            self.last_pair_results = gate_plan.pair_records(
+                pa, pb, [(sel,) + tuple(x.cpu().numpy() for x in dev) for sel, *dev in rec])
         out["pairs_verified"] = len(pa)
         out["verified_valid"] = n_valid
         out["verifier_invalid"] = len(pa) - n_valid
@@ -586,19 +575,13 @@ class DeviceGate:
         free += torch.cuda.memory_reserved(self.dev) - torch.cuda.memory_allocated(self.dev)
         avail = free - 0.06 * total - (4 << 30)
         per = _native.lightglue_workspace_bytes(1024, self.kp) / 1024 + self._RANSAC_PAIR_BYTES
-        chunk = int(max(avail, 0) // per) // 256 * 256
-        if chunk < 256:
-            raise MemoryError(f"LightGlue needs {per * 256 / 2**30:.1f} GiB for 256 pairs; "
-                              f"{max(avail, 0) / 2**30:.1f} GiB free")
-        return min(chunk, 5120, max(256, -(-n_pairs // 256) * 256))
+        return gate_plan.auto_chunk(avail, per, n_pairs)
 
     def _extract_side(self, rows):
         """_extract_rows on the SuperPoint side stream, after everything already queued on
         the current stream; returns the event the consumers of those rows wait on."""
         torch = self.torch
         main = torch.cuda.current_stream(self.dev)
-        if getattr(self, "_sp_stream", None) is None:
-            self._sp_stream = torch.cuda.Stream(device=self.dev)
         sps = self._sp_stream
         sps.wait_stream(main)
         with torch.cuda.stream(sps):
@@ -607,74 +590,30 @@ class DeviceGate:
         done.record(sps)
         return done
 
-    def _verify_chunks(self, starts, bounds, order, inv, ua, ub, pa, pb, swap_all, dedup, kp_all, ds_all, counts,
-                       local, sp_done=None, cnt_c=None):
+    def _ransac_inliers(self, kp_all, m, n, la, lb):
+        """Inlier counts [P] of one batched RANSAC (+ recoverPose when K is given) over the
+        matched keypoints of P pairs: matches m [P, kp, 2] with counts n [P] between rows
+        la / lb (host int arrays) of the feature table kp_all.  The flat match arrays are
+        laid out on the device without a host sync (no nonzero): pair p's matches go to
+        [offs[p], offs[p] + n[p]) of a buffer of P * kp rows (RANSAC reads each pair's own
+        range only), the padding of the match lists to one dummy row past the end."""
         torch = self.torch
         from . import geometry
-        main = torch.cuda.current_stream(self.dev)
-        side = self._side_stream()
-        n_valid_t = torch.zeros((), dtype=torch.int64, device=self.dev)
-        gate_rej_t = torch.zeros((), dtype=torch.int64, device=self.dev)
-        rec = [] if self.record else None
-        for ci in range(len(starts) - 1):
-            c0, c1 = starts[ci], starts[ci + 1]
-            if ci == 1 and sp_done is not None:  # the side-stream SuperPoint rows from here on
-                main.wait_event(sp_done)
-                counts = cnt_c.view(-1).cpu().numpy()
-                sp_done = None
-            mu, su, nu, _ = self.lg.match_device(kp_all, ds_all, counts, ua[c0:c1], ub[c0:c1])
-            sel = order[bounds[ci]:bounds[ci + 1]]  # the ordered pairs of these unordered ones
-            ca, cb = pa[sel], pb[sel]
-            if dedup:
-                rows = torch.from_numpy((inv[sel] - c0).astype(np.int32)).to(self.dev)
-                sw = torch.from_numpy(swap_all[sel]).to(self.dev)
-                m, _, n = _native.ops().lg_orient(mu, su, nu, rows, sw)
-            else:
-                m, n = mu, nu
-            ready = torch.cuda.Event()
-            ready.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ready)
-                m.record_stream(side)
-                n.record_stream(side)
-                # matched keypoints -> one batched RANSAC (+ recoverPose when K is given).
-                # The flat match arrays are laid out on the device without a host sync (no
-                # nonzero): pair p's matches go to [offs[p], offs[p] + n[p]) of a buffer of
-                # P * kmax rows (RANSAC reads each pair's own range only), the padding of
-                # the match lists to one dummy row past the end.
-                P = len(ca)
-                KP = self.kp
-                sidx = torch.arange(KP, device=self.dev)
-                lv = sidx[None, :] < n[:, None]
-                ta = torch.from_numpy(ca).to(self.dev).long()  # global keyframe indices
-                tb = torch.from_numpy(cb).to(self.dev).long()
-                la = torch.from_numpy(local(ca)).to(self.dev).long()  # feature-table rows
-                lb = torch.from_numpy(local(cb)).to(self.dev).long()
-                offs = torch.zeros(P + 1, dtype=torch.int32, device=self.dev)
-                offs[1:] = torch.cumsum(n, 0)
-                dest = torch.where(lv, offs[:-1, None].long() + sidx[None, :], P * KP).view(-1)
-                m0 = torch.where(lv, m[:, :, 0].long(), 0)
-                m1 = torch.where(lv, m[:, :, 1].long(), 0)
-                k1 = kp_all.new_zeros(P * KP + 1, 2)
-                k2 = kp_all.new_zeros(P * KP + 1, 2)
-                k1.index_copy_(0, dest, kp_all[la[:, None], m0].view(-1, 2))
-                k2.index_copy_(0, dest, kp_all[lb[:, None], m1].view(-1, 2))
-                _, _, inl, _, _ = geometry.epipolar_ransac_device(k1[:P * KP], k2[:P * KP], offs, self.K, 0, 3.0)
-                ratio = inl.double() / n.clamp(min=1).double()
-                ok = (n >= 5) & (inl >= self.min_inliers) & (ratio >= self.min_inlier_ratio)
-                n_valid_t += ok.sum()
-                if rec is not None:
-                    rec.append((sel, n, inl, ok))
-                # the floor gate on the geometrically valid pairs.  Deviation, by design: a
-                # None label is NaN here and never rejects, where the reference's host gate
-                # computes abs(None - None) and raises TypeError (loop_closure_gate.py:89;
-                # the drop-in SemanticLoopClosureGate keeps that TypeError,
-                # tests/test_api_cpu.py::test_gate_none_labels_raise_nan_labels_accept)
-                gate_rej_t += (ok & ((self.f_num[ta] - self.f_num[tb]).abs() > self.limit)).sum()
-        if sp_done is not None:  # one chunk only: the tables are complete when step() returns
-            main.wait_event(sp_done)
-        main.wait_stream(side)
-        return n_valid_t, gate_rej_t, rec
+        P, KP = len(la), self.kp
+        sidx = torch.arange(KP, device=self.dev)
+        lv = sidx[None, :] < n[:, None]
+        la = torch.from_numpy(la).to(self.dev).long()
+        lb = torch.from_numpy(lb).to(self.dev).long()
+        offs = torch.zeros(P + 1, dtype=torch.int32, device=self.dev)
+        offs[1:] = torch.cumsum(n, 0)
+        dest = torch.where(lv, offs[:-1, None].long() + sidx[None, :], P * KP).view(-1)
+        m0 = torch.where(lv, m[:, :, 0].long(), 0)
+        m1 = torch.where(lv, m[:, :, 1].long(), 0)
+        k1 = kp_all.new_zeros(P * KP + 1, 2)
+        k2 = kp_all.new_zeros(P * KP + 1, 2)
+        k1.index_copy_(0, dest, kp_all[la[:, None], m0].view(-1, 2))
+        k2.index_copy_(0, dest, kp_all[lb[:, None], m1].view(-1, 2))
+        return geometry.epipolar_ransac_device(k1[:P * KP], k2[:P * KP], offs, self.K, 0, 3.0)[2]
 
     def _verify_loftr(self, pa_t, pb_t, out):
         """verify_with_semantics with GeometricVerifier('loftr') on this rank's slice of the
@@ -688,7 +627,6 @@ class DeviceGate:
         and recomputed only for keyframes not already held."""
         torch = self.torch
         from . import geometry
-        import time
         if self.time_verify:
             torch.cuda.synchronize(self.dev)
         t_start = time.perf_counter()
@@ -710,19 +648,13 @@ class DeviceGate:
         order = np.lexsort((pb, pa))
         C = self.loftr_chunk
         cap = 4 * C
-        slot_of, free = {}, list(range(cap))
+        cache = gate_plan.SlotCache(cap)
         coarse = fine = None
-        n_valid_t = torch.zeros((), dtype=torch.int64, device=self.dev)
-        gate_rej_t = torch.zeros((), dtype=torch.int64, device=self.dev)
-        rec = [] if self.record else None
+        n_valid_t, gate_rej_t, rec = self._tallies()
         for c0 in range(0, len(order), C):
             sel = order[c0:c0 + C]
             ca, cb = pa[sel], pb[sel]
-            frs = np.unique(np.concatenate([ca, cb]))
-            keep = set(int(f) for f in frs)
-            for f in [f for f in slot_of if f not in keep] if len(free) < len(frs) else []:
-                free.append(slot_of.pop(f))
-            todo = [int(f) for f in frs if int(f) not in slot_of]
+            todo, slots = cache.assign(np.unique(np.concatenate([ca, cb])))
             if todo:
                 rows = [f if row_of is None else row_of[f] for f in todo]
                 if row_of is None:
@@ -731,13 +663,11 @@ class DeviceGate:
                 if coarse is None:
                     coarse = torch.empty((cap,) + tuple(cf_.shape[1:]), dtype=cf_.dtype, device=self.dev)
                     fine = torch.empty((cap,) + tuple(ff_.shape[1:]), dtype=ff_.dtype, device=self.dev)
-                slots = [free.pop() for _ in todo]
                 st = torch.as_tensor(slots, device=self.dev)
                 coarse.index_copy_(0, st, cf_)
                 fine.index_copy_(0, st, ff_)
-                slot_of.update(zip(todo, slots))
-            n, k0, k1, _ = self.lf.match_device(coarse, fine, H, W, [slot_of[int(a)] for a in ca],
-                                                [slot_of[int(b)] for b in cb])
+            n, k0, k1, _ = self.lf.match_device(coarse, fine, H, W, [cache.slot_of[int(a)] for a in ca],
+                                                [cache.slot_of[int(b)] for b in cb])
             n = n.to(self.dev).long()
             P = len(sel)
             lv = torch.arange(k0.shape[1], device=self.dev)[None, :] < n[:, None]
@@ -746,32 +676,17 @@ class DeviceGate:
             offs[1:] = torch.cumsum(n, 0)
             _, _, inl, _, _ = geometry.epipolar_ransac_device(k0[pi, si].contiguous(), k1[pi, si].contiguous(),
                                                               offs, self.K, 0, 3.0)
-            ratio = inl.double() / n.clamp(min=1).double()
-            ok = (n >= 5) & (inl >= self.min_inliers) & (ratio >= self.min_inlier_ratio)
-            n_valid_t += ok.sum()
             ta = torch.from_numpy(ca).to(self.dev)
             tb = torch.from_numpy(cb).to(self.dev)
-            gate_rej_t += (ok & ((self.f_num[ta] - self.f_num[tb]).abs() > self.limit)).sum()
+            ok = decide_pairs(n, inl, ta, tb, self.f_num, self.limit, self.min_inliers, self.min_inlier_ratio,
+                              n_valid_t, gate_rej_t)
             if rec is not None:
                 rec.append((sel, n, inl, ok))
-        n_valid, gate_rej = int(n_valid_t), int(gate_rej_t)  # (a device sync)
         if self.time_verify:
+            torch.cuda.synchronize(self.dev)
             self.last_verify_s = time.perf_counter() - t_start  # this rank's LoFTR verification wall time
-        if rec is not None:
-            r = {"a": pa, "b": pb, "matches": np.zeros(len(pa), np.int32), "inliers": np.zeros(len(pa), np.int32),
-                 "is_valid": np.zeros(len(pa), bool)}
-            for sel, n, inl, ok in rec:
-                r["matches"][sel] = n.cpu().numpy()
-                r["inliers"][sel] = inl.cpu().numpy()
-                r["is_valid"][sel] = ok.cpu().numpy()
-            self.last_pair_results = r
-        out["pairs_verified"] = len(pa)
         out["pairs_matched_loftr"] = len(pa)
-        out["verified_valid"] = n_valid
-        out["verifier_invalid"] = len(pa) - n_valid
-        out["gate_rejected_cross_floor"] = gate_rej
-        out["accepted"] = n_valid - gate_rej
-        return out
+        return self._finish(out, pa, pb, n_valid_t, gate_rej_t, rec)
 
     def _first_pairs(self, pa_t, pb_t, limit):
         """The first `limit` pairs of the global (rank-ordered) pair list, as this rank's part."""

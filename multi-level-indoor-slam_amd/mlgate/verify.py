@@ -375,17 +375,21 @@ class GeometricVerifier:
             raise ValueError(f"Unknown matcher: {matcher_type}")
         self.matcher = cls(device=device)
 
-    def decide(self, kpts1, kpts2, inlier_mask, E, inlier_ratio, K=None, query_idx=0, match_idx=0) -> MatchResult:
-        """The decision rule given matches and a RANSAC result (geometric_verification.py:606-634)."""
+    def _result(self, kpts1, kpts2, inlier_mask, E, inlier_ratio, K, query_idx, match_idx, pose_fn) -> MatchResult:
+        """The MatchResult of a RANSAC result under the decision rule (geometric_verification.py:
+        606-634); pose_fn() gives the relative pose where the reference computes one."""
         n_in = int(np.sum(inlier_mask)) if len(inlier_mask) > 0 else 0
-        pose = None
-        if K is not None and E is not None and n_in >= 5:
-            pose = self.matcher.estimate_relative_pose(kpts1, kpts2, K, inlier_mask, E)
+        pose = pose_fn() if (K is not None and E is not None and n_in >= 5) else None
         return MatchResult(query_idx=query_idx, match_idx=match_idx, num_keypoints_query=len(kpts1),
                            num_keypoints_match=len(kpts2), num_matches=len(kpts1), num_inliers=n_in,
                            inlier_ratio=inlier_ratio, relative_pose=pose, essential_matrix=E,
                            confidence=min(1.0, inlier_ratio * (n_in / self.min_inliers)),
                            is_valid=n_in >= self.min_inliers and inlier_ratio >= self.min_inlier_ratio)
+
+    def decide(self, kpts1, kpts2, inlier_mask, E, inlier_ratio, K=None, query_idx=0, match_idx=0) -> MatchResult:
+        """The decision rule given matches and a RANSAC result (geometric_verification.py:606-634)."""
+        return self._result(kpts1, kpts2, inlier_mask, E, inlier_ratio, K, query_idx, match_idx,
+                            lambda: self.matcher.estimate_relative_pose(kpts1, kpts2, K, inlier_mask, E))
 
     def verify(self, image1: np.ndarray, image2: np.ndarray, K: Optional[np.ndarray] = None, query_idx: int = 0,
                match_idx: int = 0) -> MatchResult:
@@ -415,12 +419,7 @@ class GeometricVerifier:
                 mask, E, ratio = np.array([]), None, 0.0
             else:
                 mask, E, ratio = r.mask, r.model, float(np.sum(r.mask) / len(k1))
-            n_in = int(np.sum(mask)) if len(mask) > 0 else 0
-            pose = r.pose if (K is not None and E is not None and n_in >= 5) else None
-            out.append(MatchResult(query_idx=q, match_idx=m, num_keypoints_query=len(k1), num_keypoints_match=len(k2),
-                                   num_matches=len(k1), num_inliers=n_in, inlier_ratio=ratio, relative_pose=pose,
-                                   essential_matrix=E, confidence=min(1.0, ratio * (n_in / self.min_inliers)),
-                                   is_valid=n_in >= self.min_inliers and ratio >= self.min_inlier_ratio))
+            out.append(self._result(k1, k2, mask, E, ratio, K, q, m, lambda: r.pose))
         return out
 
     def verify_batch(self, image_pairs: List[Tuple[np.ndarray, np.ndarray]], K: Optional[np.ndarray] = None,

@@ -145,7 +145,7 @@ def test_device_gate_counts_equal_full_gate(dev, chain, reports, cfg):
 
 
 @pytest.mark.parametrize("cfg", list(CFG))
-def test_device_gate_unordered_matching_changes_nothing(dev, chain, cfg, monkeypatch):
+def test_device_gate_unordered_matching_changes_nothing(dev, chain, cfg):
     """LightGlue once per unordered pair (the default) vs once per ordered pair: the same
     counts and, PER ORDERED PAIR, the same match count, inlier count and decision in every
     configuration (LightGlue(b, a) is exactly swap(LightGlue(a, b)):
@@ -154,10 +154,10 @@ def test_device_gate_unordered_matching_changes_nothing(dev, chain, cfg, monkeyp
     rg, vg = CFG[cfg]
     outs, recs = {}, {}
     for dd in ("1", "0"):
-        monkeypatch.setenv("MLGATE_LG_DEDUP", dd)
         g = DeviceGate(frames, chain["seq"].t, chain["labels"], device=str(dev), k=chain["k"],
                        similarity_threshold=chain["thr"], min_time_gap=chain["gap"], retrieval_floor_gating=rg,
-                       verifier_floor_gating=vg, K=ogeo.ISEC_K, vit_batch=64, lg_chunk=64, record=True)
+                       verifier_floor_gating=vg, K=ogeo.ISEC_K, vit_batch=64, lg_chunk=64, record=True,
+                       lg_dedup=dd == "1")
         outs[dd] = g.step()
         r = g.last_pair_results
         recs[dd] = {(int(x), int(y)): (int(n), int(i), bool(v))
@@ -169,26 +169,31 @@ def test_device_gate_unordered_matching_changes_nothing(dev, chain, cfg, monkeyp
     assert len(recs["1"]) == a["pairs_verified"] > 0
 
 
-def test_superpoint_overlap_changes_nothing(dev, chain, monkeypatch):
-    """SuperPoint of the keyframes past the first LightGlue chunk on a side stream under
-    that chunk (MLGATE_SP_OVERLAP=1) vs every keyframe first (the default): the same counts
-    and, per ordered pair, the same match count, inlier count and decision; several
-    chunks, so the side-stream rows feed later chunks, and two steps, so a step starts
-    from the previous step's tables."""
+def test_stream_overlap_changes_nothing(dev, chain):
+    """The overlapped schedule (the default: the step on a high-priority stream, SuperPoint
+    on a side stream under the ViT and the kNN, each chunk's RANSAC on a side stream under
+    the next chunk's LightGlue) vs overlap=False (everything on the caller's stream, in
+    program order): the same counts and, per ordered pair, the same match count, inlier
+    count and decision; several chunks and SuperPoint batches, so both side streams hand
+    work over repeatedly, and two steps, so a step starts from the previous step's tables.
+    A third gate with chunks of 64 and one SuperPoint batch: per-pair results do not depend
+    on the chunking or on which frames share a batch."""
     frames = torch.from_numpy(chain["frames"]).to(dev)
     outs, recs = {}, {}
-    for ov in ("1", "0"):
-        monkeypatch.setenv("MLGATE_SP_OVERLAP", ov)
+    for name, kw in (("1", dict(overlap=True, lg_chunk=16, sp_batch=8)),
+                     ("0", dict(overlap=False, lg_chunk=16, sp_batch=8)),
+                     ("whole", dict(overlap=True, lg_chunk=64, sp_batch=64))):
         g = DeviceGate(frames, chain["seq"].t, chain["labels"], device=str(dev), k=chain["k"],
                        similarity_threshold=chain["thr"], min_time_gap=chain["gap"], K=ogeo.ISEC_K,
-                       vit_batch=64, lg_chunk=16, sp_batch=8, record=True)
+                       vit_batch=64, record=True, **kw)
         for _ in range(2):
-            outs[ov] = g.step()
+            outs[name] = g.step()
             r = g.last_pair_results
-            recs[ov] = {(int(x), int(y)): (int(n), int(i), bool(v))
-                        for x, y, n, i, v in zip(r["a"], r["b"], r["matches"], r["inliers"], r["is_valid"])}
+            recs[name] = {(int(x), int(y)): (int(n), int(i), bool(v))
+                          for x, y, n, i, v in zip(r["a"], r["b"], r["matches"], r["inliers"], r["is_valid"])}
     assert outs["1"] == outs["0"]
     assert recs["1"] == recs["0"] and len(recs["1"]) > 0
+    assert recs["whole"] == recs["1"]
 
 
 def test_orient_matches_is_the_swapped_call(dev):

@@ -107,7 +107,7 @@ def main():
         t_sp = timed(sp, a.reps)
         spa, spb, nu = rank_slice(pa, pb, W, r)
         out = {}
-        t_ver = timed(lambda: gate._verify_lightglue(spa, spb, True, out), a.reps)
+        t_ver = timed(lambda: gate._verify_lightglue(spa, spb, out), a.reps)
         need = np.unique(np.concatenate([spa, spb]))
         remote = int(((need < lo) | (need >= hi)).sum())
         x_bytes = (W - 1) / W * N * 768 * 4 + remote * FEATURE_BYTES
