@@ -399,6 +399,54 @@ int mlg_rerank_gate(const float* feats, int F, int L, int D, int q0, int Q, int 
                     int32_t* r_idx, float* r_sim, float* r_cross, double* r_score, int32_t* r_count,
                     unsigned long long* dropped_total_or_null, void* stream);
 
+/* Sequence-consistency check of mlg_knn_gate's candidates (SeqSLAM's idea; the reference
+ * names "temporal consistency" among the gate's extensions, loop_closure_gate.py:36-39): a
+ * true revisit is similar over a run of consecutive keyframes, in the same or the opposite
+ * travel direction; an aliased view is similar for one frame only.  On the device,
+ * asynchronous on `stream`, no host synchronisation.  THE RULE (stated here once):
+ *
+ * Inputs: the raw descriptors desc f32 [N, D]; t f64 [N]; floor codes int64 [N] and
+ * has_floor uint8 [N] as vpr.floor_codes makes them; mlg_knn_gate's idx / sim [Q, k] and
+ * count [Q] (clamped to [0, k]), query row r being frame i = q0 + r; mask_or_null uint8
+ * [Q, k], a zero byte marking an entry that is not a candidate (NULL: every emitted entry).
+ * Parameters: radius w in [1, 7]; min_gap, the retrieval's; min_terms >= 1; threshold.
+ *
+ * Xn = the rows normalised as mlg_row_normalize_f32 does it; S(a, b) = the float32 value
+ * mlg_similarity yields for rows a, b of Xn (the exact-f32 MFMA in sim_tile's k order).
+ * For a candidate entry (i, j = idx[r][s]) and a direction dir in {+1, -1}, an off-centre
+ * term d in [-w, w], d != 0, is VALID when all of these hold:
+ *   0 <= i + d < N and 0 <= j + dir d < N;
+ *   !(|t[i + d] - t[j + dir d]| < min_gap)  (the retrieval's own mask, place_recognition.py:
+ *   878-882: temporal neighbours never vouch for each other);
+ *   frame i + d is not labelled onto a different floor from i:
+ *   !has[i + d] || !has[i] || code[i + d] == code[i], and the same for j + dir d against j
+ *   (a window does not reach across an elevator ride).
+ * n_dir = the number of valid terms;
+ * score_dir = (float64(sim[r][s]) + SUM float64(S(i + d, j + dir d))) / (1 + n_dir), the sum
+ * over the valid d ascending in float64, one division; the centre term is the sim the caller
+ * passed, not recomputed.  A direction with n_dir < min_terms is not eligible.
+ *   Neither direction eligible (the start of a map, a lone labelled frame): the entry is
+ *   kept unjudged: score = float64(sim), dir = 0, terms = 0, keep = 1.
+ *   Otherwise the eligible direction with the larger score, +1 on a tie: terms = n_dir,
+ *   keep = score >= threshold.
+ *   Entries that are not candidates (past count, masked out, or j outside [0, N), which is
+ *   never read): score = 0, dir = 0, terms = 0, keep = 0.
+ * Outputs, all [Q, k] in emission order, nothing compacted: s_score f64, s_dir int8,
+ * s_terms int32, keep uint8; rejected_total_or_null: a device uint64 that the number of
+ * judged-and-rejected candidates is added to (an integer atomic per row).
+ * Refused before any HIP call: MLG_EINVAL for a null required pointer, a non-positive size,
+ * k outside [1, 64], radius outside [1, 7], min_terms < 1, q0 < 0 or q0 + Q > N;
+ * MLG_ENOMEM for a workspace below mlg_seq_workspace_bytes (0 for a bad shape).
+ * The workspace layout, every buffer rounded up to 256 bytes:
+ *   normalised descriptors f32 [N, D]
+ * and nothing else: the per-slot diagonals stay in LDS (tests/test_seq_cpu.py restates it). */
+extern size_t mlg_seq_workspace_bytes(int N, int D, int Q, int k);
+int mlg_seq_gate(const float* desc, int N, int D, const double* t, const int64_t* floor, const uint8_t* has_floor,
+                 int q0, int Q, int k, const int32_t* idx, const float* sim, const uint8_t* mask_or_null,
+                 const int32_t* count, int radius, double min_gap, int min_terms, double threshold, void* workspace,
+                 size_t workspace_bytes, double* s_score, int8_t* s_dir, int32_t* s_terms, uint8_t* keep,
+                 unsigned long long* rejected_total_or_null, void* stream);
+
 /* ----------------------------------------------------------- op-level access --
  * Individual kernels of the ViT path (parity tests against a float32 reference). */
 int mlg_op_gemm_f32out(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, void* stream);

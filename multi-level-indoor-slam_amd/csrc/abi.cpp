@@ -735,6 +735,18 @@ int mlg_rerank_gate(const float* feats, int F, int L, int D, int q0, int Q, int 
                           (hipStream_t)stream);
 }
 
+size_t mlg_seq_workspace_bytes(int N, int D, int Q, int k) { return mlg_seq_ws_bytes(N, D, Q, k); }
+
+int mlg_seq_gate(const float* desc, int N, int D, const double* t, const int64_t* floor, const uint8_t* has_floor,
+                 int q0, int Q, int k, const int32_t* idx, const float* sim, const uint8_t* mask_or_null,
+                 const int32_t* count, int radius, double min_gap, int min_terms, double threshold, void* workspace,
+                 size_t workspace_bytes, double* s_score, int8_t* s_dir, int32_t* s_terms, uint8_t* keep,
+                 unsigned long long* rejected_total_or_null, void* stream) {
+    return mlg_seq_run(desc, N, D, t, floor, has_floor, q0, Q, k, idx, sim, mask_or_null, count, radius, min_gap,
+                       min_terms, threshold, workspace, workspace_bytes, s_score, s_dir, s_terms, keep,
+                       rejected_total_or_null, (hipStream_t)stream);
+}
+
 int mlg_op_gemm_f32out(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, void* stream) {
     return mlg_gemm_f32out(A, W, C, M, N, K, (hipStream_t)stream);
 }

@@ -151,6 +151,14 @@ int mlg_rerank_run(const float* feats, int F, int L, int D, int q0, int Q, int k
                    void* ws, size_t ws_bytes, int32_t* r_idx, float* r_sim, float* r_cross, double* r_score,
                    int32_t* r_count, unsigned long long* dropped, hipStream_t s);
 
+// seq.hip -- sequence-consistency check of mlg_knn_gate's candidates (the rule: include/mlgate.h)
+size_t mlg_seq_ws_bytes(int N, int D, int Q, int k);
+int mlg_seq_run(const float* desc, int N, int D, const double* t, const int64_t* floor, const uint8_t* has_floor,
+                int q0, int Q, int k, const int32_t* idx, const float* sim, const uint8_t* mask, const int32_t* count,
+                int radius, double min_gap, int min_terms, double threshold, void* ws, size_t ws_bytes,
+                double* s_score, int8_t* s_dir, int32_t* s_terms, uint8_t* keep, unsigned long long* rejected,
+                hipStream_t s);
+
 // proximity.hip -- trajectory-proximity candidates + floor gate
 bool mlg_proximity_shape_ok(int N, int row0, int nrows);
 size_t mlg_proximity_ws_bytes(int N, int nrows);

@@ -532,6 +532,60 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rerank_gate(const Tensor& fea
     return {r_idx, r_sim, r_cross, r_score, r_count};
 }
 
+// The sequence-consistency check over knn_gate's lists (mlg_seq_gate states the rule): desc f32 [N, D],
+// t f64 [N], floor int64 [N], has_floor uint8 [N]; idx / sim / mask [Q, k], count [Q]; totals int64 [1] or
+// none -> s_score f64, s_dir int8, s_terms int32, keep uint8, all [Q, k]
+std::tuple<Tensor, Tensor, Tensor, Tensor> seq_gate(const Tensor& desc, const Tensor& t, const Tensor& floor,
+                                                    const Tensor& has_floor, const Tensor& idx, const Tensor& sim,
+                                                    const c10::optional<Tensor>& mask, const Tensor& count,
+                                                    int64_t radius, double threshold, double min_gap,
+                                                    int64_t min_terms, int64_t q0,
+                                                    const c10::optional<Tensor>& totals) {
+    want(desc, at::kFloat, "desc");
+    want(t, at::kDouble, "t");
+    want(floor, at::kLong, "floor");
+    want(has_floor, at::kByte, "has_floor");
+    want(idx, at::kInt, "idx");
+    want(sim, at::kFloat, "sim");
+    want(count, at::kInt, "count");
+    TORCH_CHECK(desc.dim() == 2, "desc [N, D]");
+    const int64_t N = desc.size(0), D = desc.size(1);
+    TORCH_CHECK(t.numel() == N && floor.numel() == N && has_floor.numel() == N, "t / floor / has_floor [N]");
+    TORCH_CHECK(idx.dim() == 2 && sim.sizes() == idx.sizes() && count.numel() == idx.size(0),
+                "idx / sim [Q, k], count [Q]");
+    const int64_t Q = idx.size(0), k = idx.size(1);
+    TORCH_CHECK(k >= 1 && k <= 64, "seq_gate: k must be in [1, 64]");
+    TORCH_CHECK(radius >= 1 && radius <= 7, "seq_gate: radius must be in [1, 7]");
+    TORCH_CHECK(min_terms >= 1, "seq_gate: min_terms must be >= 1");
+    TORCH_CHECK(q0 >= 0 && q0 + Q <= N, "query rows out of range");
+    const bool has_mask = mask.has_value() && mask->defined();
+    const bool has_totals = totals.has_value() && totals->defined();
+    if (has_mask) {
+        want(*mask, at::kByte, "mask");
+        TORCH_CHECK(mask->sizes() == idx.sizes(), "mask must be uint8 [Q, k]");
+    }
+    if (has_totals) {
+        want(*totals, at::kLong, "totals");
+        TORCH_CHECK(totals->numel() == 1, "totals must be int64 [1]");
+    }
+    c10::DeviceGuard g(desc.device());
+    auto o = desc.options();
+    Tensor s_score = at::empty({Q, k}, o.dtype(at::kDouble)), s_dir = at::empty({Q, k}, o.dtype(at::kChar));
+    Tensor s_terms = at::empty({Q, k}, o.dtype(at::kInt)), keep = at::empty({Q, k}, o.dtype(at::kByte));
+    if (Q == 0) return {s_score, s_dir, s_terms, keep};
+    const size_t nbytes = mlg_seq_workspace_bytes((int)N, (int)D, (int)Q, (int)k);
+    TORCH_CHECK(nbytes > 0, "seq_gate: unsupported shape N=", N, " D=", D, " Q=", Q, " k=", k);
+    Tensor ws = workspace(nbytes, desc);
+    check_rc(mlg_seq_gate(cp<float>(desc), (int)N, (int)D, cp<double>(t), cp<int64_t>(floor), cp<uint8_t>(has_floor),
+                          (int)q0, (int)Q, (int)k, cp<int32_t>(idx), cp<float>(sim),
+                          has_mask ? cp<uint8_t>(*mask) : nullptr, cp<int32_t>(count), (int)radius, min_gap,
+                          (int)min_terms, threshold, ws.data_ptr(), (size_t)ws.numel(), mp<double>(s_score),
+                          mp<int8_t>(s_dir), mp<int32_t>(s_terms), mp<uint8_t>(keep),
+                          has_totals ? mp<unsigned long long>(*totals) : nullptr, stream_of(desc)),
+             "mlg_seq_gate");
+    return {s_score, s_dir, s_terms, keep};
+}
+
 // --------------------------------------------------------------- LightGlue
 std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const Tensor& desc, const Tensor& counts,
                                                      const Tensor& pair_a, const Tensor& pair_b, at::TensorList w,
@@ -1190,6 +1244,9 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("xcorr_batch(Tensor feats, Tensor query, Tensor cand) -> Tensor");
     m.def("rerank_gate(Tensor feats, Tensor idx, Tensor sim, Tensor? mask, Tensor count, int top_k, int q0, "
           "Tensor? cached, Tensor(a!)? totals) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("seq_gate(Tensor desc, Tensor t, Tensor floor, Tensor has_floor, Tensor idx, Tensor sim, Tensor? mask, "
+          "Tensor count, int radius, float threshold, float min_gap, int min_terms, int q0, Tensor(a!)? totals) "
+          "-> (Tensor, Tensor, Tensor, Tensor)");
     m.def("superpoint(Tensor frames, Tensor[] weights, float detection_threshold, int max_keypoints, "
           "int nms_radius, int remove_borders, bool with_bf16) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("lightglue(Tensor kpts, Tensor desc, Tensor counts, Tensor pair_a, Tensor pair_b, Tensor[] weights, "
@@ -1252,6 +1309,7 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("xcorr_score", &xcorr_score);
     m.impl("xcorr_batch", &xcorr_batch);
     m.impl("rerank_gate", &rerank_gate);
+    m.impl("seq_gate", &seq_gate);
     m.impl("superpoint", &superpoint);
     m.impl("lightglue", &lightglue);
     m.impl("ransac_epipolar", &ransac_epipolar);

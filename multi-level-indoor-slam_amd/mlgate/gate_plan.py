@@ -28,6 +28,13 @@ def pairs_from_rerank(r_idx, r_count, lo):
     return _row_major(r_idx, np.arange(r_idx.shape[1])[None, :] < r_count[:, None], lo)
 
 
+def pairs_from_sequence(h_idx, h_keep, lo):
+    """The retrieval lists after the sequence-consistency check (idx / keep [Q, k]; keep is 0
+    for every entry that was no candidate) -> (pa, pb): the kept entries, row-major by query
+    in emission order."""
+    return _row_major(h_idx, h_keep != 0, lo)
+
+
 def same_floor(pa, pb, h_codes, h_has):
     """The pairs verify_with_semantics does NOT skip: it skips when floor1 != floor2 in
     Python (geometric_verification.py:709-710) -- None == None only, NaN != NaN (equality

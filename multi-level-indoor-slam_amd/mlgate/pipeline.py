@@ -8,6 +8,9 @@ the reference's public APIs, and this module is that harness:
   2. descriptors   SemanticPlaceRecognition('cricavpr').add_image per keyframe
                    (place_recognition.py:843-849; here one batched add_images);
   3. retrieval     find_loop_closures(enable_floor_gating, k) (:851-911);
+  3a. sequence     (opt-in, seq_radius) the sequence-consistency check of each valid match
+                   over the keyframes around it (mlg_seq_gate, include/mlgate.h), before 3b:
+                   the matches it rejects reach neither the re-ranking nor the verifier;
   3b. re-ranking   (opt-in, rerank_top_k) CricaVPR.rerank_candidates (:714-757) over each
                    query's valid matches: the first rerank_top_k go on to the verifier;
   4. verification  SemanticGeometricVerifier.verify_with_semantics on every retrieved
@@ -77,6 +80,8 @@ class GateReport:
     rejections: RejectionCount = field(default_factory=RejectionCount)
     # rerank_top_k: the matches the re-ranking stage did not keep (not a rejection term)
     reranked_out: List[PlaceMatch] = field(default_factory=list)
+    # seq_radius: the matches the sequence-consistency check rejected (not a rejection term)
+    sequence_rejected: List[PlaceMatch] = field(default_factory=list)
 
 
 def floor_labels_from_imu(timestamps, imu, start_floor=5, detector_kwargs=None):
@@ -96,8 +101,12 @@ class FullSemanticGate:
                  min_inlier_ratio: float = 0.25, strict_mode: bool = True, retrieval_floor_gating: bool = True,
                  verifier_floor_gating: bool = True, verify_rejected: bool = False, start_floor: int = 5,
                  imu_detector_kwargs: Optional[Dict] = None, backbone: str = 'dinov2_vitb14',
-                 rerank_top_k: Optional[int] = None):
+                 rerank_top_k: Optional[int] = None, seq_radius: Optional[int] = None, seq_threshold: float = 0.3,
+                 seq_min_terms: int = 2):
         self.vpr_method, self.matcher_type, self.device = vpr_method, matcher_type, device
+        # seq_radius: the sequence-consistency check between retrieval and re-ranking, as
+        # DeviceGate(seq_radius=...) runs it; None: no such stage
+        self.seq_radius, self.seq_threshold, self.seq_min_terms = _seq_args(seq_radius, seq_threshold, seq_min_terms, k)
         # rerank_top_k: CricaVPR.rerank_candidates (place_recognition.py:714-757) between
         # retrieval and verification, as DeviceGate(rerank_top_k=...) runs it; None: no such stage
         if rerank_top_k is not None:
@@ -150,7 +159,9 @@ class FullSemanticGate:
         self.spr.add_images(frames, timestamps.tolist(), labels)
         matches = self.spr.find_loop_closures(enable_floor_gating=self.retrieval_floor_gating, k=self.k)
         to_verify = [m for m in matches if m.is_valid or self.verify_rejected]
-        reranked_out = []
+        sequence_rejected, reranked_out = [], []
+        if self.seq_radius is not None:
+            to_verify, sequence_rejected = self._sequence(to_verify, len(timestamps))
         if self.rerank_top_k is not None:
             to_verify, reranked_out = self._rerank(to_verify, len(timestamps))
         self.verifier = SemanticGeometricVerifier(self.matcher_type, self.device, self.min_inliers,
@@ -170,15 +181,13 @@ class FullSemanticGate:
         return GateReport(floor_labels=floor_labels, events=events, matches=matches, verified=to_verify,
                           results=results, accepted=accepted, rejected=rejected,
                           retrieval_stats=self.spr.get_statistics(matches), verifier_stats=vstats,
-                          gate_stats=gstats, rejections=counts, reranked_out=reranked_out)
+                          gate_stats=gstats, rejections=counts, reranked_out=reranked_out,
+                          sequence_rejected=sequence_rejected)
 
-    def _rerank(self, to_verify, n):
-        """(kept, dropped) of the matches bound for the verifier: each query's matches, in
-        emission order, through mlg_rerank_gate over the cached local features; the kept ones
-        row-major by query and in re-ranked order within a row, similarities unchanged."""
-        import torch
-        from . import retrieval
-        vpr = self.spr.vpr
+    @staticmethod
+    def _rows(to_verify, n):
+        """The matches bound for the verifier as knn_gate-shaped host lists: (rows, idx, sim,
+        count), each query's matches in emission order."""
         rows = {}
         for m in to_verify:
             rows.setdefault(m.query_idx, []).append(m)
@@ -189,6 +198,41 @@ class FullSemanticGate:
             idx[q, :len(r)] = [m.match_idx for m in r]
             sim[q, :len(r)] = [m.similarity for m in r]
             count[q] = len(r)
+        return rows, idx, sim, count
+
+    def _sequence(self, to_verify, n):
+        """(kept, rejected) of the matches bound for the verifier, through mlg_seq_gate over
+        the descriptors, timestamps and floor codes find_loop_closures used; order unchanged."""
+        import torch
+        from . import retrieval
+        from .vpr import floor_codes
+        if not to_verify:
+            return [], []
+        rows, idx, sim, count = self._rows(to_verify, n)
+        descs = self.spr.vpr.descriptors
+        X, dev = self.spr.vpr._device_matrix()
+        codes, has = floor_codes([d.floor_label for d in descs])
+        keep = retrieval.sequence_gate(
+            X, torch.tensor([float(d.timestamp) for d in descs], dtype=torch.float64, device=dev),
+            torch.from_numpy(codes).to(dev), torch.from_numpy(has).to(dev), torch.from_numpy(idx).to(dev),
+            torch.from_numpy(sim).to(dev), None, torch.from_numpy(count).to(dev), self.seq_radius,
+            self.seq_threshold, self.min_time_gap, self.seq_min_terms)[3].cpu().numpy()
+        kept, rejected = [], []
+        seen = {}
+        for m in to_verify:  # a query's matches are in its row in the order they appear here
+            s = seen[m.query_idx] = seen.get(m.query_idx, -1) + 1
+            (kept if keep[m.query_idx, s] else rejected).append(m)
+        return kept, rejected
+
+    def _rerank(self, to_verify, n):
+        """(kept, dropped) of the matches bound for the verifier: each query's matches, in
+        emission order, through mlg_rerank_gate over the cached local features; the kept ones
+        row-major by query and in re-ranked order within a row, similarities unchanged."""
+        import torch
+        from . import retrieval
+        vpr = self.spr.vpr
+        rows, idx, sim, count = self._rows(to_verify, n)
+        k = idx.shape[1]
         cache = vpr._feature_cache if vpr.use_reranking else {}
         cached = np.array([f in cache for f in range(n)], np.uint8)
         some = next(iter(cache.values())) if cache else None
@@ -210,6 +254,20 @@ class FullSemanticGate:
             kept += [by_idx[int(j)] for j in r_idx[q, :r_count[q]]]
         keep_ids = {id(m) for m in kept}
         return kept, [m for m in to_verify if id(m) not in keep_ids]
+
+
+def _seq_args(seq_radius, seq_threshold, seq_min_terms, k):
+    """(radius or None, threshold, min_terms) of both gates' seq_* arguments, refused before
+    anything is built: the kernel takes a radius in [1, 7] and a lane per slot (k <= 64)."""
+    if seq_radius is None:
+        return None, float(seq_threshold), int(seq_min_terms)
+    if not 1 <= int(seq_radius) <= 7:
+        raise ValueError(f"seq_radius must be in [1, 7] (got {seq_radius})")
+    if int(seq_min_terms) < 1:
+        raise ValueError(f"seq_min_terms must be >= 1 (got {seq_min_terms})")
+    if int(k) > 64:
+        raise ValueError(f"seq_radius takes k <= 64 (got k = {k})")
+    return int(seq_radius), float(seq_threshold), int(seq_min_terms)
 
 
 def decide_pairs(n, inl, ta, tb, f_num, limit, min_inliers, min_inlier_ratio, n_valid_t, gate_rej_t):
@@ -246,7 +304,15 @@ class DeviceGate:
                  verifier_floor_gating=True, verify=True, K=None, min_inliers=20, min_inlier_ratio=0.25,
                  vit_batch=123, sp_batch=64, lg_chunk=1024, max_keypoints=2048, vit_state_dict=None, record=False,
                  vit_precise=True, matcher='lightglue', loftr_chunk=256, max_pairs=None, lg_tail=0,
-                 local_features=True, backbone='dinov2_vitb14', rerank_top_k=None, overlap=True, lg_dedup=True):
+                 local_features=True, backbone='dinov2_vitb14', rerank_top_k=None, overlap=True, lg_dedup=True,
+                 seq_radius=None, seq_threshold=0.3, seq_min_terms=2):
+        # seq_radius: the sequence-consistency check (mlg_seq_gate, include/mlgate.h) of the
+        # valid entries of each query row, after retrieval and before re-ranking: a match whose
+        # neighbouring keyframes do not match in either travel direction goes no further.
+        # None: the stage does not exist.  With several ranks nothing new is exchanged: every
+        # rank holds the gathered [N, D] descriptors and judges its own rows.
+        self.seq_radius, self.seq_threshold, self.seq_min_terms = _seq_args(seq_radius, seq_threshold, seq_min_terms, k)
+        self.last_sequence = None
         if rerank_top_k is not None:  # refused before anything is built
             if not local_features:
                 raise ValueError("rerank_top_k needs the local features: local_features=True")
@@ -361,6 +427,7 @@ class DeviceGate:
         self.last_verify_s = None
         self.last_pair_results = None
         self.last_retrieval = None
+        self.last_pairs = None
 
     def step(self):
         """Gate the sequence once.  Returns this rank's counts (dict of ints): matches,
@@ -403,21 +470,35 @@ class DeviceGate:
                                                     Q=self.n_local, totals=self.totals)
         # the retrieval lists come to the host once (Q x k entries): the pair list that
         # drives the verifier's chunks is built there, with no further device syncs
-        rr = ()
+        rr = sq = ()
+        cand = valid  # the entries that go on: the valid ones, then those the sequence check keeps
+        if self.seq_radius is not None:
+            sq = retrieval.sequence_gate(self.gather.out, self.t_all, self.f_all, self.hf_all, idx, sim, valid, count,
+                                         self.seq_radius, self.seq_threshold, self.gap, self.seq_min_terms, q0=self.lo)
+            cand = sq[3]
         if self.rerank_top_k is not None:
             bank = self.local_feats
             if self.world > 1:  # every rank's keyframes' local features, in keyframe order
                 bank = self.feat_gather(self.local_feats.view(self.n_local, -1)).view(
                     self.N, self.local_feats.shape[1], self.local_feats.shape[2])
-            rr = retrieval.rerank_gate(bank, idx, sim, valid, count, min(self.rerank_top_k, idx.shape[1]),
+            rr = retrieval.rerank_gate(bank, idx, sim, cand, count, min(self.rerank_top_k, idx.shape[1]),
                                        q0=self.lo)
-        h_idx, h_valid, h_count, *h_rr = (x.cpu().numpy() for x in (idx, valid, count) + tuple(rr))
+        h_idx, h_valid, h_count, *h_more = (x.cpu().numpy() for x in (idx, valid, count) + tuple(sq) + tuple(rr))
+        h_sq, h_rr = h_more[:len(sq)], h_more[len(sq):]
         if self.record:  # this rank's query rows: idx / sim / valid [Q, k], count [Q] (host)
             self.last_retrieval = (h_idx, sim.cpu().numpy(), h_valid, h_count)
         matches, floor_rej, pa_h, pb_h = gate_plan.pairs_from_retrieval(h_idx, h_valid, h_count, self.lo)
         out = {"matches": matches, "retrieval_floor_rejected": floor_rej, "skipped_floor_mismatch": 0,
                "verifier_invalid": 0, "gate_rejected_cross_floor": 0, "pairs_verified": 0, "verified_valid": 0,
                "accepted": 0}
+        if h_sq:
+            # the sequence check on: the entries it kept, in emission order.  sequence_rejected
+            # is not a rejection term either
+            if self.record:  # s_score / s_dir / s_terms / keep [Q, k] (host)
+                self.last_sequence = tuple(h_sq)
+            out["sequence_candidates"] = len(pa_h)
+            pa_h, pb_h = gate_plan.pairs_from_sequence(h_idx, h_sq[3], self.lo)
+            out["sequence_rejected"] = out["sequence_candidates"] - len(pa_h)
         if h_rr:
             # re-ranking on: the kept entries instead, in re-ranked order within a row.
             # reranked_out is not a rejection term (RejectionCount keeps its four)
@@ -426,6 +507,8 @@ class DeviceGate:
             out["rerank_candidates"] = len(pa_h)
             pa_h, pb_h = gate_plan.pairs_from_rerank(h_rr[0], h_rr[4], self.lo)
             out["reranked_out"] = out["rerank_candidates"] - len(pa_h)
+        if self.record:  # the ordered pairs bound for the verifier, before its floor skip (host int32)
+            self.last_pairs = (pa_h, pb_h)
         if not self.verify:
             return out
         # SuperPoint once per keyframe (the reference re-extracts per pair), cached in HBM

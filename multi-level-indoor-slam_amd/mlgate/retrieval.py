@@ -76,6 +76,28 @@ def rerank_gate(feats, idx, sim, mask, count, top_k, q0=0, cached=None, totals=N
     return _native.ops().rerank_gate(feats, idx, sim, mask, count, int(top_k), int(q0), cached, totals)
 
 
+def sequence_gate(desc, t, floor, has_floor, idx, sim, mask, count, radius, threshold, min_gap, min_terms=2, q0=0,
+                  totals=None):
+    """The sequence-consistency check of knn_gate's candidates, on the device and asynchronous
+    on the current stream (mlg_seq_gate; include/mlgate.h states the rule).  desc f32 [N, D],
+    t f64 [N], floor i64 [N], has_floor u8 [N] as knn_gate takes them; idx / sim [Q, k],
+    count [Q] as it returned them, query row r being frame q0 + r; mask uint8 [Q, k] (or None:
+    every emitted entry): the entries that are candidates; min_gap: the retrieval's; totals
+    int64 [1] (or None) is added the number of judged-and-rejected candidates.
+
+    Returns device tensors s_score f64, s_dir int8, s_terms int32, keep uint8 -- all [Q, k] in
+    emission order, nothing compacted."""
+    k = idx.shape[1]
+    if not 1 <= k <= 64:
+        raise ValueError(f"sequence_gate takes k in [1, 64] (got {k})")
+    if not 1 <= int(radius) <= 7:
+        raise ValueError(f"radius must be in [1, 7] (got {radius})")
+    if int(min_terms) < 1:
+        raise ValueError(f"min_terms must be >= 1 (got {min_terms})")
+    return _native.ops().seq_gate(desc, t, floor, has_floor, idx, sim, mask, count, int(radius), float(threshold),
+                                  float(min_gap), int(min_terms), int(q0), totals)
+
+
 def xcorr_score(qf, mf):
     """CricaVPR.compute_cross_correlation_score on device float32 [n1, D] / [n2, D] -> device scalar."""
     return _native.ops().xcorr_score(qf.contiguous(), mf.contiguous())
