@@ -336,6 +336,54 @@ int mlg_knn_gate(const float* desc, int N, int D, const double* t, const int64_t
                  size_t workspace_bytes, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
                  unsigned long long* totals, void* stream);
 
+/* mlg_knn_gate as keyframes arrive: the lists of n_new keyframes from the lists of the first
+ * n_old and the new rows alone.  On the device, asynchronous on `stream`, no host
+ * synchronisation.  THE RULE (stated here once): after any sequence of calls that grows the
+ * state from 0 to n rows, idx / sim / valid / count of rows [0, n) hold, bit for bit, what
+ * mlg_knn_gate writes for q0 = 0, Q = N = n on the same descriptors and labels.
+ *
+ * State, all the caller's, on the device, sized to a capacity cap >= n_new:
+ *   xn f32 [cap, D]: rows [0, n_new) normalised as mlg_row_normalize_f32 does it (the bits
+ *   mlg_knn_gate normalises to); rows [0, n_old) unchanged since the call that added them;
+ *   t f64 [cap]; floor int64 [cap] and has_floor uint8 [cap] (both may be NULL when !gating);
+ *   idx int32 / sim f32 / valid uint8 [cap, k] and count int32 [cap] in mlg_knn_gate's
+ *   layout and emission order, rows [0, n_old) as the earlier calls left them.
+ * One call, 0 <= n_old < n_new:
+ *   rows [n_old, n_new) get fresh lists over all columns [0, n_new) -- the fused scan and
+ *   merge of mlg_knn_gate, reading xn;
+ *   rows [0, n_old) are scanned against the new columns [n_old, n_new) only, and a row's
+ *   survivors -- !(|t_j - t_i| < min_gap) in float64, !(sim < thr) in float32 -- are merged
+ *   into its stored list in the order (sim desc, index desc), so a new column whose
+ *   similarity equals a stored entry's goes before it; the first k stay.  The floor bit of
+ *   every kept entry is mlg_knn_gate's: 0 only when gating and both labels are present and
+ *   differ.  This is exact because a row's top-k over old and new columns is the top-k of
+ *   (its stored top-k, the new columns), and every similarity is the exact-f32 MFMA value in
+ *   sim_tile's k order wherever the row and column sit in a tile.
+ * Outputs for the old rows: inserted int32 [n_old], the new columns that entered (0: the
+ * row's list, count and the memory behind them are not written); evicted_idx int32
+ * [n_old, k] and n_evicted int32 [n_old], the match indices pushed off the end, in their
+ * former order (slots past n_evicted hold -1).  Memory past count in a row and past row
+ * n_new is never written.  n_old = 0 is the batch call; the three outputs may then be NULL.
+ * Refused before any HIP call: MLG_EINVAL for k outside [1, 32], D % 4 != 0, n_old < 0,
+ * n_old >= n_new, a null or misaligned required pointer (xn to 16 bytes), gating without
+ * labels; MLG_ENOMEM for a workspace below mlg_knn_append_workspace_bytes (0 for a shape the
+ * call refuses).  The workspace holds only the scans' partial lists, each buffer rounded up
+ * to 256 bytes. */
+extern size_t mlg_knn_append_workspace_bytes(int n_old, int n_new, int D, int k);
+int mlg_knn_append(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                   const uint8_t* has_floor, double min_gap, float thr, int k, int gating, void* workspace,
+                   size_t workspace_bytes, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
+                   int32_t* inserted, int32_t* evicted_idx, int32_t* n_evicted, void* stream);
+/* Measurement access: mlg_knn_append running only the phases named -- the list update of
+ * the old rows, the fresh lists of the new rows, or (both bits) the call above.  One phase
+ * alone leaves the state half updated: for timing on a copy of the state. */
+#define MLG_KNN_APPEND_UPDATE 1
+#define MLG_KNN_APPEND_FRESH 2
+int mlg_op_knn_append_phases(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                             const uint8_t* has_floor, double min_gap, float thr, int k, int gating, void* workspace,
+                             size_t workspace_bytes, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
+                             int32_t* inserted, int32_t* evicted_idx, int32_t* n_evicted, int phases, void* stream);
+
 /* BasePlaceRecognition.query (place_recognition.py:117-163) for Q query descriptors
  * against a database of N: cosine similarity, |t_db - t_query| < min_gap masked
  * (t_query NaN = no timestamp), top-k (no threshold).  Same workspace query. */

@@ -518,6 +518,39 @@ int mlg_knn_query(const float* db, int N, int D, const float* qdesc, int Q, cons
     return MLG_OK;
 }
 
+size_t mlg_knn_append_workspace_bytes(int n_old, int n_new, int D, int k) {
+    if (n_old < 0 || n_new <= n_old || !knn_fused(D, k)) return 0;
+    return mlg_knn_append_ws_bytes(n_old, n_new, k);
+}
+
+int mlg_knn_append(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                   const uint8_t* has_floor, double min_gap, float thr, int k, int gating, void* workspace,
+                   size_t workspace_bytes, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
+                   int32_t* inserted, int32_t* evicted_idx, int32_t* n_evicted, void* stream) {
+    return mlg_op_knn_append_phases(xn, n_old, n_new, D, t, floor, has_floor, min_gap, thr, k, gating, workspace,
+                                    workspace_bytes, idx, sim, valid, count, inserted, evicted_idx, n_evicted,
+                                    MLG_KNN_APPEND_UPDATE | MLG_KNN_APPEND_FRESH, stream);
+}
+
+int mlg_op_knn_append_phases(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                             const uint8_t* has_floor, double min_gap, float thr, int k, int gating, void* workspace,
+                             size_t workspace_bytes, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
+                             int32_t* inserted, int32_t* evicted_idx, int32_t* n_evicted, int phases, void* stream) {
+    if (phases < 1 || phases > (MLG_KNN_APPEND_UPDATE | MLG_KNN_APPEND_FRESH)) return MLG_EINVAL;
+    if (n_old < 0 || n_new <= n_old || D <= 0 || !knn_fused(D, k)) return MLG_EINVAL;
+    if (!xn || !t || !workspace || !idx || !sim || !valid || !count) return MLG_EINVAL;
+    if (n_old > 0 && (!inserted || !evicted_idx || !n_evicted)) return MLG_EINVAL;
+    if (gating && (!floor || !has_floor)) return MLG_EINVAL;
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (misaligned(xn, 16) || misaligned(t, 8) || misaligned(floor, 8) || misaligned(workspace, 16) ||
+        misaligned(idx, 4) || misaligned(sim, 4) || misaligned(count, 4) || misaligned(inserted, 4) ||
+        misaligned(evicted_idx, 4) || misaligned(n_evicted, 4))
+        return MLG_EINVAL;
+    return mlg_knn_append_run(xn, n_old, n_new, D, t, floor, has_floor, min_gap, thr, k, gating, workspace,
+                              workspace_bytes, idx, sim, valid, count, inserted, evicted_idx, n_evicted,
+                              (hipStream_t)stream, phases);
+}
+
 int mlg_row_normalize_f32(const float* X, float* Xn, int N, int D, float* norms_or_null, void* stream) {
     return mlg_row_normalize(X, Xn, N, D, norms_or_null, (hipStream_t)stream);
 }

@@ -143,6 +143,15 @@ int mlg_knn_fused(const float* Xq, int Q, const float* Xd, int N, int D, const d
                   const int64_t* fq, const uint8_t* hfq, const int64_t* fdb, const uint8_t* hfdb, double min_gap,
                   float thr, int k, int gating, void* ws, int32_t* idx, float* sim, uint8_t* valid, int32_t* count,
                   unsigned long long* totals, hipStream_t s);
+// streaming form of the fused kNN over persistent normalised rows (the rule: include/mlgate.h,
+// mlg_knn_append): fresh lists for rows [n_old, n_new), the window [n_old, n_new) merged into
+// the stored lists of rows [0, n_old)
+size_t mlg_knn_append_ws_bytes(int n_old, int n_new, int k);
+int mlg_knn_append_run(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                       const uint8_t* hf, double min_gap, float thr, int k, int gating, void* ws, size_t ws_bytes,
+                       int32_t* idx, float* sim, uint8_t* valid, int32_t* count, int32_t* inserted,
+                       int32_t* evicted_idx, int32_t* n_evicted, hipStream_t s,
+                       int phases = MLG_KNN_APPEND_UPDATE | MLG_KNN_APPEND_FRESH);
 
 // rerank.hip -- CricaVPR.rerank_candidates over mlg_knn_gate's lists: fused cross-correlation + selection
 size_t mlg_rerank_ws_bytes(int F, int L, int D, int Q, int k);

@@ -25,6 +25,13 @@
 //                    ballot + shuffle, so after the first tile almost every value is
 //                    rejected by one compare.  Writes each row's sorted partial list.
 //   k_knn_merge      per row: merges the column splits' lists, floor bit, totals.
+// Streaming (mlg_knn_append): the lists of n_new keyframes from those of the first n_old.
+//   k_knn_scan<true> the old rows against the window of new columns only: the scan above with
+//                    the grid dealt by row block (the window is small, the old rows are the
+//                    traffic).
+//   k_knn_update     per old row: merges the window's lists into the stored list in place
+//                    (a new column of equal similarity first), writes what entered and what
+//                    was evicted; the new rows then run the batch scan and merge.
 #include <algorithm>
 
 #include "common.h"
@@ -518,6 +525,10 @@ constexpr int FC = 128;   // database columns per tile
 constexpr int FKMAX = 32;  // fused path: k <= 32 (a list rank per lane)
 
 // Row lists in registers: lane l holds rank l of each of the wave's 16 rows.
+// ROWDEAL (mlg_knn_append_run's list update, a window of few columns): the grid walks the row
+// blocks first, so consecutive row blocks land on consecutive XCDs and each XCD reads only its
+// own share of the query rows; the column window it scans is small enough for every L2.
+template <bool ROWDEAL>
 __global__ __launch_bounds__(256, 2) void k_knn_scan(const float* __restrict__ Xq, int Q, const float* __restrict__ Xd,
                                                      int N, int D, const double* __restrict__ tq,
                                                      const double* __restrict__ tdb, double min_gap, float thr, int k,
@@ -532,9 +543,9 @@ __global__ __launch_bounds__(256, 2) void k_knn_scan(const float* __restrict__ X
     // own splits' database rows and keeps them in its L2
     const int nrb = (Q + FR - 1) / FR, nsplit = nsplit_arg;
     const int xcd = (int)blockIdx.x & 7, i8 = (int)blockIdx.x >> 3;
-    const int split = xcd + 8 * (i8 / nrb);
+    const int split = ROWDEAL ? (int)blockIdx.x / nrb : xcd + 8 * (i8 / nrb);
     if (split >= nsplit) return;
-    const int r0 = (i8 % nrb) * FR;
+    const int r0 = (ROWDEAL ? (int)blockIdx.x % nrb : i8 % nrb) * FR;
     const int cb = split * cols_per_split, ce = min(N, cb + cols_per_split);
     if (cb >= ce) {
         for (int q = 0; q < 16; ++q) {
@@ -719,6 +730,74 @@ __global__ __launch_bounds__(64) void k_knn_merge(const float* __restrict__ part
             atomicAdd(totals + 1, (unsigned long long)(emitted - nvalid));
         }
     }
+}
+
+// mlg_knn_append's list update (one wave per old row): the row's stored list, held across
+// the lanes (lane l = rank l) so the in-place write reads nothing it has overwritten, is one
+// more sorted input next to the window's column splits (indices relative to col0).  k rounds
+// of k_knn_merge's wave argmax, the stored head losing to a new column that is before() it --
+// a new column's index is the larger, so an equal similarity goes first.  What is emitted is
+// a prefix of the stored list interleaved with new columns: the stored entries left over are
+// the evictions, in their former order.  A row no new column enters is not written at all.
+__global__ __launch_bounds__(64) void k_knn_update(const float* __restrict__ part_v, const int32_t* __restrict__ part_i,
+                                                   const int32_t* __restrict__ part_n, int nsplit, int Q, int col0,
+                                                   const int64_t* __restrict__ floor, const uint8_t* __restrict__ hf,
+                                                   int k, int gating, int32_t* __restrict__ idx,
+                                                   float* __restrict__ sim, uint8_t* __restrict__ valid,
+                                                   int32_t* __restrict__ count, int32_t* __restrict__ inserted,
+                                                   int32_t* __restrict__ evicted_idx, int32_t* __restrict__ n_evicted) {
+    const int lane = threadIdx.x, r = blockIdx.x;
+    if (r >= Q) return;
+    const size_t row = (size_t)r * k;
+    const int c_old = min(max(count[r], 0), k);
+    const float sv = lane < c_old ? sim[row + lane] : -INFINITY;
+    const int si = lane < c_old ? idx[row + lane] : -1;
+    const bool own = lane < nsplit;
+    const size_t base = ((size_t)r * nsplit + lane) * k;
+    const int n = own ? min(part_n[(size_t)r * nsplit + lane], k) : 0;
+    int ptr = 0, sptr = 0, emitted = 0, ins = 0;
+    float ov = -INFINITY;
+    int oi = -1;
+    for (int step = 0; step < k; ++step) {
+        float bv = ptr < n ? part_v[base + ptr] : -INFINITY;
+        int bi = ptr < n ? part_i[base + ptr] + col0 : -1;
+        const int mine = bi;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float xv = __shfl_xor(bv, o, 64);
+            const int xi = __shfl_xor(bi, o, 64);
+            if (xi >= 0 && (bi < 0 || before(xv, xi, bv, bi))) { bv = xv; bi = xi; }
+        }
+        const bool has_s = sptr < c_old;  // sptr <= c_old <= 32: a lane of the wave
+        const float hv = __shfl(sv, sptr & 63, 64);
+        const int hi = __shfl(si, sptr & 63, 64);
+        const bool take_new = bi >= 0 && (!has_s || before(bv, bi, hv, hi));
+        if (!take_new && !has_s) break;
+        if (take_new) {
+            if (mine == bi) ++ptr;  // indices are distinct across splits
+            ++ins;
+        } else {
+            ++sptr;
+        }
+        if (lane == emitted) { ov = take_new ? bv : hv; oi = take_new ? bi : hi; }
+        ++emitted;
+    }
+    const int nev = ins ? c_old - sptr : 0;
+    if (lane >= sptr && lane < c_old && ins) evicted_idx[row + lane - sptr] = si;
+    if (lane < k && lane >= nev) evicted_idx[row + lane] = -1;
+    if (lane == 0) {
+        inserted[r] = ins;
+        n_evicted[r] = nev;
+    }
+    if (!ins) return;  // wave-uniform: the stored list stands, bit for bit
+    if (lane < emitted) {
+        bool ok = true;
+        if (gating && hf[r] != 0 && hf[oi]) ok = floor[r] == floor[oi];
+        idx[row + lane] = oi;
+        sim[row + lane] = ov;
+        valid[row + lane] = ok;
+    }
+    if (lane == 0) count[r] = emitted;
 }
 
 // CricaVPR.compute_cross_correlation_score reduction: given C [n1, n2],
@@ -983,11 +1062,79 @@ int mlg_knn_fused(const float* Xq, int Q, const float* Xd, int N, int D, const d
     int32_t* pn = pi + (size_t)Q * nsplit * k;
     const int nrb = (Q + FR - 1) / FR;
     const int grid = 8 * nrb * ((nsplit + 7) / 8);
-    hipLaunchKernelGGL(k_knn_scan, dim3(grid), dim3(256), 0, s, Xq, Q, Xd, N, D, tq, tdb, min_gap, thr, k, cps, nsplit,
+    hipLaunchKernelGGL(k_knn_scan<false>, dim3(grid), dim3(256), 0, s, Xq, Q, Xd, N, D, tq, tdb, min_gap, thr, k, cps, nsplit,
                        pv, pi, pn);
     MLG_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_knn_merge, dim3(Q), dim3(64), 0, s, pv, pi, pn, nsplit, Q, fq, hfq, fdb, hfdb, k, gating, idx,
                        sim, valid, count, totals);
     MLG_LAUNCH_CHECK();
     return MLG_OK;
+}
+
+// ------------------------------------------------------------- streaming ----
+// mlg_knn_append (the rule: include/mlgate.h).  Rows [n_old, n_new) are the batch call on the
+// persistent normalised rows.  Rows [0, n_old) scan the window [n_old, n_new) alone: with 1-64
+// new columns that pass is bound by reading the old rows once (n_old D 4 B), so the grid
+// deals row blocks across the XCDs (k_knn_scan<true>) and splits the window only every
+// UPD_COLS columns; k_knn_update walks a split per lane next to the stored list.
+namespace {
+constexpr int UPD_COLS = 512;       // columns per split of the window (4 tiles)
+constexpr int UPD_MAX_SPLITS = 63;  // k_knn_update: a lane per split
+
+int upd_cols_per_split(int B) {
+    const int tiles = (B + FC - 1) / FC;
+    const int per = std::max(UPD_COLS / FC, (tiles + UPD_MAX_SPLITS - 1) / UPD_MAX_SPLITS);
+    return per * FC;
+}
+
+struct AppendBufs {
+    char* fresh;  // mlg_knn_fused's partial lists of the new rows
+    float* uv;    // the window's partial lists of the old rows: [n_old, splits, k]
+    int32_t *ui, *un;
+    int splits, cps;
+};
+
+size_t append_carve(int n_old, int n_new, int k, void* base, AppendBufs* out) {
+    const int B = n_new - n_old;
+    WsCarver c(base);
+    AppendBufs b;
+    b.cps = upd_cols_per_split(B);
+    b.splits = (B + b.cps - 1) / b.cps;
+    b.fresh = c.take<char>(mlg_knn_fused_ws_bytes(B, n_new, k));
+    b.uv = c.take<float>((size_t)n_old * b.splits * k);
+    b.ui = c.take<int32_t>((size_t)n_old * b.splits * k);
+    b.un = c.take<int32_t>((size_t)n_old * b.splits);
+    if (out) *out = b;
+    return c.total();
+}
+}  // namespace
+
+size_t mlg_knn_append_ws_bytes(int n_old, int n_new, int k) {
+    if (n_old < 0 || n_new <= n_old || k <= 0 || k > FKMAX) return 0;
+    return append_carve(n_old, n_new, k, nullptr, nullptr);
+}
+
+int mlg_knn_append_run(const float* xn, int n_old, int n_new, int D, const double* t, const int64_t* floor,
+                       const uint8_t* hf, double min_gap, float thr, int k, int gating, void* ws, size_t ws_bytes,
+                       int32_t* idx, float* sim, uint8_t* valid, int32_t* count, int32_t* inserted,
+                       int32_t* evicted_idx, int32_t* n_evicted, hipStream_t s, int phases) {
+    if (n_old < 0 || n_new <= n_old || D <= 0 || (D % 4) || k <= 0 || k > FKMAX) return MLG_EINVAL;
+    if (gating && (!floor || !hf)) return MLG_EINVAL;
+    AppendBufs b;
+    if (append_carve(n_old, n_new, k, ws, &b) > ws_bytes) return MLG_ENOMEM;
+    const int B = n_new - n_old;
+    if (n_old > 0 && (phases & MLG_KNN_APPEND_UPDATE)) {
+        const int nrb = (n_old + FR - 1) / FR;
+        hipLaunchKernelGGL(k_knn_scan<true>, dim3(nrb * b.splits), dim3(256), 0, s, xn, n_old, xn + (size_t)n_old * D,
+                           B, D, t, t + n_old, min_gap, thr, k, b.cps, b.splits, b.uv, b.ui, b.un);
+        MLG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_knn_update, dim3(n_old), dim3(64), 0, s, b.uv, b.ui, b.un, b.splits, n_old, n_old, floor,
+                           hf, k, gating, idx, sim, valid, count, inserted, evicted_idx, n_evicted);
+        MLG_LAUNCH_CHECK();
+    }
+    if (!(phases & MLG_KNN_APPEND_FRESH)) return MLG_OK;
+    return mlg_knn_fused(xn + (size_t)n_old * D, B, xn, n_new, D, t + n_old, t, gating ? floor + n_old : nullptr,
+                         gating ? hf + n_old : nullptr, gating ? floor : nullptr, gating ? hf : nullptr, min_gap, thr, k,
+                         gating, b.fresh, idx + (size_t)n_old * k, sim + (size_t)n_old * k, valid + (size_t)n_old * k,
+                         count + n_old, nullptr, s);
 }

@@ -586,6 +586,50 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> seq_gate(const Tensor& desc, const Te
     return {s_score, s_dir, s_terms, keep};
 }
 
+// knn_gate as keyframes arrive (mlg_knn_append states the rule).  The state tensors are the caller's and
+// are updated in place: xn f32 [cap, D] (rows [0, n_new) normalised), t f64 / floor int64 / has_floor uint8
+// [cap], idx int32 / sim f32 / valid uint8 [cap, k], count int32 [cap] -> inserted int32 [n_old],
+// evicted_idx int32 [n_old, k], n_evicted int32 [n_old]
+std::tuple<Tensor, Tensor, Tensor> knn_append(const Tensor& xn, const Tensor& t, const Tensor& floor,
+                                              const Tensor& has_floor, const Tensor& idx, const Tensor& sim,
+                                              const Tensor& valid, const Tensor& count, int64_t n_old, int64_t n_new,
+                                              double min_gap, double thr, int64_t k, bool gating, int64_t phases) {
+    want(xn, at::kFloat, "xn");
+    want(t, at::kDouble, "t");
+    want(floor, at::kLong, "floor");
+    want(has_floor, at::kByte, "has_floor");
+    want(idx, at::kInt, "idx");
+    want(sim, at::kFloat, "sim");
+    want(valid, at::kByte, "valid");
+    want(count, at::kInt, "count");
+    TORCH_CHECK(xn.dim() == 2, "xn must be [cap, D]");
+    const int64_t cap = xn.size(0), D = xn.size(1);
+    TORCH_CHECK(t.numel() == cap && floor.numel() == cap && has_floor.numel() == cap,
+                "t / floor / has_floor must be [cap]");
+    TORCH_CHECK(idx.dim() == 2 && idx.size(0) == cap && idx.size(1) == k && sim.sizes() == idx.sizes() &&
+                    valid.sizes() == idx.sizes() && count.numel() == cap,
+                "idx / sim / valid must be [cap, k], count [cap]");
+    TORCH_CHECK(k >= 1 && k <= 32, "knn_append: k must be in [1, 32]");
+    TORCH_CHECK(D % 4 == 0, "knn_append: D must be a multiple of 4");
+    TORCH_CHECK(n_old >= 0 && n_old < n_new && n_new <= cap, "knn_append: need 0 <= n_old < n_new <= cap");
+    for (const Tensor* x : {&t, &floor, &has_floor, &idx, &sim, &valid, &count})
+        TORCH_CHECK(x->device() == xn.device(), "knn_append: every state tensor must be on ", xn.device());
+    c10::DeviceGuard g(xn.device());
+    auto o = xn.options().dtype(at::kInt);
+    Tensor inserted = at::empty({n_old}, o), evicted = at::empty({n_old, k}, o), n_evicted = at::empty({n_old}, o);
+    const size_t nbytes = mlg_knn_append_workspace_bytes((int)n_old, (int)n_new, (int)D, (int)k);
+    TORCH_CHECK(nbytes > 0, "knn_append: unsupported shape n_old=", n_old, " n_new=", n_new, " D=", D, " k=", k);
+    Tensor ws = workspace(nbytes, xn);
+    TORCH_CHECK(phases >= 1 && phases <= 3, "knn_append: phases must be 1 (update), 2 (fresh) or 3 (both)");
+    check_rc(mlg_op_knn_append_phases(cp<float>(xn), (int)n_old, (int)n_new, (int)D, cp<double>(t), cp<int64_t>(floor),
+                            cp<uint8_t>(has_floor), min_gap, (float)thr, (int)k, gating ? 1 : 0, ws.data_ptr(),
+                            (size_t)ws.numel(), mp<int32_t>(idx), mp<float>(sim), mp<uint8_t>(valid),
+                            mp<int32_t>(count), mp<int32_t>(inserted), mp<int32_t>(evicted), mp<int32_t>(n_evicted),
+                            (int)phases, stream_of(xn)),
+             "mlg_knn_append");
+    return {inserted, evicted, n_evicted};
+}
+
 // --------------------------------------------------------------- LightGlue
 std::tuple<Tensor, Tensor, Tensor, Tensor> lightglue(const Tensor& kpts, const Tensor& desc, const Tensor& counts,
                                                      const Tensor& pair_a, const Tensor& pair_b, at::TensorList w,
@@ -1247,6 +1291,10 @@ TORCH_LIBRARY(mlgate, m) {
     m.def("seq_gate(Tensor desc, Tensor t, Tensor floor, Tensor has_floor, Tensor idx, Tensor sim, Tensor? mask, "
           "Tensor count, int radius, float threshold, float min_gap, int min_terms, int q0, Tensor(a!)? totals) "
           "-> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("knn_append(Tensor xn, Tensor t, Tensor floor, Tensor has_floor, Tensor(a!) idx, Tensor(b!) sim, "
+          "Tensor(c!) valid, Tensor(d!) count, int n_old, int n_new, float min_gap, float thr, int k, bool gating, "
+          "int phases=3) "
+          "-> (Tensor, Tensor, Tensor)");
     m.def("superpoint(Tensor frames, Tensor[] weights, float detection_threshold, int max_keypoints, "
           "int nms_radius, int remove_borders, bool with_bf16) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("lightglue(Tensor kpts, Tensor desc, Tensor counts, Tensor pair_a, Tensor pair_b, Tensor[] weights, "
@@ -1310,6 +1358,7 @@ TORCH_LIBRARY_IMPL(mlgate, CUDA, m) {
     m.impl("xcorr_batch", &xcorr_batch);
     m.impl("rerank_gate", &rerank_gate);
     m.impl("seq_gate", &seq_gate);
+    m.impl("knn_append", &knn_append);
     m.impl("superpoint", &superpoint);
     m.impl("lightglue", &lightglue);
     m.impl("ransac_epipolar", &ransac_epipolar);

@@ -18,8 +18,10 @@ from .lidar import FloorEstimate, LiDARFloorTracker, MultiModalFloorDetector
 from .verify import (GeometricVerifier, LightGlue, LoFTR, MatchResult, SemanticGeometricVerifier, SuperGlue)
 from .vpr import (AnyLoc, CricaVPR, MixVPR, PlaceDescriptor, PlaceMatch, SALAD, SemanticPlaceRecognition,
                   process_image_sequence)
+from .pipeline import StreamingGate  # the composed gate for keyframes as they arrive (not in the reference)
 
 __all__ = [
+    'StreamingGate',
     'IMUFloorDetector', 'ElevatorEvent', 'load_imu_from_bag',
     'LiDARFloorTracker', 'MultiModalFloorDetector', 'FloorEstimate',
     'SemanticLoopClosureGate', 'LoopClosureCandidate', 'ContextualPriorFactor', 'integrate_with_orbslam3',

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmlgate.so")
 TORCH_LIB_PATH = os.path.join(_HERE, "libmlgate_torch.so")
 OPS = ("vit_forward_into", "dino_forward_into", "dino_weights_check", "salad_forward", "knn_gate", "knn_query", "row_normalize", "similarity", "xcorr_score", "xcorr_batch", "rerank_gate", "seq_gate",
-       "superpoint",
+       "knn_append", "superpoint",
        "lightglue", "ransac_epipolar", "recover_pose", "resnet50", "loftr_features", "loftr_pack_tails", "loftr_coarse_layer", "loftr_match", "superglue", "pillow_resize_224", "plane_ransac", "proximity",
        "jpeg_pixels", "mixvpr_forward", "mixvpr_head", "mixvpr_preprocess", "vlad", "anyloc_forward", "kmeans_step",
        "crica_forward", "vit_trunk", "crica_pool", "crica_encoder",
@@ -149,6 +149,11 @@ EXPORTS = {
     "mlg_seq_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mlg_seq_gate": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                      + [c_int, c_double, c_int, c_double, c_void_p, c_size_t] + [c_void_p] * 6),
+    "mlg_knn_append_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mlg_knn_append": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_float, c_int,
+                               c_int, c_void_p, c_size_t] + [c_void_p] * 8),
+    "mlg_op_knn_append_phases": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_float,
+                                         c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 7 + [c_int, c_void_p]),
     "mlg_dbg_lg_trace_begin": (c_int, [c_void_p, c_size_t]),
     "mlg_dbg_lg_trace_end": (c_int, [c_void_p, c_void_p, c_int]),
     "mlg_dbg_fill_lds": (c_int, [ctypes.c_uint32, c_void_p, c_void_p]),

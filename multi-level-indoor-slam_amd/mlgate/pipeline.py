@@ -30,6 +30,9 @@ Two front ends run the same kernels:
   * ``DeviceGate`` is the same chain on device arrays, frame-sharded over ranks (one
     process per GPU, RCCL all-gathers; bench.py's step).  Its decisions and counts are
     those of FullSemanticGate (tests/test_pipeline_gpu.py).
+``StreamingGate`` is DeviceGate for keyframes that arrive one batch at a time: after any
+sequence of appends its lists, per-pair results and counts are DeviceGate.step()'s on the
+keyframes seen so far (tests/test_streaming_gate_gpu.py).
 """
 import time
 from dataclasses import dataclass, field
@@ -285,6 +288,28 @@ def decide_pairs(n, inl, ta, tb, f_num, limit, min_inliers, min_inlier_ratio, n_
     n_valid_t += ok.sum()
     gate_rej_t += (ok & ((f_num[ta] - f_num[tb]).abs() > limit)).sum()
     return ok
+
+
+def _ransac_pairs(torch, dev, KP, K, kp_all, m, n, la, lb):
+    """geometry.epipolar_ransac_device's whole result (model, mask, inliers, pose, status) for
+    the P pairs DeviceGate._ransac_inliers describes: the flat match arrays laid out on the
+    device without a host sync, one batched RANSAC (+ recoverPose when K is given)."""
+    from . import geometry
+    P = len(la)
+    sidx = torch.arange(KP, device=dev)
+    lv = sidx[None, :] < n[:, None]
+    la = torch.from_numpy(la).to(dev).long()
+    lb = torch.from_numpy(lb).to(dev).long()
+    offs = torch.zeros(P + 1, dtype=torch.int32, device=dev)
+    offs[1:] = torch.cumsum(n, 0)
+    dest = torch.where(lv, offs[:-1, None].long() + sidx[None, :], P * KP).view(-1)
+    m0 = torch.where(lv, m[:, :, 0].long(), 0)
+    m1 = torch.where(lv, m[:, :, 1].long(), 0)
+    k1 = kp_all.new_zeros(P * KP + 1, 2)
+    k2 = kp_all.new_zeros(P * KP + 1, 2)
+    k1.index_copy_(0, dest, kp_all[la[:, None], m0].view(-1, 2))
+    k2.index_copy_(0, dest, kp_all[lb[:, None], m1].view(-1, 2))
+    return geometry.epipolar_ransac_device(k1[:P * KP], k2[:P * KP], offs, K, 0, 3.0)
 
 
 class DeviceGate:
@@ -680,23 +705,7 @@ class DeviceGate:
         laid out on the device without a host sync (no nonzero): pair p's matches go to
         [offs[p], offs[p] + n[p]) of a buffer of P * kp rows (RANSAC reads each pair's own
         range only), the padding of the match lists to one dummy row past the end."""
-        torch = self.torch
-        from . import geometry
-        P, KP = len(la), self.kp
-        sidx = torch.arange(KP, device=self.dev)
-        lv = sidx[None, :] < n[:, None]
-        la = torch.from_numpy(la).to(self.dev).long()
-        lb = torch.from_numpy(lb).to(self.dev).long()
-        offs = torch.zeros(P + 1, dtype=torch.int32, device=self.dev)
-        offs[1:] = torch.cumsum(n, 0)
-        dest = torch.where(lv, offs[:-1, None].long() + sidx[None, :], P * KP).view(-1)
-        m0 = torch.where(lv, m[:, :, 0].long(), 0)
-        m1 = torch.where(lv, m[:, :, 1].long(), 0)
-        k1 = kp_all.new_zeros(P * KP + 1, 2)
-        k2 = kp_all.new_zeros(P * KP + 1, 2)
-        k1.index_copy_(0, dest, kp_all[la[:, None], m0].view(-1, 2))
-        k2.index_copy_(0, dest, kp_all[lb[:, None], m1].view(-1, 2))
-        return geometry.epipolar_ransac_device(k1[:P * KP], k2[:P * KP], offs, self.K, 0, 3.0)[2]
+        return _ransac_pairs(self.torch, self.dev, self.kp, self.K, kp_all, m, n, la, lb)[2]
 
     def _verify_loftr(self, pa_t, pb_t, out):
         """verify_with_semantics with GeometricVerifier('loftr') on this rank's slice of the
@@ -783,3 +792,204 @@ class DeviceGate:
         take = max(0, min(pa_t.numel(), limit - before))
         return pa_t[:take], pb_t[:take]
 
+
+
+class StreamingGate:
+    """DeviceGate for keyframes that arrive one batch at a time: ``append`` gates the new
+    keyframes against everything seen and updates what the earlier ones close against, paying
+    for the new rows only.  After any sequence of appends the state is what
+    ``DeviceGate(...).step()`` computes on the keyframes seen so far -- the retrieval lists bit
+    for bit (mlg_knn_append, include/mlgate.h), every per-pair match count, inlier count and
+    decision, and every count of ``report()``.  One GPU, the LightGlue matcher; the sequence
+    check, the re-ranking and the local features are DeviceGate's alone.  The host side is
+    mlgate.stream_plan (CPU-tested); the arguments have DeviceGate's names and meaning."""
+
+    def __init__(self, capacity, device='cuda', k=10, similarity_threshold=0.5, min_time_gap=10.0, strict_mode=True,
+                 retrieval_floor_gating=True, verifier_floor_gating=True, verify=True, K=None, min_inliers=20,
+                 min_inlier_ratio=0.25, vit_batch=123, sp_batch=64, lg_chunk=1024, max_keypoints=2048,
+                 vit_state_dict=None, vit_precise=True, backbone='dinov2_vitb14'):
+        if int(capacity) < 1:
+            raise ValueError(f"capacity must be >= 1 (got {capacity})")
+        if not 1 <= int(k) <= 32:  # refused before anything is built
+            raise ValueError(f"StreamingGate takes k in [1, 32] (got k = {k})")
+        import torch
+        from . import retrieval, stream_plan
+        from .lightglue import LightGlueGPU
+        from .superpoint import SuperPointGPU
+        from .vit import engine_for
+        from .weights import backbone_config, synthetic_state_dict
+        self.torch = torch
+        self.dev = torch.device(device)
+        self.capacity, self.k = int(capacity), int(k)
+        self.embed = backbone_config(backbone)[0]
+        self.verify, self.sp_batch, self.lg_chunk, self.kp = bool(verify), int(sp_batch), int(lg_chunk), max_keypoints
+        self.knn = retrieval.StreamingKnn(self.capacity, self.embed, self.k, min_time_gap, similarity_threshold,
+                                          retrieval_floor_gating, self.dev)
+        self.plan = stream_plan.StreamPlan(self.capacity, self.k, strict_mode, verifier_floor_gating, verify,
+                                           min_inliers, min_inlier_ratio)
+        sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
+        self.eng = engine_for(sd, backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise)
+        self.K = None
+        if self.verify:
+            self.K = (torch.from_numpy(np.asarray(K, np.float64).reshape(9).copy()).to(self.dev)
+                      if K is not None else None)
+            self.sp = SuperPointGPU(device=self.dev, max_num_keypoints=self.kp)
+            self.lg = LightGlueGPU(device=self.dev)
+            # every keyframe's SuperPoint features, extracted once when it arrives
+            self.kp_tab = torch.empty(self.capacity, self.kp, 2, device=self.dev)
+            self.ds_tab = torch.empty(self.capacity, self.kp, 256, device=self.dev)
+            self.cnt_tab = torch.zeros(self.capacity, dtype=torch.int32, device=self.dev)
+        self.h_kpcount = np.zeros(self.capacity, np.int32)
+        self.frame_shape = None
+        # ordered pairs that have gone through RANSAC, ever: no pair does twice
+        self.ransac_pairs = 0
+        self.last_append = {}
+        # a list here makes append() record a timed HIP event after each stage: (stage, event)
+        # pairs, the stage being what ran since the previous event (tools/bench_streaming_gate.py)
+        self.stage_events = None
+
+    def _mark(self, stage):
+        if self.stage_events is not None:
+            e = self.torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.stage_events.append((stage, e))
+
+    @property
+    def n(self):
+        return self.plan.n
+
+    def lists(self):
+        """The retrieval lists on the device (StreamingKnn.lists)."""
+        return self.knn.lists()
+
+    def report(self):
+        """DeviceGate.step()'s counts on the keyframes seen so far."""
+        return self.plan.counts()
+
+    def pair_results(self):
+        """The live verified ordered pairs, sorted by (a, b): gate_plan.pair_records' form."""
+        return self.plan.pair_results()
+
+    def append(self, frames, timestamps, floor_labels):
+        """frames uint8 [B, H, W, C] on the device, their timestamps and floor labels.  Runs the
+        ViT and SuperPoint on the new frames only, updates every retrieval list, brings the
+        changed rows to the host in one transfer, and verifies the ordered pairs that are new.
+        Returns the cumulative counts plus 'appended', 'new_pairs_verified', 'pairs_evicted',
+        'new_closures' (arrays a, b, similarity, matches, inliers, and pose f64 [P, 4, 4] when K
+        is given, of the pairs every stage newly accepts) and 'retracted' (arrays a, b of the
+        pairs accepted earlier whose entry a better match has now pushed out)."""
+        torch, dev, k = self.torch, self.dev, self.k
+        from . import stream_plan
+        # everything is checked before the first launch
+        try:
+            frames = _native.device_frames(frames)
+        except TypeError as e:
+            raise ValueError(str(e))
+        B = int(frames.shape[0])
+        ts = np.asarray(timestamps, np.float64).reshape(-1)
+        labels = stream_plan.label_list(floor_labels)
+        if B < 1 or len(ts) != B or len(labels) != B:
+            raise ValueError(f"{B} frames, {len(ts)} timestamps, {len(labels)} floor labels")
+        n_old, n_new = self.n, self.n + B
+        if n_new > self.capacity:
+            raise ValueError(f"appending {B} keyframes to {n_old} exceeds the capacity {self.capacity}")
+        if self.frame_shape is None:
+            self.frame_shape = tuple(frames.shape[1:])
+        elif tuple(frames.shape[1:]) != self.frame_shape:
+            raise ValueError(f"frames are {tuple(frames.shape[1:])}, the first append's were {self.frame_shape}")
+        codes, has = self.plan.add_labels(labels)
+
+        # 1-3: descriptors and SuperPoint features of the new frames, then the kNN update
+        self._mark("start")
+        desc = torch.empty(B, self.embed, dtype=torch.float32, device=dev)
+        self.eng.forward_into(frames, desc, None)
+        self._mark("vit")
+        if self.verify:
+            for b0 in range(0, B, self.sp_batch):
+                kp, _, ds, _, cnt = self.sp.extract_device(frames[b0:b0 + self.sp_batch])
+                dst = slice(n_old + b0, n_old + b0 + kp.shape[0])
+                self.kp_tab[dst].copy_(kp)
+                self.ds_tab[dst].copy_(ds)
+                self.cnt_tab[dst].copy_(cnt)
+        self._mark("superpoint")
+        inserted, ev_idx, n_ev = self.knn.append(desc, torch.from_numpy(ts).to(dev), torch.from_numpy(codes).to(dev),
+                                                 torch.from_numpy(has).to(dev))
+        self._mark("knn_append")
+
+        # 4: which old rows changed (4 B per old row), then those rows and the new ones in one
+        # transfer: idx | sim bits | valid | count | n_evicted | evicted_idx | keypoint count
+        rows = self.plan.changed_rows(inserted.cpu().numpy(), n_old, n_new)
+        rt = torch.from_numpy(rows).to(dev)
+        fresh = rt >= n_old
+        old = rt.clamp(max=max(n_old - 1, 0))
+        i32 = lambda x: x.to(torch.int32)  # noqa: E731
+        nev = torch.where(fresh, 0, n_ev[old]) if n_old else torch.zeros_like(rt, dtype=torch.int32)
+        ev = (torch.where(fresh[:, None], -1, ev_idx[old]) if n_old
+              else torch.full((len(rows), k), -1, dtype=torch.int32, device=dev))
+        kpc = self.cnt_tab[rt] if self.verify else torch.zeros_like(rt, dtype=torch.int32)
+        packed = torch.cat([self.knn.idx[rt], self.knn.sim[rt].view(torch.int32), i32(self.knn.valid[rt]),
+                            self.knn.count[rt][:, None], i32(nev)[:, None], i32(ev), i32(kpc)[:, None]], 1).cpu().numpy()
+        r_idx, r_sim = packed[:, :k], packed[:, k:2 * k].copy().view(np.float32)
+        r_valid, r_count, r_nev = packed[:, 2 * k:3 * k].astype(np.uint8), packed[:, 3 * k], packed[:, 3 * k + 1]
+        r_ev = packed[:, 3 * k + 2:4 * k + 2]
+        self.h_kpcount[n_old:n_new] = packed[len(rows) - B:, 4 * k + 2]
+        up = self.plan.update(n_new, rows, r_idx, r_sim, r_valid, r_count, r_nev, r_ev)
+        self._mark("transfer_and_plan")
+
+        # 5-6: LightGlue under the canonical orientation and RANSAC on the new ordered pairs
+        # only, in DeviceGate's chunks; their results come to the host in one transfer
+        va, vb = up["verify"]
+        closures = {"a": va[:0], "b": vb[:0], "similarity": np.zeros(0, np.float32),
+                    "matches": np.zeros(0, np.int32), "inliers": np.zeros(0, np.int32)}
+        if self.K is not None:
+            closures["pose"] = np.zeros((0, 4, 4), np.float64)
+        if len(va):
+            n_m, n_i, pose = self._verify_pairs(va, vb)
+            _, acc = self.plan.record(va, vb, n_m, n_i, pose)
+            s = self.plan._slots(va[acc].astype(np.int64), vb[acc].astype(np.int64))
+            closures.update(a=va[acc], b=vb[acc], similarity=self.plan.sim[va[acc], s], matches=n_m[acc],
+                            inliers=n_i[acc])
+            if pose is not None:
+                closures["pose"] = pose[acc]
+        self._mark("results_and_plan")
+        out = self.plan.counts()
+        out.update(appended=B, new_pairs_verified=len(va), pairs_evicted=len(up["evicted"][0]), new_closures=closures,
+                   retracted={"a": up["retracted"][0], "b": up["retracted"][1]})
+        # what this append did, for tests and tools: the ordered pairs it sent through RANSAC
+        self.last_append = {"changed_rows": len(rows), "new_pairs": len(up["new"][0]), "verified": (va, vb)}
+        return out
+
+    def _verify_pairs(self, pa, pb):
+        """(matches int32 [P], inliers int32 [P], pose f64 [P, 4, 4] or None) of the ordered
+        pairs (pa, pb): LightGlue once per unordered (min, max) pair and mlg_lg_orient_matches,
+        then one RANSAC per ordered pair, as DeviceGate._verify_lightglue runs them."""
+        torch, dev = self.torch, self.dev
+        ua, ub, inv, swap_all, order = self.plan.canonical(pa, pb)
+        starts, bounds = gate_plan.chunk_starts(len(ua), self.lg_chunk, 0, inv[order])
+        parts = []
+        for ci in range(len(starts) - 1):
+            c0, c1 = starts[ci], starts[ci + 1]
+            mu, su, nu, _ = self.lg.match_device(self.kp_tab, self.ds_tab, self.h_kpcount, ua[c0:c1], ub[c0:c1])
+            sel = order[bounds[ci]:bounds[ci + 1]]
+            rows = torch.from_numpy((inv[sel] - c0).astype(np.int32)).to(dev)
+            sw = torch.from_numpy(swap_all[sel]).to(dev)
+            m, _, n = _native.ops().lg_orient(mu, su, nu, rows, sw)
+            self._mark("lightglue")
+            _, _, inl, pose, _ = _ransac_pairs(torch, dev, self.kp, self.K, self.kp_tab, m, n,
+                                               np.asarray(pa[sel], np.int32), np.asarray(pb[sel], np.int32))
+            self._mark("ransac")
+            self.ransac_pairs += len(sel)
+            parts.append((sel, n, inl, pose))
+        sel = np.concatenate([p[0] for p in parts])
+        cols = [torch.cat([p[1] for p in parts]).double()[:, None], torch.cat([p[2] for p in parts]).double()[:, None]]
+        has_pose = parts[0][3] is not None
+        if has_pose:
+            cols.append(torch.cat([p[3] for p in parts]).view(-1, 16))
+        host = torch.cat(cols, 1).cpu().numpy()
+        n_m, n_i = np.zeros(len(pa), np.int32), np.zeros(len(pa), np.int32)
+        n_m[sel], n_i[sel] = host[:, 0].astype(np.int32), host[:, 1].astype(np.int32)
+        pose = None
+        if has_pose:
+            pose = np.zeros((len(pa), 4, 4), np.float64)
+            pose[sel] = host[:, 2:].reshape(-1, 4, 4)
+        return n_m, n_i, pose

@@ -27,6 +27,64 @@ def knn_gate(desc, t, floor, has_floor, min_gap, thr, k, gating, q0=0, Q=None, t
                                   int(q0), int(Q), totals)
 
 
+class StreamingKnn:
+    """knn_gate as keyframes arrive (mlg_knn_append; include/mlgate.h states the rule): after
+    any sequence of appends, ``lists()`` holds bit for bit what ``knn_gate`` returns on the
+    keyframes appended so far.  Owns the device state, sized to ``capacity`` rows: the
+    normalised descriptors, the timestamps and floor codes, and the per-row lists."""
+
+    def __init__(self, capacity, D, k, min_gap, thr, gating, device="cuda"):
+        import torch
+        if capacity < 1:
+            raise ValueError(f"capacity must be >= 1 (got {capacity})")
+        if not 1 <= k <= 32:
+            raise ValueError(f"StreamingKnn takes k in [1, 32] (got {k})")
+        if D < 4 or D % 4:
+            raise ValueError(f"StreamingKnn takes D % 4 == 0 (got {D})")
+        self.capacity, self.D, self.k = int(capacity), int(D), int(k)
+        self.min_gap, self.thr, self.gating = float(min_gap), float(thr), bool(gating)
+        self.n = 0
+        dev = torch.device(device)
+        self.xn = torch.zeros(self.capacity, self.D, dtype=torch.float32, device=dev)
+        self.t = torch.zeros(self.capacity, dtype=torch.float64, device=dev)
+        self.floor = torch.zeros(self.capacity, dtype=torch.int64, device=dev)
+        self.has_floor = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
+        self.idx = torch.full((self.capacity, self.k), -1, dtype=torch.int32, device=dev)
+        self.sim = torch.zeros(self.capacity, self.k, dtype=torch.float32, device=dev)
+        self.valid = torch.zeros(self.capacity, self.k, dtype=torch.uint8, device=dev)
+        self.count = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+
+    def append(self, desc_new, t_new, floor_new, has_new):
+        """desc_new f32 [B, D] (raw descriptors), t_new f64 [B], floor_new i64 [B], has_new u8
+        [B], on the device.  Normalises the new rows into place, updates every list, and
+        returns the device tensors (inserted int32 [n_old], evicted_idx int32 [n_old, k],
+        n_evicted int32 [n_old]) of the rows that were there before.  No host sync."""
+        B = desc_new.shape[0]
+        if desc_new.dim() != 2 or desc_new.shape[1] != self.D or B < 1:
+            raise ValueError(f"desc_new must be [B >= 1, {self.D}] (got {tuple(desc_new.shape)})")
+        if not (t_new.numel() == B and floor_new.numel() == B and has_new.numel() == B):
+            raise ValueError(f"t_new / floor_new / has_new must each hold {B} entries (got {t_new.numel()}, "
+                             f"{floor_new.numel()}, {has_new.numel()})")
+        n_old, n_new = self.n, self.n + B
+        if n_new > self.capacity:
+            raise ValueError(f"appending {B} keyframes to {n_old} exceeds the capacity {self.capacity}")
+        ops = _native.ops()
+        self.xn[n_old:n_new] = ops.row_normalize(desc_new.contiguous())
+        self.t[n_old:n_new] = t_new.reshape(-1)
+        self.floor[n_old:n_new] = floor_new.reshape(-1)
+        self.has_floor[n_old:n_new] = has_new.reshape(-1)
+        out = ops.knn_append(self.xn, self.t, self.floor, self.has_floor, self.idx, self.sim, self.valid, self.count,
+                             n_old, n_new, self.min_gap, self.thr, self.k, self.gating)
+        self.n = n_new
+        return out
+
+    def lists(self):
+        """Views (idx int32 [n, k], sim f32 [n, k], valid uint8 [n, k], count int32 [n]) of the
+        state, in knn_gate's layout."""
+        n = self.n
+        return self.idx[:n], self.sim[:n], self.valid[:n], self.count[:n]
+
+
 def pairwise_similarities(desc):
     """Device float32 N x N cosine similarity matrix (compute_all_pairwise_similarities)."""
     ops = _native.ops()
