@@ -1,7 +1,8 @@
-"""DeviceGate's host plan: which pairs exist, which are skipped, how they are grouped,
-chunked and recorded.  numpy only -- no device, no native library -- so every decision
-here is checked on the CPU (tests/test_gate_plan_cpu.py); mlgate.pipeline runs the device
-work these plans drive.  (csrc/pair_plan.h is the same split for the matchers' C++ side.)
+"""DeviceGate's host plan: how floor labels are coded, which pairs exist, which are skipped,
+how they are grouped, chunked and recorded.  numpy only -- no device, no native library -- so
+every decision here is checked on the CPU (tests/test_gate_plan_cpu.py); mlgate.pipeline and
+mlgate.lg_pairs run the device work these plans drive.  (csrc/pair_plan.h is the same split
+for the matchers' C++ side.)
 """
 import numpy as np
 
@@ -35,10 +36,57 @@ def pairs_from_sequence(h_idx, h_keep, lo):
     return _row_major(h_idx, h_keep != 0, lo)
 
 
+class FloorCoder:
+    """Integer codes with the reference's equality semantics for the floor check
+    ``query_floor == match_floor`` (place_recognition.py:896-899): labels that compare
+    equal in Python share a code (1 and 1.0 included), every NaN gets its own code
+    (NaN != NaN), None marks "no label" (has = 0).  One coder across several extend() calls
+    gives the codes of one call on the concatenation (StreamingGate's appends)."""
+
+    def __init__(self):
+        self.seen, self.nxt = {}, 0
+
+    def extend(self, labels):
+        """(codes int64, has uint8) of the new labels."""
+        codes = np.zeros(len(labels), np.int64)
+        has = np.ones(len(labels), np.uint8)
+        for i, f in enumerate(labels):
+            if f is None:
+                has[i] = 0
+            elif isinstance(f, (float, np.floating)) and f != f:
+                codes[i] = self.nxt
+                self.nxt += 1
+            else:
+                key = f.item() if isinstance(f, np.generic) else f
+                if key not in self.seen:
+                    self.seen[key] = self.nxt
+                    self.nxt += 1
+                codes[i] = self.seen[key]
+        return codes, has
+
+
+def floor_codes(labels):
+    """(codes int64, has uint8) of a whole list of labels: FloorCoder's rule."""
+    return FloorCoder().extend(labels)
+
+
+def label_list(floor_labels):
+    """The labels as Python objects (an object array keeps its elements; any other array
+    goes through tolist)."""
+    lab = np.asarray(floor_labels)
+    return list(lab) if lab.dtype == object else list(lab.tolist())
+
+
+def numeric_labels(lab):
+    """label_list's labels as the float64 array of the gate's |floor_i - floor_j| > limit
+    (loop_closure_gate.py:91-98): None is NaN, which never rejects."""
+    return np.array([np.nan if v is None else float(v) for v in lab], np.float64)
+
+
 def same_floor(pa, pb, h_codes, h_has):
     """The pairs verify_with_semantics does NOT skip: it skips when floor1 != floor2 in
     Python (geometric_verification.py:709-710) -- None == None only, NaN != NaN (equality
-    codes of vpr.floor_codes: every NaN keyframe has its own code)."""
+    codes of floor_codes: every NaN keyframe has its own code)."""
     ha, hb = h_has[pa] != 0, h_has[pb] != 0
     return (ha & hb & (h_codes[pa] == h_codes[pb])) | (~ha & ~hb)
 

@@ -32,7 +32,8 @@ Two front ends run the same kernels:
     those of FullSemanticGate (tests/test_pipeline_gpu.py).
 ``StreamingGate`` is DeviceGate for keyframes that arrive one batch at a time: after any
 sequence of appends its lists, per-pair results and counts are DeviceGate.step()'s on the
-keyframes seen so far (tests/test_streaming_gate_gpu.py).
+keyframes seen so far (tests/test_streaming_gate_gpu.py); the two share mlgate.lg_pairs (feature
+table, LightGlue chunk loop, RANSAC call) and gate_plan's floor coding.
 """
 import time
 from dataclasses import dataclass, field
@@ -40,7 +41,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import _native, gate_plan
+from . import _native, gate_plan, lg_pairs, stream_plan
 
 from .floors import IMUFloorDetector
 from .gate import LoopClosureCandidate, SemanticLoopClosureGate
@@ -112,15 +113,9 @@ class FullSemanticGate:
         self.seq_radius, self.seq_threshold, self.seq_min_terms = _seq_args(seq_radius, seq_threshold, seq_min_terms, k)
         # rerank_top_k: CricaVPR.rerank_candidates (place_recognition.py:714-757) between
         # retrieval and verification, as DeviceGate(rerank_top_k=...) runs it; None: no such stage
-        if rerank_top_k is not None:
-            if vpr_method != 'cricavpr':
-                raise ValueError(f"rerank_top_k needs CricaVPR's cached local features; the {vpr_method} method "
-                                 "caches none")
-            if int(rerank_top_k) < 1:
-                raise ValueError(f"rerank_top_k must be >= 1 (got {rerank_top_k})")
-            if k > 64:
-                raise ValueError(f"rerank_top_k takes k <= 64 (got k = {k})")
-        self.rerank_top_k = None if rerank_top_k is None else int(rerank_top_k)
+        self.rerank_top_k = _rerank_arg(
+            rerank_top_k, k, vpr_method == 'cricavpr',
+            f"rerank_top_k needs CricaVPR's cached local features; the {vpr_method} method caches none")
         # the DINOv2 backbone of the 'cricavpr' / 'anyloc' methods (dinov2_vits14 / b14 / l14)
         self.backbone = backbone
         self.similarity_threshold, self.min_time_gap, self.k = similarity_threshold, min_time_gap, k
@@ -208,13 +203,12 @@ class FullSemanticGate:
         the descriptors, timestamps and floor codes find_loop_closures used; order unchanged."""
         import torch
         from . import retrieval
-        from .vpr import floor_codes
         if not to_verify:
             return [], []
         rows, idx, sim, count = self._rows(to_verify, n)
         descs = self.spr.vpr.descriptors
         X, dev = self.spr.vpr._device_matrix()
-        codes, has = floor_codes([d.floor_label for d in descs])
+        codes, has = gate_plan.floor_codes([d.floor_label for d in descs])
         keep = retrieval.sequence_gate(
             X, torch.tensor([float(d.timestamp) for d in descs], dtype=torch.float64, device=dev),
             torch.from_numpy(codes).to(dev), torch.from_numpy(has).to(dev), torch.from_numpy(idx).to(dev),
@@ -273,6 +267,35 @@ def _seq_args(seq_radius, seq_threshold, seq_min_terms, k):
     return int(seq_radius), float(seq_threshold), int(seq_min_terms)
 
 
+def _rerank_arg(rerank_top_k, k, has_local_features, why_not):
+    """rerank_top_k (int or None) of both gates, refused before anything is built: without the
+    gate's local features (ValueError(why_not)), below 1, or with more slots than lanes (k > 64)."""
+    if rerank_top_k is None:
+        return None
+    if not has_local_features:
+        raise ValueError(why_not)
+    if int(rerank_top_k) < 1:
+        raise ValueError(f"rerank_top_k must be >= 1 (got {rerank_top_k})")
+    if int(k) > 64:
+        raise ValueError(f"rerank_top_k takes k <= 64 (got k = {k})")
+    return int(rerank_top_k)
+
+
+def _camera_matrix(torch, K, dev):
+    """The camera matrix (3x3 array-like, or None) as the f64 [9] device tensor RANSAC takes."""
+    return None if K is None else torch.from_numpy(np.asarray(K, np.float64).reshape(9).copy()).to(dev)
+
+
+def _vit_engine(vit_state_dict, backbone, dev, vit_batch, vit_precise):
+    """The gates' ViT engine; vit_state_dict None: the synthetic weights of seed 0."""
+    from .vit import engine_for
+    from .weights import synthetic_state_dict
+    sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
+    # vit_precise: the split-bf16 ViT (MLG_VIT_SPLIT), whose descriptors follow the fp32
+    # network closely enough that the kNN ranks near-ties as the fp32 reference does
+    return engine_for(sd, backbone, device=dev, max_batch=vit_batch, precise=vit_precise)
+
+
 def decide_pairs(n, inl, ta, tb, f_num, limit, min_inliers, min_inlier_ratio, n_valid_t, gate_rej_t):
     """The verifier's decision rule (geometric_verification.py:602-620) and the floor gate
     (loop_closure_gate.py:91-98) for a chunk of pairs, on tensors of any one device: match
@@ -288,28 +311,6 @@ def decide_pairs(n, inl, ta, tb, f_num, limit, min_inliers, min_inlier_ratio, n_
     n_valid_t += ok.sum()
     gate_rej_t += (ok & ((f_num[ta] - f_num[tb]).abs() > limit)).sum()
     return ok
-
-
-def _ransac_pairs(torch, dev, KP, K, kp_all, m, n, la, lb):
-    """geometry.epipolar_ransac_device's whole result (model, mask, inliers, pose, status) for
-    the P pairs DeviceGate._ransac_inliers describes: the flat match arrays laid out on the
-    device without a host sync, one batched RANSAC (+ recoverPose when K is given)."""
-    from . import geometry
-    P = len(la)
-    sidx = torch.arange(KP, device=dev)
-    lv = sidx[None, :] < n[:, None]
-    la = torch.from_numpy(la).to(dev).long()
-    lb = torch.from_numpy(lb).to(dev).long()
-    offs = torch.zeros(P + 1, dtype=torch.int32, device=dev)
-    offs[1:] = torch.cumsum(n, 0)
-    dest = torch.where(lv, offs[:-1, None].long() + sidx[None, :], P * KP).view(-1)
-    m0 = torch.where(lv, m[:, :, 0].long(), 0)
-    m1 = torch.where(lv, m[:, :, 1].long(), 0)
-    k1 = kp_all.new_zeros(P * KP + 1, 2)
-    k2 = kp_all.new_zeros(P * KP + 1, 2)
-    k1.index_copy_(0, dest, kp_all[la[:, None], m0].view(-1, 2))
-    k2.index_copy_(0, dest, kp_all[lb[:, None], m1].view(-1, 2))
-    return geometry.epipolar_ransac_device(k1[:P * KP], k2[:P * KP], offs, K, 0, 3.0)
 
 
 class DeviceGate:
@@ -338,19 +339,13 @@ class DeviceGate:
         # rank holds the gathered [N, D] descriptors and judges its own rows.
         self.seq_radius, self.seq_threshold, self.seq_min_terms = _seq_args(seq_radius, seq_threshold, seq_min_terms, k)
         self.last_sequence = None
-        if rerank_top_k is not None:  # refused before anything is built
-            if not local_features:
-                raise ValueError("rerank_top_k needs the local features: local_features=True")
-            if int(rerank_top_k) < 1:
-                raise ValueError(f"rerank_top_k must be >= 1 (got {rerank_top_k})")
-            if int(k) > 64:
-                raise ValueError(f"rerank_top_k takes k <= 64 (got k = {k})")
+        self.rerank_top_k = _rerank_arg(rerank_top_k, k, local_features,
+                                        "rerank_top_k needs the local features: local_features=True")
         import torch
         from . import distributed as mdist
         from .lightglue import LightGlueGPU
         from .superpoint import SuperPointGPU
-        from .vit import engine_for
-        from .weights import backbone_config, synthetic_state_dict
+        from .weights import backbone_config
         self.torch, self.mdist = torch, mdist
         # the DINOv2 backbone: its width sizes the gather, descriptor and local-feature buffers
         self.backbone = backbone
@@ -372,22 +367,16 @@ class DeviceGate:
         self.sp_batch, self.lg_chunk, self.kp = sp_batch, lg_chunk, max_keypoints
         self.lg_tail = int(lg_tail)
         self.t_all = torch.as_tensor(np.asarray(timestamps, np.float64), device=self.dev)
-        from .vpr import floor_codes
         self.labels = np.asarray(floor_labels)
         # equality codes for the retrieval floor check and the verifier skip (Python ==
         # semantics: 1 == 1.0, NaN != NaN, None = no label), the numeric labels for the
         # gate's |floor_i - floor_j| > limit (loop_closure_gate.py:91-98; NaN never rejects)
-        lab = list(self.labels.tolist()) if self.labels.dtype != object else list(self.labels)
-        codes, has = floor_codes(lab)
-        self.h_codes, self.h_has = np.asarray(codes), np.asarray(has, np.uint8)
-        self.f_all = torch.as_tensor(codes, device=self.dev)
-        self.hf_all = torch.as_tensor(has, dtype=torch.uint8, device=self.dev)
-        num = np.array([np.nan if v is None else float(v) for v in lab], np.float64)
-        self.f_num = torch.as_tensor(num, device=self.dev)
-        sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
-        # vit_precise: the split-bf16 ViT (MLG_VIT_SPLIT), whose descriptors follow the fp32
-        # network closely enough that the kNN ranks near-ties as the fp32 reference does
-        self.eng = engine_for(sd, backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise)
+        lab = gate_plan.label_list(self.labels)
+        self.h_codes, self.h_has = gate_plan.floor_codes(lab)  # int64, uint8
+        self.f_all = torch.as_tensor(self.h_codes, device=self.dev)
+        self.hf_all = torch.as_tensor(self.h_has, device=self.dev)
+        self.f_num = torch.as_tensor(gate_plan.numeric_labels(lab), device=self.dev)
+        self.eng = _vit_engine(vit_state_dict, backbone, self.dev, vit_batch, vit_precise)
         self.gather = mdist.RowGather(N, EMBED, world, self.dev)
         self.desc_loc = (self.gather.out[self.lo:self.hi] if world == 1
                          else torch.empty(self.n_local, EMBED, device=self.dev))
@@ -404,9 +393,7 @@ class DeviceGate:
         # verifier (mlg_rerank_gate).  None: the stage does not exist.  With several ranks the
         # bank of local features is all-gathered: every rank then holds all N keyframes'
         # [528, EMBED] f32 features (1.6 MB per keyframe at ViT-B)
-        self.rerank_top_k = None
-        if rerank_top_k is not None:
-            self.rerank_top_k = int(rerank_top_k)
+        if self.rerank_top_k is not None:
             self.feat_gather = (mdist.RowGather(N, self.eng.n_local * EMBED, world, self.dev) if world > 1
                                 else None)
         self.last_rerank = None
@@ -420,20 +407,17 @@ class DeviceGate:
         self.max_pairs = max_pairs  # verify only the first max_pairs pairs of the global list (bench sub-runs)
         if verify:
             self.fx = mdist.FeatureExchange(N, world, rank) if world > 1 else None
-            self.K = (torch.from_numpy(np.asarray(K, np.float64).reshape(9).copy()).to(self.dev)
-                      if K is not None else None)
+            self.K = _camera_matrix(torch, K, self.dev)
         if verify and matcher == 'loftr':
             from .loftr import LoFTRGPU
             self.lf = LoFTRGPU(device=self.dev, feature_batch=16)
         elif verify:
-            KP = max_keypoints
-            self.sp = SuperPointGPU(device=self.dev, max_num_keypoints=KP)
+            self.sp = SuperPointGPU(device=self.dev, max_num_keypoints=max_keypoints)
             self.lg = LightGlueGPU(device=self.dev)
             # this rank's keyframes' features; with world > 1 each rank then receives the
             # features of exactly the keyframes its verification slice touches
-            self.kp_loc = torch.empty(self.n_local, KP * 2, device=self.dev)
-            self.ds_loc = torch.empty(self.n_local, KP * 256, device=self.dev)
-            self.cnt_loc = torch.zeros(self.n_local, 1, dtype=torch.int32, device=self.dev)
+            self.feats = lg_pairs.FeatureTable(self.n_local, max_keypoints, self.dev)
+            self.kp_loc, self.ds_loc, self.cnt_loc = self.feats.kp, self.feats.ds, self.feats.cnt
         # overlap=True: the step on a high-priority stream, SuperPoint on a side stream under
         # the ViT and the kNN, each LightGlue chunk's RANSAC on a side stream under the next
         # chunk (step, _step, _verify_lightglue).  overlap=False: everything on the caller's
@@ -442,7 +426,6 @@ class DeviceGate:
         # lg_dedup=False: LightGlue on every ordered pair, not once per unordered pair.
         self.overlap, self.lg_dedup = bool(overlap), bool(lg_dedup)
         self._hi = self._sp_stream = self._side = None  # made by the first overlapped step
-        self.last = {}
         # record=True: step() keeps every verified ordered pair's (a, b, matches, inliers,
         # is_valid) in self.last_pair_results (host arrays in verification order)
         self.record = record
@@ -485,7 +468,7 @@ class DeviceGate:
         # the CUs its LayerNorm / attention launches leave free (same-box ABAB, profiles/
         # r06u_ab_sp_under_vit.txt: -0.4 % step time, counts identical).  The LightGlue stage
         # waits on its event.  overlap=False: SuperPoint after them on this stream.
-        sp_ev = self._extract_side(np.arange(self.n_local)) if lightglue and self.overlap else None
+        sp_ev = self._extract_side() if lightglue and self.overlap else None
         self.eng.forward_into(self.frames, self.desc_loc, self.local_feats)
         if self.world > 1:
             self.gather(self.desc_loc)  # RCCL all-gather of the descriptors over xGMI
@@ -540,7 +523,7 @@ class DeviceGate:
         if sp_ev is not None:
             torch.cuda.current_stream(self.dev).wait_event(sp_ev)
         elif lightglue:
-            self._extract_rows(np.arange(self.n_local))
+            self.feats.fill(self.sp, self.frames, 0, self.sp_batch)
         if self.verifier_floor_gating:  # the verifier's skip rule on floors
             same = gate_plan.same_floor(pa_h, pb_h, self.h_codes, self.h_has)
             out["skipped_floor_mismatch"] = int((~same).sum())
@@ -558,34 +541,11 @@ class DeviceGate:
             pa, pb = pa_h, pb_h
         return self._verify_lightglue(pa, pb, out)
 
-    def _extract_rows(self, rows):
-        """SuperPoint of the local keyframes `rows` (host int array, any order) into the
-        feature tables, in batches of sp_batch on the current stream.  Per-frame results do
-        not depend on which frames share a batch."""
-        torch = self.torch
-        for b0 in range(0, len(rows), self.sp_batch):
-            r = rows[b0:b0 + self.sp_batch]
-            if len(r) == r[-1] - r[0] + 1:  # a contiguous run: a view, no gather
-                fr, dst = self.frames[int(r[0]):int(r[-1]) + 1], slice(int(r[0]), int(r[-1]) + 1)
-            else:
-                dst = torch.from_numpy(np.ascontiguousarray(r, np.int64)).to(self.dev)
-                fr = self.frames.index_select(0, dst)
-            kp, _, ds, _, cnt = self.sp.extract_device(fr)
-            if isinstance(dst, slice):
-                self.kp_loc[dst].copy_(kp.view(len(r), -1))
-                self.ds_loc[dst].copy_(ds.view(len(r), -1))
-                self.cnt_loc[dst, 0].copy_(cnt)
-            else:
-                self.kp_loc.index_copy_(0, dst, kp.view(len(r), -1))
-                self.ds_loc.index_copy_(0, dst, ds.view(len(r), -1))
-                self.cnt_loc.index_copy_(0, dst, cnt.view(-1, 1).to(self.cnt_loc.dtype))
-
     def _verify_lightglue(self, pa, pb, out):
         """SuperPoint features (local table or need-driven exchange) -> LightGlue (once per
         unordered pair with lg_dedup) -> RANSAC + decision + floor gate per ordered pair, for
         this rank's slice (pa, pb) of the pair list (host int32 arrays); fills `out`."""
         torch = self.torch
-        dedup = self.lg_dedup
         self.last_pairs = (pa, pb)
         # features of the keyframes the pairs touch: the local table (world 1), or the
         # need-driven exchange (row k of the compact tables = keyframe need[k])
@@ -600,18 +560,12 @@ class DeviceGate:
             local = lambda x: np.asarray(x, np.int32)  # noqa: E731
         kp_all = kp_t.view(nf, self.kp, 2)
         ds_all = ds_t.view(nf, self.kp, 256)
-        # LightGlue once per UNORDERED pair: it is symmetric in its two images (shared
-        # weights; self / cross blocks, dual-softmax assignment, early stopping and pruning
-        # treat both alike), so (b, a) is (a, b) with the image roles exchanged and the
-        # matches re-sorted by the new image0 index (mlg_lg_orient_matches).  Every ORDERED
-        # pair still gets its own RANSAC on its own match order and its own decision, as
-        # verify_with_semantics gives each (query, match) (geometric_verification.py:688-744).
-        ua, ub, inv, swap_all, order = gate_plan.unordered_plan(pa, pb, self.N, dedup)
-        chunk = self.last_lg_chunk = self._lg_chunk_for(len(ua))
-        starts, bounds = gate_plan.chunk_starts(len(ua), chunk, self.lg_tail, inv[order])
-        out["pairs_matched_lightglue"] = len(ua)
-        ua, ub = local(ua), local(ub)  # LightGlue indexes the feature tables
         counts = cnt_t.view(-1).cpu().numpy()
+
+        def chunk_for(n_unordered):  # the pairs LightGlue runs on are known inside lg_pairs
+            out["pairs_matched_lightglue"] = n_unordered
+            self.last_lg_chunk = self._lg_chunk_for(n_unordered)
+            return self.last_lg_chunk
         # RANSAC of chunk c runs on a side stream while LightGlue matches chunk c + 1 on
         # this one (mlg_lightglue waits on its stream once per layer; the side stream
         # fills those gaps and the CUs the small RANSAC / assignment grids leave idle).
@@ -619,17 +573,9 @@ class DeviceGate:
         main = torch.cuda.current_stream(self.dev)
         side = self._side if self.overlap else main
         n_valid_t, gate_rej_t, rec = self._tallies()
-        for ci in range(len(starts) - 1):
-            c0, c1 = starts[ci], starts[ci + 1]
-            mu, su, nu, _ = self.lg.match_device(kp_all, ds_all, counts, ua[c0:c1], ub[c0:c1])
-            sel = order[bounds[ci]:bounds[ci + 1]]  # the ordered pairs of these unordered ones
+        for sel, m, n in lg_pairs.oriented_matches(self.lg, kp_all, ds_all, counts, pa, pb, self.N, chunk_for,
+                                                   self.lg_tail, self.lg_dedup, local):
             ca, cb = pa[sel], pb[sel]
-            if dedup:
-                rows = torch.from_numpy((inv[sel] - c0).astype(np.int32)).to(self.dev)
-                sw = torch.from_numpy(swap_all[sel]).to(self.dev)
-                m, _, n = _native.ops().lg_orient(mu, su, nu, rows, sw)
-            else:
-                m, n = mu, nu
             ready = torch.cuda.Event()
             ready.record(main)
             with torch.cuda.stream(side):
@@ -639,7 +585,7 @@ class DeviceGate:
                 # (every host -> device copy before the RANSAC launch: a copy waits for its stream)
                 ta = torch.from_numpy(ca).to(self.dev).long()  # global keyframe indices
                 tb = torch.from_numpy(cb).to(self.dev).long()
-                inl = self._ransac_inliers(kp_all, m, n, local(ca), local(cb))
+                inl = lg_pairs.ransac_pairs(self.K, kp_all, m, n, local(ca), local(cb))[2]
                 ok = decide_pairs(n, inl, ta, tb, self.f_num, self.limit, self.min_inliers, self.min_inlier_ratio,
                                   n_valid_t, gate_rej_t)
                 if rec is not None:
@@ -685,27 +631,19 @@ class DeviceGate:
         per = _native.lightglue_workspace_bytes(1024, self.kp) / 1024 + self._RANSAC_PAIR_BYTES
         return gate_plan.auto_chunk(avail, per, n_pairs)
 
-    def _extract_side(self, rows):
-        """_extract_rows on the SuperPoint side stream, after everything already queued on
-        the current stream; returns the event the consumers of those rows wait on."""
+    def _extract_side(self):
+        """SuperPoint of every local keyframe into the feature table on the SuperPoint side
+        stream, after everything already queued on the current stream; returns the event the
+        consumers of the table wait on."""
         torch = self.torch
         main = torch.cuda.current_stream(self.dev)
         sps = self._sp_stream
         sps.wait_stream(main)
         with torch.cuda.stream(sps):
-            self._extract_rows(rows)
+            self.feats.fill(self.sp, self.frames, 0, self.sp_batch)
         done = torch.cuda.Event()
         done.record(sps)
         return done
-
-    def _ransac_inliers(self, kp_all, m, n, la, lb):
-        """Inlier counts [P] of one batched RANSAC (+ recoverPose when K is given) over the
-        matched keypoints of P pairs: matches m [P, kp, 2] with counts n [P] between rows
-        la / lb (host int arrays) of the feature table kp_all.  The flat match arrays are
-        laid out on the device without a host sync (no nonzero): pair p's matches go to
-        [offs[p], offs[p] + n[p]) of a buffer of P * kp rows (RANSAC reads each pair's own
-        range only), the padding of the match lists to one dummy row past the end."""
-        return _ransac_pairs(self.torch, self.dev, self.kp, self.K, kp_all, m, n, la, lb)[2]
 
     def _verify_loftr(self, pa_t, pb_t, out):
         """verify_with_semantics with GeometricVerifier('loftr') on this rank's slice of the
@@ -813,11 +751,10 @@ class StreamingGate:
         if not 1 <= int(k) <= 32:  # refused before anything is built
             raise ValueError(f"StreamingGate takes k in [1, 32] (got k = {k})")
         import torch
-        from . import retrieval, stream_plan
+        from . import retrieval
         from .lightglue import LightGlueGPU
         from .superpoint import SuperPointGPU
-        from .vit import engine_for
-        from .weights import backbone_config, synthetic_state_dict
+        from .weights import backbone_config
         self.torch = torch
         self.dev = torch.device(device)
         self.capacity, self.k = int(capacity), int(k)
@@ -827,18 +764,13 @@ class StreamingGate:
                                           retrieval_floor_gating, self.dev)
         self.plan = stream_plan.StreamPlan(self.capacity, self.k, strict_mode, verifier_floor_gating, verify,
                                            min_inliers, min_inlier_ratio)
-        sd = vit_state_dict if vit_state_dict is not None else synthetic_state_dict(0, backbone)
-        self.eng = engine_for(sd, backbone, device=self.dev, max_batch=vit_batch, precise=vit_precise)
-        self.K = None
+        self.eng = _vit_engine(vit_state_dict, backbone, self.dev, vit_batch, vit_precise)
+        self.K = _camera_matrix(torch, K, self.dev) if self.verify else None
         if self.verify:
-            self.K = (torch.from_numpy(np.asarray(K, np.float64).reshape(9).copy()).to(self.dev)
-                      if K is not None else None)
             self.sp = SuperPointGPU(device=self.dev, max_num_keypoints=self.kp)
             self.lg = LightGlueGPU(device=self.dev)
             # every keyframe's SuperPoint features, extracted once when it arrives
-            self.kp_tab = torch.empty(self.capacity, self.kp, 2, device=self.dev)
-            self.ds_tab = torch.empty(self.capacity, self.kp, 256, device=self.dev)
-            self.cnt_tab = torch.zeros(self.capacity, dtype=torch.int32, device=self.dev)
+            self.feats = lg_pairs.FeatureTable(self.capacity, self.kp, self.dev)
         self.h_kpcount = np.zeros(self.capacity, np.int32)
         self.frame_shape = None
         # ordered pairs that have gone through RANSAC, ever: no pair does twice
@@ -879,7 +811,6 @@ class StreamingGate:
         is given, of the pairs every stage newly accepts) and 'retracted' (arrays a, b of the
         pairs accepted earlier whose entry a better match has now pushed out)."""
         torch, dev, k = self.torch, self.dev, self.k
-        from . import stream_plan
         # everything is checked before the first launch
         try:
             frames = _native.device_frames(frames)
@@ -887,7 +818,7 @@ class StreamingGate:
             raise ValueError(str(e))
         B = int(frames.shape[0])
         ts = np.asarray(timestamps, np.float64).reshape(-1)
-        labels = stream_plan.label_list(floor_labels)
+        labels = gate_plan.label_list(floor_labels)
         if B < 1 or len(ts) != B or len(labels) != B:
             raise ValueError(f"{B} frames, {len(ts)} timestamps, {len(labels)} floor labels")
         n_old, n_new = self.n, self.n + B
@@ -905,19 +836,14 @@ class StreamingGate:
         self.eng.forward_into(frames, desc, None)
         self._mark("vit")
         if self.verify:
-            for b0 in range(0, B, self.sp_batch):
-                kp, _, ds, _, cnt = self.sp.extract_device(frames[b0:b0 + self.sp_batch])
-                dst = slice(n_old + b0, n_old + b0 + kp.shape[0])
-                self.kp_tab[dst].copy_(kp)
-                self.ds_tab[dst].copy_(ds)
-                self.cnt_tab[dst].copy_(cnt)
+            self.feats.fill(self.sp, frames, n_old, self.sp_batch)
         self._mark("superpoint")
         inserted, ev_idx, n_ev = self.knn.append(desc, torch.from_numpy(ts).to(dev), torch.from_numpy(codes).to(dev),
                                                  torch.from_numpy(has).to(dev))
         self._mark("knn_append")
 
         # 4: which old rows changed (4 B per old row), then those rows and the new ones in one
-        # transfer: idx | sim bits | valid | count | n_evicted | evicted_idx | keypoint count
+        # transfer (stream_plan.PACKED_COLUMNS)
         rows = self.plan.changed_rows(inserted.cpu().numpy(), n_old, n_new)
         rt = torch.from_numpy(rows).to(dev)
         fresh = rt >= n_old
@@ -926,14 +852,14 @@ class StreamingGate:
         nev = torch.where(fresh, 0, n_ev[old]) if n_old else torch.zeros_like(rt, dtype=torch.int32)
         ev = (torch.where(fresh[:, None], -1, ev_idx[old]) if n_old
               else torch.full((len(rows), k), -1, dtype=torch.int32, device=dev))
-        kpc = self.cnt_tab[rt] if self.verify else torch.zeros_like(rt, dtype=torch.int32)
-        packed = torch.cat([self.knn.idx[rt], self.knn.sim[rt].view(torch.int32), i32(self.knn.valid[rt]),
-                            self.knn.count[rt][:, None], i32(nev)[:, None], i32(ev), i32(kpc)[:, None]], 1).cpu().numpy()
-        r_idx, r_sim = packed[:, :k], packed[:, k:2 * k].copy().view(np.float32)
-        r_valid, r_count, r_nev = packed[:, 2 * k:3 * k].astype(np.uint8), packed[:, 3 * k], packed[:, 3 * k + 1]
-        r_ev = packed[:, 3 * k + 2:4 * k + 2]
-        self.h_kpcount[n_old:n_new] = packed[len(rows) - B:, 4 * k + 2]
-        up = self.plan.update(n_new, rows, r_idx, r_sim, r_valid, r_count, r_nev, r_ev)
+        kpc = self.feats.cnt.view(-1)[rt] if self.verify else torch.zeros_like(rt, dtype=torch.int32)
+        cols = {"idx": self.knn.idx[rt], "sim": self.knn.sim[rt].view(torch.int32), "valid": i32(self.knn.valid[rt]),
+                "count": self.knn.count[rt], "n_evicted": i32(nev), "evicted": i32(ev), "kp_count": i32(kpc)}
+        packed = torch.cat([cols[name] if wide else cols[name][:, None]
+                            for name, wide in stream_plan.PACKED_COLUMNS], 1)
+        r = stream_plan.unpack(packed.cpu().numpy(), k)
+        self.h_kpcount[n_old:n_new] = r["kp_count"][len(rows) - B:]
+        up = self.plan.update(n_new, rows, r["idx"], r["sim"], r["valid"], r["count"], r["n_evicted"], r["evicted"])
         self._mark("transfer_and_plan")
 
         # 5-6: LightGlue under the canonical orientation and RANSAC on the new ordered pairs
@@ -962,21 +888,17 @@ class StreamingGate:
     def _verify_pairs(self, pa, pb):
         """(matches int32 [P], inliers int32 [P], pose f64 [P, 4, 4] or None) of the ordered
         pairs (pa, pb): LightGlue once per unordered (min, max) pair and mlg_lg_orient_matches,
-        then one RANSAC per ordered pair, as DeviceGate._verify_lightglue runs them."""
-        torch, dev = self.torch, self.dev
-        ua, ub, inv, swap_all, order = self.plan.canonical(pa, pb)
-        starts, bounds = gate_plan.chunk_starts(len(ua), self.lg_chunk, 0, inv[order])
+        then one RANSAC per ordered pair, as DeviceGate._verify_lightglue runs them (the same
+        lg_pairs.oriented_matches, over the keyframes seen)."""
+        torch = self.torch
+        kp_all = self.feats.kp.view(self.capacity, self.kp, 2)
+        ds_all = self.feats.ds.view(self.capacity, self.kp, 256)
         parts = []
-        for ci in range(len(starts) - 1):
-            c0, c1 = starts[ci], starts[ci + 1]
-            mu, su, nu, _ = self.lg.match_device(self.kp_tab, self.ds_tab, self.h_kpcount, ua[c0:c1], ub[c0:c1])
-            sel = order[bounds[ci]:bounds[ci + 1]]
-            rows = torch.from_numpy((inv[sel] - c0).astype(np.int32)).to(dev)
-            sw = torch.from_numpy(swap_all[sel]).to(dev)
-            m, _, n = _native.ops().lg_orient(mu, su, nu, rows, sw)
+        for sel, m, n in lg_pairs.oriented_matches(self.lg, kp_all, ds_all, self.h_kpcount, pa, pb, max(self.n, 1),
+                                                   self.lg_chunk):
             self._mark("lightglue")
-            _, _, inl, pose, _ = _ransac_pairs(torch, dev, self.kp, self.K, self.kp_tab, m, n,
-                                               np.asarray(pa[sel], np.int32), np.asarray(pb[sel], np.int32))
+            _, _, inl, pose, _ = lg_pairs.ransac_pairs(self.K, kp_all, m, n, np.asarray(pa[sel], np.int32),
+                                                       np.asarray(pb[sel], np.int32))
             self._mark("ransac")
             self.ransac_pairs += len(sel)
             parts.append((sel, n, inl, pose))
@@ -985,11 +907,7 @@ class StreamingGate:
         has_pose = parts[0][3] is not None
         if has_pose:
             cols.append(torch.cat([p[3] for p in parts]).view(-1, 16))
-        host = torch.cat(cols, 1).cpu().numpy()
-        n_m, n_i = np.zeros(len(pa), np.int32), np.zeros(len(pa), np.int32)
-        n_m[sel], n_i[sel] = host[:, 0].astype(np.int32), host[:, 1].astype(np.int32)
-        pose = None
-        if has_pose:
-            pose = np.zeros((len(pa), 4, 4), np.float64)
-            pose[sel] = host[:, 2:].reshape(-1, 4, 4)
-        return n_m, n_i, pose
+        # the chunks' sel together are a permutation of the pairs: back to (pa, pb)'s order
+        host = torch.cat(cols, 1).cpu().numpy()[np.argsort(sel)]
+        pose = host[:, 2:].reshape(-1, 4, 4) if has_pose else None
+        return host[:, 0].astype(np.int32), host[:, 1].astype(np.int32), pose

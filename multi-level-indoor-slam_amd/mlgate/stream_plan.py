@@ -1,57 +1,45 @@
-"""StreamingGate's host plan: the floor codes as labels arrive, which ordered pairs are live,
-which are new and bound for the verifier, which were evicted, what every verified pair's
-result was, and the cumulative counts.  numpy only -- no device, no native library -- so every
-decision here is checked on the CPU (tests/test_stream_plan_cpu.py); mlgate.pipeline runs the
-device work this plan drives.  The batch rules are not restated: the pairs, the verifier's
-floor skip and the canonical orientation come from gate_plan.
+"""StreamingGate's host plan: the floor codes as labels arrive, the format of the changed-rows
+transfer, which ordered pairs are live, which are new and bound for the verifier, which were
+evicted, what every verified pair's result was, and the cumulative counts.  numpy only -- no
+device, no native library -- so every decision here is checked on the CPU
+(tests/test_stream_plan_cpu.py); mlgate.pipeline runs the device work this plan drives.  The
+batch rules are not restated: the floor coder, the pairs, the verifier's floor skip and the
+canonical orientation come from gate_plan.
 """
 import numpy as np
 
 from . import gate_plan
+from .gate_plan import FloorCoder
 
 COUNT_KEYS = ("matches", "retrieval_floor_rejected", "skipped_floor_mismatch", "verifier_invalid",
               "gate_rejected_cross_floor", "pairs_verified", "verified_valid", "accepted")
 
 
-class FloorCoder:
-    """vpr.floor_codes across appends: the codes of the labels seen so far are those
-    floor_codes gives on the whole list -- labels that compare equal in Python share a code
-    (1 and 1.0 included), every NaN gets its own, None is "no label" (has = 0)."""
-
-    def __init__(self):
-        self.seen, self.nxt = {}, 0
-
-    def extend(self, labels):
-        """(codes int64, has uint8) of the new labels."""
-        codes = np.zeros(len(labels), np.int64)
-        has = np.ones(len(labels), np.uint8)
-        for i, f in enumerate(labels):
-            if f is None:
-                has[i] = 0
-                continue
-            if isinstance(f, (float, np.floating)) and f != f:
-                codes[i] = self.nxt
-                self.nxt += 1
-                continue
-            key = f.item() if isinstance(f, np.generic) else f
-            c = self.seen.get(key)
-            if c is None:
-                c = self.seen[key] = self.nxt
-                self.nxt += 1
-            codes[i] = c
-        return codes, has
+# The changed rows of an append come to the host in one int32 transfer whose columns are
+# these, in this order: (name, wide) with wide = k columns ([R, k]), else one ([R]).  sim
+# travels as its float32 bits.
+PACKED_COLUMNS = (("idx", True), ("sim", True), ("valid", True), ("count", False), ("n_evicted", False),
+                  ("evicted", True), ("kp_count", False))
 
 
-def label_list(floor_labels):
-    """The labels as Python objects, as DeviceGate reads them (an object array keeps its
-    elements; any other array goes through tolist)."""
-    lab = np.asarray(floor_labels)
-    return list(lab) if lab.dtype == object else list(lab.tolist())
+def unpack(packed, k):
+    """The transfer (int32 [R, 4 k + 3]) -> {name: array} over PACKED_COLUMNS: sim as float32,
+    valid as uint8, the rest int32."""
+    width = sum(k if wide else 1 for _, wide in PACKED_COLUMNS)
+    if packed.shape[1] != width:
+        raise ValueError(f"{packed.shape[1]} packed columns, {width} expected at k = {k}")
+    out, c0 = {}, 0
+    for name, wide in PACKED_COLUMNS:
+        out[name] = packed[:, c0:c0 + k] if wide else packed[:, c0]
+        c0 += k if wide else 1
+    out["sim"] = out["sim"].copy().view(np.float32)
+    out["valid"] = out["valid"].astype(np.uint8)
+    return out
 
 
 def verifier_ok(n, inl, min_inliers, min_inlier_ratio):
     """The verifier's decision rule (geometric_verification.py:602-620) on host integers: the
-    same float64 ratio and comparisons as pipeline.decide_pairs."""
+    same float64 ratio and comparisons as pipeline.decide_pairs (tests/test_gate_plan_cpu.py)."""
     n, inl = np.asarray(n, np.int64), np.asarray(inl, np.int64)
     ratio = inl.astype(np.float64) / np.maximum(n, 1).astype(np.float64)
     return (n >= 5) & (inl >= min_inliers) & (ratio >= min_inlier_ratio)
@@ -92,13 +80,13 @@ class StreamPlan:
     def add_labels(self, floor_labels):
         """The new keyframes' labels -> (codes int64, has uint8) for the device; also keeps the
         numeric labels of the gate's |floor_i - floor_j| > limit (None -> NaN, never rejects)."""
-        lab = label_list(floor_labels)
+        lab = gate_plan.label_list(floor_labels)
         lo, hi = self.labelled, self.labelled + len(lab)
         if hi > self.capacity:
             raise ValueError(f"{hi} keyframes exceed the capacity {self.capacity}")
         codes, has = self.coder.extend(lab)
         self.codes[lo:hi], self.has[lo:hi] = codes, has
-        self.num[lo:hi] = [np.nan if v is None else float(v) for v in lab]
+        self.num[lo:hi] = gate_plan.numeric_labels(lab)
         self.labelled = hi
         return codes, has
 
@@ -163,11 +151,6 @@ class StreamPlan:
         acc = np.asarray(ev_acc, bool)
         return {"new": (new_a, new_b), "verify": (va, vb), "evicted": (ev_a, ev_b),
                 "retracted": (ev_a[acc], ev_b[acc])}
-
-    def canonical(self, pa, pb):
-        """gate_plan.unordered_plan over the keyframes seen: each ordered pair matches under its
-        (min, max) pair, so the oriented result is the batch's."""
-        return gate_plan.unordered_plan(pa, pb, max(self.n, 1))
 
     def _slots(self, pa, pb):
         hit = (self.idx[pa] == np.asarray(pb)[:, None]) & (np.arange(self.k)[None, :] < self.count[pa][:, None])

@@ -32,6 +32,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import numpy as np
 
 from . import _native, weights
+from .gate_plan import floor_codes  # the floor check's equality codes, stated once in gate_plan
 
 
 @dataclass
@@ -100,32 +101,6 @@ def _device_frames(images, device):
             raise ValueError("frames must be uint8")
         return t.to(device).contiguous()
     return torch.from_numpy(_as_frames(images)).to(device)
-
-
-def floor_codes(labels):
-    """Integer codes with the reference's equality semantics for the floor check
-    ``query_floor == match_floor`` (place_recognition.py:896-899): labels that compare
-    equal in Python share a code (1 and 1.0 included), every NaN gets its own code
-    (NaN != NaN), None marks "no label" (has = 0)."""
-    codes = np.zeros(len(labels), np.int64)
-    has = np.ones(len(labels), np.uint8)
-    seen = {}
-    nxt = 0
-    for i, f in enumerate(labels):
-        if f is None:
-            has[i] = 0
-            continue
-        if isinstance(f, (float, np.floating)) and f != f:
-            codes[i] = nxt
-            nxt += 1
-            continue
-        key = f.item() if isinstance(f, np.generic) else f
-        c = seen.get(key)
-        if c is None:
-            c = seen[key] = nxt
-            nxt += 1
-        codes[i] = c
-    return codes, has
 
 
 def _as_frames(images):

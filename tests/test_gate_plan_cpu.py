@@ -1,6 +1,6 @@
 """DeviceGate's host plan (mlgate.gate_plan) and its shared decision tail
-(mlgate.pipeline.decide_pairs) on the CPU: the pair list from the retrieval lists, the
-verifier's floor skip, the unordered-pair plan, chunk starts and bounds, the 'auto' chunk
+(mlgate.pipeline.decide_pairs, held to its host form stream_plan.verifier_ok) on the CPU:
+the pair list from the retrieval lists, the verifier's floor skip, the unordered-pair plan, chunk starts and bounds, the 'auto' chunk
 arithmetic, LoFTR's frame-slot cache -- against the oracle chain's fixture
 (tests/golden/gate_chain.npz, oracle.pipeline.gate_chain) and brute force.
 """
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from mlgate import gate_plan, synthetic
+from mlgate import gate_plan, stream_plan, synthetic
 from mlgate.pipeline import decide_pairs
 from mlgate.vpr import floor_codes
 from oracle import pipeline as opipe
@@ -75,6 +75,8 @@ def test_fixture_chain_through_the_plan_and_the_tail(chain, cfg):
         n, inl = (torch.from_numpy(chain[key][i[sel]]) for key in ("pair_matches", "pair_inliers"))
         ok = decide_pairs(n, inl, torch.from_numpy(pa[sel]).long(), torch.from_numpy(pb[sel]).long(), f_num, 0,
                           20, 0.25, n_valid_t, gate_rej_t)
+        # the host form of the rule (StreamingGate's) decides every pair as the device form does
+        assert np.array_equal(stream_plan.verifier_ok(n.numpy(), inl.numpy(), 20, 0.25), ok.numpy())
         rec.append((sel, n.numpy(), inl.numpy(), ok.numpy()))
     r = gate_plan.pair_records(pa, pb, rec)
     assert np.array_equal(r["is_valid"], chain["pair_valid"][i])
@@ -87,6 +89,36 @@ def test_fixture_chain_through_the_plan_and_the_tail(chain, cfg):
            "verifier_invalid": len(pa) - n_valid, "gate_rejected_cross_floor": gate_rej}
     got["total"] = sum(got.values())
     assert got == ref["counts"] == chain["counts"][cfg]
+
+
+def test_decision_rule_edges_device_form_equals_host_form():
+    """(matches, inliers, min_inliers) -> is_valid at the rule's edges (geometric_verification.py:
+    602-620: at least 5 matches, inliers >= min_inliers, inliers / matches >= 0.25), the same
+    from decide_pairs on CPU tensors and from stream_plan.verifier_ok."""
+    rows = [(0, 0, 0, False),      # no matches: the ratio's denominator is clamped, n < 5 decides
+            (0, 0, 20, False),
+            (4, 4, 0, False),      # every match an inlier, but fewer than 5 matches
+            (5, 5, 5, True),       # the first n that can pass
+            (5, 4, 5, False),
+            (80, 20, 20, True),    # ratio exactly 0.25 passes
+            (81, 20, 20, False),   # just under it
+            (80, 19, 19, False)]
+    f_num = torch.zeros(2, dtype=torch.float64)
+    for n_, inl_, min_inl, want in rows:
+        n, inl = torch.tensor([n_], dtype=torch.int32), torch.tensor([inl_], dtype=torch.int32)
+        z = torch.zeros(1, dtype=torch.int64)
+        n_valid_t, gate_rej_t = torch.zeros((), dtype=torch.int64), torch.zeros((), dtype=torch.int64)
+        ok = decide_pairs(n, inl, z, z + 1, f_num, 0, min_inl, 0.25, n_valid_t, gate_rej_t)
+        host = stream_plan.verifier_ok(np.array([n_], np.int32), np.array([inl_], np.int32), min_inl, 0.25)
+        assert ok.tolist() == host.tolist() == [want], (n_, inl_, min_inl)
+        assert int(n_valid_t) == int(want) and int(gate_rej_t) == 0
+    # all rows at once, one min_inliers: the two forms agree element by element
+    n = np.array([r[0] for r in rows], np.int32)
+    inl = np.array([r[1] for r in rows], np.int32)
+    z = torch.zeros(len(rows), dtype=torch.int64)
+    ok = decide_pairs(torch.from_numpy(n), torch.from_numpy(inl), z, z, f_num, 0, 5, 0.25,
+                      torch.zeros((), dtype=torch.int64), torch.zeros((), dtype=torch.int64))
+    assert np.array_equal(ok.numpy(), stream_plan.verifier_ok(n, inl, 5, 0.25))
 
 
 def test_pairs_from_retrieval_and_rerank_offsets():

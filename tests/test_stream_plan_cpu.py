@@ -1,6 +1,7 @@
-"""mlgate.stream_plan on the CPU: the incremental floor codes against vpr.floor_codes, and a
-host replay of a streamed sequence whose every prefix must give the plan exactly what
-gate_plan gives on that prefix's full lists.  Every comparison is exact."""
+"""mlgate.stream_plan on the CPU: the floor coder used incrementally against its one-shot use
+(floor_codes), the packed changed-rows format's round trip, and a host replay of a streamed
+sequence whose every prefix must give the plan exactly what gate_plan gives on that prefix's
+full lists.  Every comparison is exact."""
 import numpy as np
 import pytest
 
@@ -32,6 +33,42 @@ def test_incremental_floor_codes_one_label_at_a_time():
     parts = [coder.extend([f]) for f in LABELS]
     assert np.array_equal(np.concatenate([p[0] for p in parts]), want_codes)
     assert np.array_equal(np.concatenate([p[1] for p in parts]), want_has)
+
+
+# ------------------------------------------------------------ the packed transfer
+@pytest.mark.parametrize("k", [1, 3, 32])
+def test_packed_rows_round_trip(k):
+    """Named arrays concatenated in PACKED_COLUMNS' order come back from unpack unchanged: sim
+    bit for bit (NaN payloads, -0.0, infinities), negative idx / evicted entries, the widths
+    at k = 1 (a wide column is still [R, 1])."""
+    rng = np.random.default_rng(k)
+    R = 9
+    sim_bits = rng.integers(-2**31, 2**31, (R, k), dtype=np.int64).astype(np.int32)
+    # quiet NaN, -0.0, NaNs with payloads (0xffffffff among them), 0.0, +inf, a denormal
+    special = np.array([0x7fc00000, -2**31, 0x7fc00001, -1, 0, 0x7f800000, 1], np.int64).astype(np.int32)
+    sim_bits.reshape(-1)[:len(special)] = special
+    want = {"idx": rng.integers(-1, 5000, (R, k)).astype(np.int32), "sim": sim_bits,
+            "valid": rng.integers(0, 2, (R, k)).astype(np.int32), "count": rng.integers(0, k + 1, R).astype(np.int32),
+            "n_evicted": rng.integers(0, k + 1, R).astype(np.int32),
+            "evicted": rng.integers(-1, 5000, (R, k)).astype(np.int32),
+            "kp_count": rng.integers(0, 2049, R).astype(np.int32)}
+    want["idx"][0], want["evicted"][-1] = -1, -1
+    assert [name for name, _ in stream_plan.PACKED_COLUMNS] == list(want)
+    packed = np.concatenate([want[name] if wide else want[name][:, None]
+                             for name, wide in stream_plan.PACKED_COLUMNS], 1)
+    assert packed.shape == (R, 4 * k + 3) and packed.dtype == np.int32
+    got = stream_plan.unpack(packed, k)
+    assert list(got) == list(want)
+    for name, wide in stream_plan.PACKED_COLUMNS:
+        assert got[name].shape == ((R, k) if wide else (R,)), name
+    assert got["sim"].dtype == np.float32 and got["valid"].dtype == np.uint8
+    assert np.array_equal(got["sim"].view(np.int32), want["sim"])
+    for name in want:
+        if name != "sim":
+            assert np.array_equal(got[name], want[name]), name
+    assert np.isnan(got["sim"]).any() and np.signbit(got["sim"][got["sim"] == 0]).any()
+    with pytest.raises(ValueError):
+        stream_plan.unpack(packed[:, :-1], k)
 
 
 # ----------------------------------------------------------------------- replay
@@ -169,8 +206,9 @@ def test_replay_equals_the_batch_plan_on_every_prefix(seq, gating, vfg, strict):
         assert list(zip(va.tolist(), vb.tolist())) == [p for p in want_new if p in bound]
         assert not (set(zip(va.tolist(), vb.tolist())) & ever_verified)        # never twice
         ever_verified |= set(zip(va.tolist(), vb.tolist()))
-        # the canonical orientation is the batch's (min, max)
-        ua, ub, inv, swap, _ = plan.canonical(va, vb)
+        # the canonical orientation (StreamingGate's plan: unordered_plan over the keyframes
+        # seen) is the batch's (min, max)
+        ua, ub, inv, swap, _ = gate_plan.unordered_plan(va, vb, max(plan.n, 1))
         assert np.array_equal(ua[inv], np.minimum(va, vb)) and np.array_equal(ub[inv], np.maximum(va, vb))
         assert np.array_equal(swap, (va > vb).astype(np.uint8))
 
